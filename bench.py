@@ -15,7 +15,15 @@ synthetic (seeded), inputs are resident in HBM.  Protocol of the reference's gen
 293-338): a 64-token context is built first (untimed, whatever --warmup is), then W untimed warm-up tokens, then the timed
 region: K graph replays bracketed by barrier + synchronize, max over ranks.
 
-The same JSON line carries
+A plain run does only that and prints the headline line (metric, value, unit, higher_is_better, dtype, ms_per_step, config).
+--dump-outputs DIR writes what the last timed step returned to its caller, as float32 / float64 .npy files:
+  logits.npy        [1, vocab] logits of the last timed token (fp16 values, stored as float32)
+  next_token.npy    [1] the greedy token that step chose (stored as float64)
+The weights are seeded and greedy decoding starts from token 1, so the same arguments give the same inputs on every run.
+
+With --full the same JSON line also carries (each of these takes runs of its own)
+  steady_128        128 further timed tokens on the same graphs
+  multi_gpu         N > 1: devices, the layer's collective timed alone, per-rank roofline, N independent replicas
   roofline          the dominant kernel (the W4 GEMV): algorithmic bytes of all GEMV launches of one token / their
                     HIP-event-timed duration (the token's GEMV launches replayed back to back from a graph on the launch
                     stream; the event time includes the inter-kernel gaps, as rocprofv3's kernel-trace durations on this
@@ -72,7 +80,21 @@ def parse_args(argv=None):
     ap.add_argument("--no-per-kind", action="store_true", help="skip the per-launch-kind timing graphs")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip latency_protocol / prefill_2048 / finetune_step (the decode line and its roofline only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side record (PMC traffic, steady_128, roofline, multi-GPU diagnostics, latency_protocol, "
+                         "boundary_gemv, prefill / fine-tune GEMMs, model_13b / model_70b, cpu_baseline); the --no-* options "
+                         "narrow it.  Off: the headline decode line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (logits, next token) as DIR/<name>.npy")
     return ap.parse_args(argv)
+
+
+def dump_outputs(out_dir, eng):
+    """What the last timed step handed its caller: the logits row and the greedy next token, in float32 / float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy"), eng.logits.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "next_token.npy"), eng.tok.cpu().numpy().astype(np.float64))
 
 
 # ---------------------------------------------------------------------------------------------------- N > 1: self-launch
@@ -104,7 +126,7 @@ def cpu_baseline(shape, budget_s=24.0):
     import numpy as np
     import torch
     from oracle import qeft_oracle as O
-    torch.set_num_threads(os.cpu_count() or 1)
+    torch.set_num_threads(int(os.environ.get("OMP_NUM_THREADS") or 0) or os.cpu_count() or 1)   # a set thread budget holds
     cores = torch.get_num_threads()
     shapes = sorted({(shape.hidden, shape.hidden), (shape.inter, shape.hidden), (shape.hidden, shape.inter)})
     counts = {(shape.hidden, shape.hidden): 4, (shape.inter, shape.hidden): 2, (shape.hidden, shape.inter): 1}
@@ -456,7 +478,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # the PMC pass is a child process of its own and has to start BEFORE this process initialises the GPU
     traffic = None
-    if world == 1 and "RANK" not in os.environ and not args.no_traffic and not args.pmc_child:
+    if args.full and world == 1 and "RANK" not in os.environ and not args.no_traffic and not args.pmc_child:
         traffic = hbm_traffic_per_gemv_launch(args.model, args.bits, args.ckpt)
 
     import torch
@@ -584,6 +606,39 @@ def main():
     if oneshot_gave_up("the timed tokens"):
         dt = timed_tokens()
     last_tok = int(eng.tok.item())
+    if args.dump_outputs and rank == 0:         # before anything below replays the engine again
+        dump_outputs(args.dump_outputs, eng)
+    tp3 = bool(getattr(eng, "tp3", False))      # (the extras below free the engine)
+    out = None
+    if rank == 0:
+        ms = dt * 1e3 / args.steps
+        out = {
+            "metric": "decode tokens/sec, Llama-2-7B w4 g128 r128" if (args.model == "7b" and args.bits == 4 and not args.ckpt)
+            else f"decode tokens/sec, {shape.name} w{args.bits} g128 r128",
+            "value": round(args.steps / dt, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
+            "scaling": "strong" if world > 1 else "weak", "vs_baseline": None, "dtype": "f16",
+            "data": f"packed checkpoint {os.path.basename(args.ckpt)}, random token ids" if args.ckpt else "synthetic",
+            "config": {"workload": f"{shape.name} w{args.bits} g{shape.group_size} r{shape.n_out} full decode step, batch 1, "
+                                   f"greedy, KV context {ctx0}..{ctx0 + args.steps} tokens ({CONTEXT}-token context + "
+                                   f"{args.warmup} warm-up tokens before the timed region)",
+                       "layers": shape.n_layers, "hipgraph": graph_ok,
+                       "parallelism": ((f"tp{world}: q/k/v/gate/up row-sharded, o/down column-sharded + one all-reduce each "
+                                        f"(2 collectives per layer{', shared-GPU rehearsal' if shared else ''})")
+                                       if tp3 else
+                                       (f"tp{world}: every linear row-sharded, one all-gather each "
+                                        f"(4 collectives per layer{', shared-GPU rehearsal' if shared else ''})"))
+                       if group is not None else "single GPU",
+                       "build_s": round(t_build, 1), "last_token": last_tok},
+        }
+        if graph_capture_error:
+            out["graph_capture_error"] = graph_capture_error
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if group is not None:
+            dist.destroy_process_group()
+        return
     # steady_128: 128 further timed tokens on the same graphs (rewound to the protocol's context, one untimed pass first so that
     # nothing is captured inside the timed one) -- shows whether a short --steps run is representative
     steady = None
@@ -745,7 +800,6 @@ def main():
                                                "shared_device": bool(shared),
                                                "note": "N independent single-GPU engines (one sequence each, no collective), each rank timed "
                                                        "on its own; `value` above is ONE sequence decoded by all N ranks (tensor parallel)"})
-    tp3 = bool(getattr(eng, "tp3", False))      # (the extras below free the engine)
     extras = {}
     if world == 1 and not args.no_extras:
         # ---- the reference's per-token protocol: synchronize after every token, median / min, tokens/s = 1 / median
@@ -829,28 +883,6 @@ def main():
                 print(f"[bench] model_70b failed: {type(e).__name__}: {e}", file=sys.stderr)
 
     if rank == 0:
-        ms = dt * 1e3 / args.steps
-        out = {
-            "metric": "decode tokens/sec, Llama-2-7B w4 g128 r128" if (args.model == "7b" and args.bits == 4 and not args.ckpt)
-            else f"decode tokens/sec, {shape.name} w{args.bits} g128 r128",
-            "value": round(args.steps / dt, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
-            "scaling": "strong" if world > 1 else "weak", "vs_baseline": None, "dtype": "f16",
-            "data": f"packed checkpoint {os.path.basename(args.ckpt)}, random token ids" if args.ckpt else "synthetic",
-            "config": {"workload": f"{shape.name} w{args.bits} g{shape.group_size} r{shape.n_out} full decode step, batch 1, "
-                                   f"greedy, KV context {ctx0}..{ctx0 + args.steps} tokens ({CONTEXT}-token context + "
-                                   f"{args.warmup} warm-up tokens before the timed region)",
-                       "layers": shape.n_layers, "hipgraph": graph_ok,
-                       "parallelism": ((f"tp{world}: q/k/v/gate/up row-sharded, o/down column-sharded + one all-reduce each "
-                                        f"(2 collectives per layer{', shared-GPU rehearsal' if shared else ''})")
-                                       if tp3 else
-                                       (f"tp{world}: every linear row-sharded, one all-gather each "
-                                        f"(4 collectives per layer{', shared-GPU rehearsal' if shared else ''})"))
-                       if group is not None else "single GPU",
-                       "build_s": round(t_build, 1), "last_token": last_tok},
-        }
-        if graph_capture_error:
-            out["graph_capture_error"] = graph_capture_error
         if multi:
             out["multi_gpu"] = multi
         if steady:

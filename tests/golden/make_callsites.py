@@ -11,8 +11,8 @@ What is recorded (no source text, only names and counts):
     line, positional-argument count and keyword names;
   * `aliases`: `self.gemv = qeft_cuda.<fn>` style bindings (qlinear.py:223-234) together with the calls made through the
     alias (`self.gemv(...)`, `self.gemm(...)`): positional count and keyword names.
-tests/test_shim_callsites.py checks the shim (`qeft_cuda` at the repo root) against this file everywhere, and against a fresh
-parse wherever /root/reference exists.
+tests/test_shim_callsites.py checks the shim (`qeft_cuda` at the repo root) against this file; rerunning this script and
+diffing the JSON shows whether the file is still current.
 """
 import ast
 import json

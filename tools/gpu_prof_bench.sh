@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_bench
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $OUT/kt -o run --output-format csv -- python3 $OLDPWD/bench.py --no-traffic > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats -d $OUT/kt -o run --output-format csv -- python3 $OLDPWD/bench.py --full --no-traffic > $OUT/bench.json 2> $OUT/bench.err
 echo "rc=$?"
 cd $OLDPWD
 python3 tools/summarize_rocprof.py $OUT/kt gpurun_out/r04_bench_kernel_stats.txt

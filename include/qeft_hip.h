@@ -330,6 +330,42 @@ int qeft_token_begin(const void* embed, const void* tok, const void* rope_tab, c
                      int hidden, int vocab, int max_seq, qeft_stream_t stream);
 int qeft_token_end(const void* logits, void* tok, int* pos, int vocab, int greedy, qeft_stream_t stream);
 
+/* Verify pass of the decode engine (DecodeEngine.verify, assisted decoding): m = 1..8 tokens of ONE sequence at positions
+ * *pos .. *pos + m - 1 in one launch sequence of m-row launches (csrc/gemv_v3_multi.hip, csrc/decode_verify.hip).  Rows are
+ * contiguous; every entry rejects m outside 1..8 (QEFT_ERR_BATCH) and bad shapes before it touches the device.
+ * qeft_decode_linear_m: qeft_decode_linear on m rows -- x [m][k], y [m][n] (mode 1: [m][n/2]), residual / y (fp32) [m][n],
+ *   ssq_in [m][n_ssq_in], y_norm [m][n], ssq_out [m][qeft_decode_linear_blocks(n)].  The weights stream once for all rows;
+ *   m == 1 is the qeft_decode_linear launch itself.
+ * qeft_gemv_v3_check_extents_m: the host-side address enumeration of such a launch (count of out-of-range accesses, -1 for a
+ *   configuration the entry rejects; shrink_rows > 0: the negative control).
+ * qeft_token_begin_norm_m: qeft_token_begin_norm for tokens[m] (int64) at positions *pos + i: h32 [m][hidden], h_norm [m][hidden],
+ *   ssq_out [m][qeft_token_begin_norm_blocks(hidden)], rope_rows [m][128] (cos 64 | sin 64 of position *pos + i).
+ * qeft_rope_attn_decode_m: rotary + KV append of m rows + causal attention, query i over keys [0, *pos + i].  q / k / v rows are
+ *   qkv_stride elements apart, out rows out_stride; cos / sin: tab_rows == m -> row i (tab_stride floats apart) is position
+ *   *pos + i, tab_rows >= max_seq -> indexed by position.  n_split 1 / 2 / 4 / 8 blocks per kv head; n_split > 1 needs a
+ *   zeroed workspace of qeft_attn_m_workspace_bytes(n_heads, n_split, m) bytes (its counters re-arm themselves).
+ * qeft_lm_head_f16_m: qeft_lm_head_f16 on m rows: logits [m][vocab] from h32 [m][hidden]; the head streams once.
+ * qeft_verify_greedy: greedy: argmax a[i] of every logits row (lowest index among equal maxima), n = longest prefix with
+ *   a[i] == tokens[i + 1]; out_tokens[0..n] = tokens[1..n], a[n]; *n_accepted = n; *tok = a[n]; *pos += n + 1.
+ *   greedy == 0: *pos += m only. */
+int qeft_decode_linear_m(const void* x, const void* qweight, const void* sz_packed, const void* oweight, const void* bias,
+                         void* y, int n, int k, int group_size, int n_out, int mode, const void* residual,
+                         const float* ssq_in, int n_ssq_in, float eps, const void* gamma_out, void* y_norm, float* ssq_out,
+                         int m, qeft_stream_t stream);
+long long qeft_gemv_v3_check_extents_m(int n, int k, int group_size, int n_out, int m, int mode, int n_ssq_in, int shrink_rows);
+int qeft_token_begin_norm_m(const void* embed, const void* tokens, const void* rope_tab, const int* pos, void* h, void* rope_rows,
+                            const void* gamma, void* h_norm, float* ssq_out, int hidden, int vocab, int max_seq, int m,
+                            qeft_stream_t stream);
+int qeft_attn_m_workspace_bytes(int n_heads, int n_split, int m);
+int qeft_rope_attn_decode_m(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
+                            int tab_stride, int tab_rows, void* k_cache, void* v_cache, const int* pos, const int* out_pos,
+                            void* out, int out_stride, void* workspace, int n_split, int n_heads, int n_kv_heads, int max_seq,
+                            int m, qeft_stream_t stream);
+int qeft_lm_head_f16_m(const void* h32, const void* gamma, const void* weight, void* logits, int hidden, int vocab, float eps,
+                       int m, qeft_stream_t stream);
+int qeft_verify_greedy(const void* logits, const void* tokens, int m, int vocab, int greedy, void* out_tokens, int* n_accepted,
+                       void* tok, int* pos, qeft_stream_t stream);
+
 /* One-shot all-reduce of the tensor-parallel decode path (csrc/oneshot.hip; no reference counterpart --
  * the reference places whole layers on GPUs, qeft/utils/modelutils.py:21-57).  In-place fp32 sum of t[n] over `world` ranks
  * (one process per GPU) by ONE kernel per rank: every rank writes its partial as 8-byte {value, tag} granules into slot `rank`

@@ -70,6 +70,13 @@ SIGNATURES = {
     "qeft_single_query_attention_alibi": [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p],
     "qeft_single_query_attention_generic": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     "qeft_rope_attn_decode": [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "qeft_decode_linear_m": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, ctypes.c_float, _p, _p, _p, _i, _p],
+    "qeft_gemv_v3_check_extents_m": [_i, _i, _i, _i, _i, _i, _i, _i],
+    "qeft_token_begin_norm_m": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "qeft_attn_m_workspace_bytes": [_i, _i, _i],
+    "qeft_rope_attn_decode_m": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
+    "qeft_lm_head_f16_m": [_p, _p, _p, _p, _i, _i, ctypes.c_float, _i, _p],
+    "qeft_verify_greedy": [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p],
     "qeft_oneshot_mailbox_bytes": [_i, _i],
     "qeft_oneshot_max_world": [],
     "qeft_oneshot_mailbox_alloc": [_i, _i, ctypes.POINTER(ctypes.c_void_p)],
@@ -108,6 +115,7 @@ def lib():
             fn.restype = (ctypes.c_char_p if name in ("qeft_error_string", "qeft_last_variant") else
                           ctypes.c_longlong if name in ("qeft_gemm_w4_workspace_bytes", "qeft_gemm_w4_dx_workspace_bytes",
                                                        "qeft_gemv_v3_check_extents", "qeft_gemv_v3_check_extents_ckpt",
+                                                       "qeft_gemv_v3_check_extents_m",
                                                        "qeft_oneshot_mailbox_bytes") else _i)
         _lib = l
     return _lib

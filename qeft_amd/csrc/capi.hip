@@ -47,6 +47,19 @@ hipError_t sqa_generic_launch(const void* q, const void* k, const void* v, void*
 hipError_t token_begin_launch(const void* embed, const void* tok, const void* rope_tab, const int* pos, void* h,
                               void* rope_row, int hidden, int vocab, int max_seq, hipStream_t st);
 hipError_t token_end_launch(const void* logits, void* tok, int* pos, int vocab, int greedy, hipStream_t st);
+hipError_t gemv_v3_multi_launch(V3Args a, int mode, hipStream_t st);                                   // gemv_v3_multi.hip
+long long gemv_v3_count_out_of_range_multi(const V3Geom& G, int n_rows_have, int m, int mode, int n_ssq_in);
+hipError_t token_begin_norm_m_launch(const void* embed, const void* toks, const void* rope_tab, const int* pos, void* h,  // decode_verify.hip
+                                     void* rope_rows, const void* gamma, void* hnorm, float* ssq_out, int hidden, int vocab,
+                                     int max_seq, int m, hipStream_t st);
+size_t attn_m_workspace_bytes(int n_heads, int S, int m);
+hipError_t rope_attn_m_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
+                              int tab_stride, int tab_rows, void* kc, void* vc, const int* pos, const int* out_pos, void* out,
+                              int out_stride, void* ws, int n_heads, int n_kv, int max_seq, int S, int m, hipStream_t st);
+hipError_t lm_head_m_launch(const void* h32, const void* gamma, const void* W, void* logits, int H, int vocab, float eps, int m,
+                            hipStream_t st);
+hipError_t verify_greedy_launch(const void* logits, const void* tokens, int m, int vocab, int greedy, void* out_tokens, int* n_acc,
+                                void* tok, int* pos, hipStream_t st);
 extern unsigned long long* g_attn_dbg;
 hipError_t dequant_w4_launch(const void* qw, const void* scales, const void* zeros, const void* ow, void* out, int N,
                              int K, int G, int n_out, hipStream_t st);
@@ -847,5 +860,110 @@ int qeft_token_end(const void* logits, void* tok, int* pos, int vocab, int greed
     if (greedy && !aligned16(logits)) return QEFT_ERR_ALIGN;
     return finish(qeft::token_end_launch(logits, tok, pos, vocab, greedy, (hipStream_t)stream));
 }
+
+// ---- verify pass (m = 1..8 rows of one sequence): gemv_v3_multi.hip, decode_verify.hip
+static bool verify_m_ok(int m) { return m >= 1 && m <= 8; }
+
+int qeft_decode_linear_m(const void* x, const void* qweight, const void* sz_packed, const void* oweight, const void* bias,
+                         void* y, int n, int k, int group_size, int n_out, int mode, const void* residual,
+                         const float* ssq_in, int n_ssq_in, float eps, const void* gamma_out, void* y_norm, float* ssq_out,
+                         int m, qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (m == 1)
+        return qeft_decode_linear(x, qweight, sz_packed, oweight, bias, y, n, k, group_size, n_out, mode, residual, ssq_in, n_ssq_in,
+                                  eps, gamma_out, y_norm, ssq_out, stream);
+    if (!x || !qweight || !sz_packed || !y || (n_out > 0 && !oweight)) return QEFT_ERR_NULL;
+    if (!aligned16(x) || !aligned16(qweight) || !aligned16(sz_packed) || (n_out > 0 && !aligned16(oweight))) return QEFT_ERR_ALIGN;
+    qeft::V3Args a{};
+    if (int e = v3_geom(a.g, n, k, group_size, n_out, mode)) return e;
+    if (a.g.ngroups == 1 && k > 128) return QEFT_ERR_GROUP;            // per-channel scales: not an engine operand
+    if ((residual || gamma_out) && mode != qeft::V3_MODE_PLAIN) return QEFT_ERR_SHAPE;
+    if (gamma_out && (!residual || !y_norm || !ssq_out)) return QEFT_ERR_NULL;
+    if ((residual && !aligned16(residual)) || (gamma_out && !aligned16(gamma_out))) return QEFT_ERR_ALIGN;
+    if (ssq_in && (n_ssq_in < 1 || n_ssq_in > qeft::V3_MAX_SSQ)) return QEFT_ERR_SHAPE;
+    a.m = m;
+    a.x = (const qeft::f16*)x;
+    a.qw = (const uint8_t*)qweight;
+    a.szp = (const uint8_t*)sz_packed;
+    a.ow = (const uint8_t*)oweight;
+    a.bias = (const qeft::f16*)bias;
+    a.residual = (const float*)residual;
+    a.y = residual ? nullptr : (qeft::f16*)y;
+    a.y32 = residual ? (float*)y : nullptr;
+    a.ssq_in = ssq_in;
+    a.n_ssq_in = ssq_in ? n_ssq_in : 0;
+    a.eps = eps;
+    a.gamma_out = (const qeft::f16*)gamma_out;
+    a.ynorm = (qeft::f16*)y_norm;
+    a.ssq_out = ssq_out;
+    hipError_t e = qeft::gemv_v3_multi_launch(a, mode, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) return QEFT_ERR_SHAPE;
+    return finish(e);
+}
+
+long long qeft_gemv_v3_check_extents_m(int n, int k, int group_size, int n_out, int m, int mode, int n_ssq_in, int shrink_rows) {
+    qeft::V3Geom G{};
+    if (!verify_m_ok(m) || v3_geom(G, n, k, group_size, n_out, mode) != QEFT_OK) return -1;
+    if (G.ngroups == 1 && k > 128) return -1;
+    if (n_ssq_in < 0 || n_ssq_in > qeft::V3_MAX_SSQ || shrink_rows < 0 || shrink_rows % 16 != 0 || shrink_rows >= n) return -1;
+    // the one-row launch's accesses (weights, scales, outliers: the same for every m) + the m-row ones
+    return qeft::gemv_v3_count_out_of_range(G, n - shrink_rows, 0, false, 4) +
+           qeft::gemv_v3_count_out_of_range_multi(G, n - shrink_rows, m, mode, n_ssq_in);
+}
+
+int qeft_token_begin_norm_m(const void* embed, const void* tokens, const void* rope_tab, const int* pos, void* h, void* rope_rows,
+                            const void* gamma, void* h_norm, float* ssq_out, int hidden, int vocab, int max_seq, int m,
+                            qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (hidden < 8 || hidden % 8 != 0 || vocab < 1 || max_seq < 1) return QEFT_ERR_SHAPE;
+    if (!embed || !tokens || !rope_tab || !pos || !h || !rope_rows || !gamma || !h_norm || !ssq_out) return QEFT_ERR_NULL;
+    if (!aligned16(embed) || !aligned16(h) || !aligned16(gamma) || !aligned16(h_norm)) return QEFT_ERR_ALIGN;
+    return finish(qeft::token_begin_norm_m_launch(embed, tokens, rope_tab, pos, h, rope_rows, gamma, h_norm, ssq_out, hidden, vocab,
+                                                  max_seq, m, (hipStream_t)stream));
+}
+
+int qeft_attn_m_workspace_bytes(int n_heads, int n_split, int m) {
+    if (n_heads < 1 || n_heads > 4096 || n_split < 1 || n_split > 8 || !verify_m_ok(m)) return 0;
+    return (int)qeft::attn_m_workspace_bytes(n_heads, n_split, m);
+}
+
+int qeft_rope_attn_decode_m(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
+                            int tab_stride, int tab_rows, void* k_cache, void* v_cache, const int* pos, const int* out_pos,
+                            void* out, int out_stride, void* workspace, int n_split, int n_heads, int n_kv_heads, int max_seq,
+                            int m, qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0 || n_heads > 4096 || max_seq < 16 || max_seq % 16 != 0 ||
+        max_seq > 32768)
+        return QEFT_ERR_SHAPE;
+    if (tab_rows != m && tab_rows < max_seq) return QEFT_ERR_SHAPE;
+    if (tab_stride < 64 || qkv_stride < 1 || out_stride < 1 || (!out_pos && out_stride < n_heads * 128)) return QEFT_ERR_SHAPE;
+    if (n_split != 1 && n_split != 2 && n_split != 4 && n_split != 8) return QEFT_ERR_SHAPE;
+    if (!q || !k || !v || !cos_tab || !sin_tab || !k_cache || !v_cache || !pos || !out) return QEFT_ERR_NULL;
+    if (n_split > 1 && !workspace) return QEFT_ERR_NULL;
+    if (!aligned16(k_cache) || !aligned16(v_cache) || !aligned16(workspace)) return QEFT_ERR_ALIGN;
+    return finish(qeft::rope_attn_m_launch(q, k, v, qkv_stride, cos_tab, sin_tab, tab_stride, tab_rows, k_cache, v_cache, pos, out_pos,
+                                           out, out_stride, workspace, n_heads, n_kv_heads, max_seq, n_split, m, (hipStream_t)stream));
+}
+
+int qeft_lm_head_f16_m(const void* h32, const void* gamma, const void* weight, void* logits, int hidden, int vocab, float eps,
+                       int m, qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (vocab < 1 || hidden < 512 || hidden % 512 != 0) return QEFT_ERR_SHAPE;
+    if (!h32 || !gamma || !weight || !logits) return QEFT_ERR_NULL;
+    if (!aligned16(h32) || !aligned16(gamma) || !aligned16(weight)) return QEFT_ERR_ALIGN;
+    hipError_t e = qeft::lm_head_m_launch(h32, gamma, weight, logits, hidden, vocab, eps, m, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) return QEFT_ERR_SHAPE;
+    return finish(e);
+}
+
+int qeft_verify_greedy(const void* logits, const void* tokens, int m, int vocab, int greedy, void* out_tokens, int* n_accepted,
+                       void* tok, int* pos, qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (vocab < 1) return QEFT_ERR_SHAPE;
+    if (!pos || (greedy && (!logits || !tokens || !out_tokens || !n_accepted || !tok))) return QEFT_ERR_NULL;
+    if (greedy && !aligned16(logits)) return QEFT_ERR_ALIGN;
+    return finish(qeft::verify_greedy_launch(logits, tokens, m, vocab, greedy, out_tokens, n_accepted, tok, pos, (hipStream_t)stream));
+}
+
 
 }  // extern "C"

@@ -300,9 +300,9 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
                                                           const f16* xn_gamma, int K_, uint32_t nblk_rscap_flags, uint32_t setsq_setsr,
                                                           V3Tail a) {
     static_assert(BITS == 4 || BITS == 3, "4-bit checkpoint layout or the 3-bit extension layout (oracle: pack_w3)");
-    static_assert(MB == 1 || (MODE == V3_MODE_PLAIN && BITS == 4), "several batch rows: plain 4-bit launches only");
+    static_assert(MB == 1 || ((MODE == V3_MODE_PLAIN || !FL) && BITS == 4), "several batch rows: 4-bit; PAIR only in the engine's m-row form");
     static_assert(RSC >= 1 && RSC <= V3_MAX_RS && D >= 2, "row sets per block 1..4, at least two loads in flight per wave");
-    static_assert(FL || MB == 1, "the batch-row launches always come with flags");
+    // (MB == 2 && !FL: the decode engine's m-row launches with its fused epilogues, gemv_v3_multi.hip)
     static_assert(!XG || (MB == 2 && D >= 4), "x fragments from global memory: batch-row launches with a deep ring");
     typedef typename V3Val<MB>::type val_t;
     // the leading parameters arrive in SGPRs (kernarg preload); the tail is one batch of scalar loads issued here and waited
@@ -695,6 +695,75 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
         fold(acc[RSC - 1]);                    // the last (step, row set)
     }
     V3_STAMP(3);
+    if constexpr (MB == 2 && !FL) {
+        // ---- the decode engine's epilogues on m <= 8 batch rows (verify pass, gemv_v3_multi.hip).  Wave i owns batch row i
+        //      (NW == 8 >= m).  Per row, exactly the arithmetic of the one-row launch: its own rsqrt of its own producer sums
+        //      (ssq_in [m][n_ssq_in]), PAIR silu(gate) * up, fp32 residual in place, gamma_out -> ynorm and ssq_out [m][nblk].
+        //      The row's operands are requested here, in front of the barrier, so their latency hides behind the slowest wave.
+        constexpr int RB = 8;
+        if (kc < 2)
+            v3_static_for<0, RSC>([&](auto r) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) red[((size_t)(decltype(r)::value * NW + wave) * RB + 4 * kc + j) * 16 + nl] = acc[r][j];
+            });
+        const int i = wave, N = G.nsets * 16;
+        const bool row_ok = i < m, lane_row = lane < RS * 16;
+        float res = 0.f, gam = 0.f, s0 = 0.f, s1 = 0.f;
+        if (MODE == V3_MODE_PLAIN && residual && row_ok && lane_row) res = ((const float*)residual)[(size_t)i * N + set0 * 16 + lane];
+        if (MODE == V3_MODE_PLAIN && gamma_out && lane_row) gam = (float)((const f16*)gamma_out)[set0 * 16 + lane];
+        if (ssq_in && row_ok) {
+            // the one-row launch's order: 4 consecutive floats per lane, a wave sum per 256-float piece, then piece 0 + piece 1
+            const float* sr = (const float*)ssq_in + (size_t)i * ssq_n;
+            const int b0 = 4 * lane, b1 = 256 + 4 * lane;
+            s0 = (b0 < ssq_n ? sr[b0] : 0.f) + (b0 + 1 < ssq_n ? sr[b0 + 1] : 0.f) + (b0 + 2 < ssq_n ? sr[b0 + 2] : 0.f) + (b0 + 3 < ssq_n ? sr[b0 + 3] : 0.f);
+            s1 = (b1 < ssq_n ? sr[b1] : 0.f) + (b1 + 1 < ssq_n ? sr[b1 + 1] : 0.f) + (b1 + 2 < ssq_n ? sr[b1 + 2] : 0.f) + (b1 + 3 < ssq_n ? sr[b1 + 3] : 0.f);
+            s0 = wave_sum(s0);
+            s1 = wave_sum(s1);
+        }
+        __syncthreads();
+        if (!row_ok) return;
+        const float rs_norm = ssq_in ? __builtin_amdgcn_rsqf((s0 + (ssq_n > 256 ? s1 : 0.f)) * (1.f / (float)G.K) + eps) : 1.f;
+        auto row_sum_m = [&](int rs, int n) {
+            float v = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) v += red[((size_t)(rs * NW + w) * RB + i) * 16 + n];
+            return v * rs_norm;
+        };
+        if constexpr (MODE == V3_MODE_PAIR) {
+            if (lane < RS * 8) {
+                const int rs = lane >> 3, n = lane & 7;
+                float gv = row_sum_m(rs, n), uv = row_sum_m(rs, n + 8);
+                if (bias) {
+                    gv += (float)bias[(set0 + rs) * 16 + n];
+                    uv += (float)bias[(set0 + rs) * 16 + 8 + n];
+                }
+                const f16 g16 = (f16)gv, u16 = (f16)uv;
+                yout[(size_t)i * (N / 2) + (set0 + rs) * 8 + n] = mul_f32_to_f16(silu_f32((float)g16), (float)u16);
+            }
+        } else {
+            float sq = 0.f;
+            if (lane_row) {
+                const int row = set0 * 16 + lane;
+                float v = row_sum_m(lane >> 4, lane & 15);
+                if (bias) v += (float)bias[row];
+                if (residual) {
+                    v += res;
+                    y32[(size_t)i * N + row] = v;
+                    if (gamma_out) {
+                        ynorm[(size_t)i * N + row] = mul_f32_to_f16(v, gam);
+                        sq = v * v;
+                    }
+                } else {
+                    yout[(size_t)i * N + row] = (f16)v;
+                }
+            }
+            if (residual && gamma_out) {
+                sq = wave_sum(sq);
+                if (lane == 0) ssq_out[(size_t)i * nblk + blockIdx.x] = sq;
+            }
+        }
+        return;
+    }
     // the producer's partial sums of squares: waves 2 and 3 requested them (step 2b) and are the ones that know, through their
     // own waits, that they have landed -- each sums its piece HERE, in the slack before the final barrier, and leaves one float;
     // behind the barrier every wave reads two floats instead of reducing 512 (that reduction was ~0.15 us of every q|k|v and

@@ -1058,6 +1058,146 @@ class DecodeEngine:
         self.tok.copy_(tok0)
         return graph
 
+    # -- verify pass: m <= 8 tokens of this sequence in one launch sequence (assisted decoding, qeft_amd/assisted.py) ---------
+    VERIFY_MAX = 8
+
+    def _verify_unsupported(self):
+        if self.tp or self.tp3:
+            return "the verify pass runs on the single-GPU engine only (this engine is tensor-parallel)"
+        if self.bits != 4:
+            return f"the verify pass runs on 4-bit weights only (this engine has {self.bits}-bit weights)"
+        if not self.v3:
+            return "the verify pass runs on the v3 engine only (QEFT_ENGINE_V2=1, or shapes the v3 GEMV does not take)"
+        return None
+
+    def _verify_bufs(self):
+        """Static buffers of the verify pass, [VERIFY_MAX] rows each (allocated on first use)."""
+        vb = getattr(self, "_vb", None)
+        if vb is not None:
+            return vb
+        import types
+        s, dev, M = self.m.shape, self.dev, self.VERIFY_MAX
+        kvd = s.n_kv_heads * s.head_dim
+        f16 = dict(dtype=torch.float16, device=dev)
+        n_ssq = max(self.n_ssq_tb, self.n_ssq_lin)
+        ws = self.lib.qeft_attn_m_workspace_bytes(s.n_heads, 8, M)
+        vb = types.SimpleNamespace(
+            toks=torch.zeros(M, dtype=torch.long, device=dev),
+            h32=torch.zeros(M, s.hidden, dtype=torch.float32, device=dev),
+            xn=torch.zeros(M, s.hidden, **f16),
+            ssq=torch.zeros(M * n_ssq + 4, dtype=torch.float32, device=dev),
+            qkv=torch.zeros(M, s.hidden + 2 * kvd, **f16),
+            att=torch.zeros(M, s.hidden, **f16),
+            act=torch.zeros(M, s.inter, **f16),
+            hn=torch.zeros(M, s.hidden, **f16),
+            rope=torch.zeros(M, 128, dtype=torch.float32, device=dev),
+            ws=torch.zeros(max(ws, 16) // 4, dtype=torch.float32, device=dev),
+            out=torch.zeros(M, dtype=torch.long, device=dev),
+            n_acc=torch.zeros(1, dtype=torch.int32, device=dev))
+        self._vb = vb
+        self.logits_m = torch.zeros(M, s.vocab, **f16)
+        return vb
+
+    @torch.no_grad()
+    def _launch_verify(self, m, split, greedy):
+        """m-row launch sequence: token begin (m rows) -> per layer q|k|v, multi-query attention, o_proj (+ residual, norm split),
+        gate|up (SiLU epilogue), down_proj (+ residual, next norm split) on m-row GEMVs -> final norm + head (m rows) -> verify."""
+        s, lib, ck, vb = self.m.shape, self.lib, _lib.check, self._vb
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        g, no, eps = s.group_size, s.n_out, s.rms_eps
+        layers = self.m.model.layers
+        kvd = s.n_kv_heads * s.head_dim
+        nq = s.hidden + 2 * kvd
+        xn, ssq, h32 = vb.xn.data_ptr(), vb.ssq.data_ptr(), vb.h32.data_ptr()
+
+        def lin(op, x, y, mode=0, residual=None, ssq_in=None, n_ssq=0, gamma_out=None):
+            return lib.qeft_decode_linear_m(x, op.qweight.data_ptr(), op.sz_packed.data_ptr(), op.oweight.data_ptr() if no else None,
+                                            None, y, op.outfeatures, op.infeatures, g, no, mode, residual, ssq_in, n_ssq, eps,
+                                            gamma_out, xn if gamma_out else None, ssq if gamma_out else None, m, st)
+        ck(lib.qeft_token_begin_norm_m(self.m.model.embed_tokens.weight.data_ptr(), vb.toks.data_ptr(), self.rope_tab.data_ptr(),
+                                       self.pos.data_ptr(), h32, vb.rope.data_ptr(), layers[0].input_layernorm.weight.data_ptr(),
+                                       xn, ssq, s.hidden, s.vocab, s.max_seq, m, st))
+        n_ssq = self.n_ssq_tb
+        qp = vb.qkv.data_ptr()
+        for li, L in enumerate(layers):
+            pk = self.v3ops[li]
+            ck(lin(pk["qkv"], xn, qp, ssq_in=ssq, n_ssq=n_ssq))
+            ck(lib.qeft_rope_attn_decode_m(qp, qp + s.hidden * 2, qp + (s.hidden + kvd) * 2, nq, vb.rope.data_ptr(),
+                                           vb.rope.data_ptr() + 64 * 4, 128, m, self.kc[li].data_ptr(), self.vc[li].data_ptr(),
+                                           self.pos.data_ptr(), self.att_pos[li].data_ptr() if self.att_pos[li] is not None else None,
+                                           vb.att.data_ptr(), s.hidden, vb.ws.data_ptr(), split, s.n_heads, s.n_kv_heads, s.max_seq,
+                                           m, st))
+            ck(lin(pk["o"], vb.att.data_ptr(), h32, residual=h32, gamma_out=L.post_attention_layernorm.weight.data_ptr()))
+            n_ssq = self.n_ssq_lin
+            ck(lin(pk["gu"], xn, vb.act.data_ptr(), mode=1, ssq_in=ssq, n_ssq=n_ssq))
+            nxt = layers[li + 1].input_layernorm.weight.data_ptr() if li + 1 < len(layers) else None
+            ck(lin(pk["d"], vb.act.data_ptr(), h32, residual=h32, gamma_out=nxt))
+        w = self.m.lm_head.weight
+        if s.hidden in (512, 1024, 2048, 4096, 5120, 8192) and w.dtype == torch.float16 and w.is_contiguous() \
+                and os.environ.get("QEFT_LM_HEAD_TORCH") != "1":
+            ck(lib.qeft_lm_head_f16_m(h32, self.m.model.norm.weight.data_ptr(), w.data_ptr(), self.logits_m.data_ptr(), s.hidden,
+                                      s.vocab, eps, m, st))
+        else:           # head widths the fused kernel does not take: as _token_tail
+            ck(lib.qeft_rmsnorm_f32(h32, self.m.model.norm.weight.data_ptr(), vb.hn.data_ptr(), m, s.hidden, eps, st))
+            torch.matmul(vb.hn[:m], w.t(), out=self.logits_m[:m])
+        ck(lib.qeft_verify_greedy(self.logits_m.data_ptr(), vb.toks.data_ptr(), m, s.vocab, 1 if greedy else 0, vb.out.data_ptr(),
+                                  vb.n_acc.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), st))
+
+    def _capture_verify(self, m, split, greedy):
+        side = torch.cuda.Stream(self.dev)
+        side.wait_stream(torch.cuda.current_stream(self.dev))
+        pos0, tok0 = self.pos.clone(), self.tok.clone()
+        with torch.cuda.stream(side):
+            self._launch_verify(m, split, greedy)
+        torch.cuda.current_stream(self.dev).wait_stream(side)
+        torch.cuda.synchronize(self.dev)
+        self.pos.copy_(pos0)
+        self.tok.copy_(tok0)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._launch_verify(m, split, greedy)
+        # (the warm-up wrote K/V rows at pos0 .. pos0 + m - 1, rewritten by the real pass, and advanced pos / tok: restore them)
+        self.pos.copy_(pos0)
+        self.tok.copy_(tok0)
+        return graph
+
+    @torch.no_grad()
+    def verify(self, tokens):
+        """Score m = len(tokens) <= 8 tokens of this sequence in ONE pass: tokens[0] is the token at host_pos, the rest are
+        drafts.  Leaves logits_m[:m] (row i predicts position host_pos + i + 1).  greedy: returns (n, accepted) -- n = the number
+        of drafts that equal the target's own greedy choice (longest prefix), accepted = those n drafts + the target's token
+        after them (n + 1 tokens) -- and advances host_pos by n + 1, with tok = the last accepted token (step() goes on from
+        there).  Not greedy: advances by m, exactly as m teacher-forced step() calls; returns None."""
+        why = self._verify_unsupported()
+        if why:
+            raise RuntimeError(why)
+        toks = torch.as_tensor(tokens, dtype=torch.long).flatten().cpu()
+        m = int(toks.numel())
+        if not 1 <= m <= self.VERIFY_MAX:
+            raise ValueError(f"verify takes 1..{self.VERIFY_MAX} tokens, got {m}")
+        if self.host_pos + m > self.m.shape.max_seq:
+            raise RuntimeError(f"KV cache full: positions {self.host_pos} .. {self.host_pos + m - 1} pass max_seq {self.m.shape.max_seq}")
+        self._check_fresh()
+        vb = self._verify_bufs()
+        vb.toks[:m].copy_(toks)
+        sp = self._split_for(self.host_pos + m - 1)
+        greedy = bool(self.greedy)
+        if self.use_graph:
+            key = ("verify", m, sp, greedy)
+            g = self.graphs.get(key)
+            if g is None:
+                g = self.graphs[key] = self._capture_verify(m, sp, greedy)
+            g.replay()
+        else:
+            self._launch_verify(m, sp, greedy)
+        if not greedy:
+            self.host_pos += m
+            return None
+        res = torch.cat([vb.n_acc.long(), vb.out]).tolist()        # one small device-to-host read
+        n = int(res[0])
+        self.host_pos += n + 1
+        return n, res[1:n + 2]
+
     @torch.no_grad()
     def teacher_forced_logits(self, tokens):
         """Feed `tokens` one by one from position 0; returns fp32 logits [T, vocab] (main.py:340-371 protocol)."""

@@ -366,6 +366,32 @@ int qeft_lm_head_f16_m(const void* h32, const void* gamma, const void* weight, v
 int qeft_verify_greedy(const void* logits, const void* tokens, int m, int vocab, int greedy, void* out_tokens, int* n_accepted,
                        void* tok, int* pos, qeft_stream_t stream);
 
+/* Batched decoding (qeft_amd/batch.py, BatchDecodeEngine): m = 1..8 rows of m DIFFERENT sequences per launch (csrc/decode_batch.hip);
+ * the linears and the head are the verify pass's m-row entries above.  Row r serves cache slot slots[r] (device int32 [m]; the
+ * slots of one launch are distinct); per slot, on the device: pos, limit, eos, done (int32 [n_slots] each).  KV caches per layer:
+ * [n_slots][n_kv_heads][max_seq][128] fp16.  Every entry rejects m outside 1..8 (QEFT_ERR_BATCH) and bad shapes before it
+ * touches the device; a row whose slot lies outside [0, n_slots) is left alone.
+ * qeft_token_begin_norm_batch: qeft_token_begin_norm_m with row r's rotary row taken at pos[slots[r]] (clamped to the table).
+ * qeft_rope_attn_decode_batch: row r, slot s = slots[r], p = pos[s]: rotary of q and k, k / v appended to slot s at p, attention
+ *   over keys [0, p] of slot s.  A row with done[s] != 0 (done may be NULL) or p outside [0, max_seq) writes nothing to the cache
+ *   and zeros to its output.  q / k / v / out / rotary rows as qeft_rope_attn_decode_m (tab_rows == m: row r; tab_rows >= max_seq:
+ *   indexed by p).  n_split 1 / 2 / 4 / 8 blocks per (row, kv head); n_split > 1 needs a zeroed workspace of
+ *   qeft_attn_batch_workspace_bytes(n_heads, n_split, m) bytes (its counters re-arm themselves).
+ * qeft_token_end_batch: k = counter[0] (counter: device int32 [2], zeroed; counter[1] is the launch's own arrival count).  Row r,
+ *   slot s: done[s] != 0 -> out[r][k] = -1 only.  Otherwise a = argmax(logits[r]) (lowest index among equal maxima),
+ *   tokens[r] = a (int64), out[r][k] = a (int64, out rows out_cap apart, written for k < out_cap), pos[s] += 1, and done[s] = 1 if
+ *   a == eos[s] >= 0, else 2 if pos[s] >= limit[s].  counter[0] += 1. */
+int qeft_token_begin_norm_batch(const void* embed, const void* tokens, const void* rope_tab, const int* slots, const int* pos, void* h,
+                                void* rope_rows, const void* gamma, void* h_norm, float* ssq_out, int hidden, int vocab, int max_seq,
+                                int n_slots, int m, qeft_stream_t stream);
+int qeft_attn_batch_workspace_bytes(int n_heads, int n_split, int m);
+int qeft_rope_attn_decode_batch(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
+                                int tab_stride, int tab_rows, void* k_cache, void* v_cache, const int* slots, const int* pos,
+                                const int* done, const int* out_pos, void* out, int out_stride, void* workspace, int n_split,
+                                int n_slots, int n_heads, int n_kv_heads, int max_seq, int m, qeft_stream_t stream);
+int qeft_token_end_batch(const void* logits, const int* slots, void* tokens, int* pos, const int* limit, const int* eos, int* done,
+                         void* out, int* counter, int vocab, int out_cap, int n_slots, int m, qeft_stream_t stream);
+
 /* One-shot all-reduce of the tensor-parallel decode path (csrc/oneshot.hip; no reference counterpart --
  * the reference places whole layers on GPUs, qeft/utils/modelutils.py:21-57).  In-place fp32 sum of t[n] over `world` ranks
  * (one process per GPU) by ONE kernel per rank: every rank writes its partial as 8-byte {value, tag} granules into slot `rank`

@@ -77,6 +77,10 @@ SIGNATURES = {
     "qeft_rope_attn_decode_m": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
     "qeft_lm_head_f16_m": [_p, _p, _p, _p, _i, _i, ctypes.c_float, _i, _p],
     "qeft_verify_greedy": [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p],
+    "qeft_token_begin_norm_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "qeft_attn_batch_workspace_bytes": [_i, _i, _i],
+    "qeft_rope_attn_decode_batch": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
+    "qeft_token_end_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "qeft_oneshot_mailbox_bytes": [_i, _i],
     "qeft_oneshot_max_world": [],
     "qeft_oneshot_mailbox_alloc": [_i, _i, ctypes.POINTER(ctypes.c_void_p)],

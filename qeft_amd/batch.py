@@ -1,0 +1,356 @@
+"""Batched decoding: one greedy token for each of up to 8 independent sequences per weight pass.
+
+`BatchDecodeEngine` is built on a single-GPU `DecodeEngine` (4-bit weights, v3 engine) and shares its fused operands, rotary
+table and library handle, so the weights are not copied again.  It owns per-slot KV caches ([n_slots][n_kv][max_seq][128] per
+layer), the per-slot position and stop state on the device, its buffers and its graphs; it never touches the engine's own
+caches, position or graphs.  One pass launches, for the m active rows (row r serves slot rows[r]): the batched token begin, per
+layer the verify pass's m-row linears with the batched attention between them (each row in its own slot at its own position),
+the m-row head and the batched token end, which stops a row on the device when it emits its EOS token or reaches its length
+limit.  A stopped row keeps its position, cache and token; later passes of the same graph leave it alone.
+
+A sequence's tokens are the argmax of its prompt's last logits (what prefill + DecodeEngine give) followed by one token per
+pass; it holds at most `max_new_tokens` of them: its length limit is position min(prompt length + max_new_tokens - 1, max_seq).
+"""
+import collections
+import os
+import types
+
+import torch
+
+from . import _lib, llama
+
+REASONS = {1: "eos", 2: "length"}       # the device's done codes
+
+
+def batch_unsupported(engine):
+    """Why `engine` cannot serve batched decoding (the verify pass's conditions: one GPU, 4-bit weights, v3 engine), or None."""
+    why = engine._verify_unsupported()
+    return why.replace("the verify pass", "batched decoding") if why else None
+
+
+def length_limit(prompt_len, max_new_tokens, max_seq):
+    """The position at which a sequence stops for length; raises ValueError when the prompt does not fit."""
+    if prompt_len < 1:
+        raise ValueError("empty prompt")
+    if prompt_len > max_seq:
+        raise ValueError(f"a prompt of {prompt_len} tokens does not fit the KV cache (max_seq = {max_seq})")
+    if max_new_tokens < 1:
+        raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
+    return min(prompt_len + max_new_tokens - 1, max_seq)
+
+
+def stop_code(token, pos, limit, eos):
+    """The stop rule of the batched token end: 1 (EOS) if `token` is the sequence's EOS, else 2 (length) if `pos` has reached
+    `limit`, else 0."""
+    if eos is not None and eos >= 0 and token == eos:
+        return 1
+    return 2 if pos >= limit else 0
+
+
+class SlotTable:
+    """Host bookkeeping of the slots: which hold a sequence, its tokens, position, limit and why it finished."""
+
+    def __init__(self, n_slots):
+        self.n_slots = n_slots
+        self.seq = [None] * n_slots
+
+    def free_count(self):
+        return sum(q is None for q in self.seq)
+
+    def take(self, prompt_len, limit, eos):
+        """The lowest free slot, now holding a new sequence; raises RuntimeError when every slot is taken."""
+        for s, q in enumerate(self.seq):
+            if q is None:
+                self.seq[s] = types.SimpleNamespace(prompt_len=prompt_len, pos=prompt_len, limit=limit, eos=eos, tokens=[], reason=None)
+                return s
+        raise RuntimeError(f"no free slot: all {self.n_slots} slots hold a sequence (release() finished ones)")
+
+    def get(self, slot):
+        if not 0 <= slot < self.n_slots or self.seq[slot] is None:
+            raise KeyError(f"slot {slot} holds no sequence")
+        return self.seq[slot]
+
+    def release(self, slot):
+        self.get(slot)
+        self.seq[slot] = None
+
+    def rows(self):
+        """The slots still decoding, in row order (row r of a pass serves rows()[r])."""
+        return [s for s, q in enumerate(self.seq) if q is not None and q.reason is None]
+
+    def record(self, slot, tokens, pos, code):
+        """New tokens of `slot`, its position and the device's done code after them."""
+        q = self.get(slot)
+        q.tokens.extend(tokens)
+        q.pos = pos
+        if code and q.reason is None:
+            q.reason = REASONS[code]
+
+    def finished(self):
+        return {s: q.reason for s, q in enumerate(self.seq) if q is not None and q.reason is not None}
+
+
+class _SlotView:
+    """What `llama.prefill` needs of an engine, for one slot: that slot's caches per layer, P = 1 and set_position."""
+    P = 1
+
+    def __init__(self, batch, slot):
+        self.kc = [k[slot] for k in batch.kc]
+        self.vc = [v[slot] for v in batch.vc]
+        self.max_seq = batch.model.shape.max_seq
+        self.position = None
+
+    def set_position(self, t):
+        if not 0 <= int(t) <= self.max_seq:
+            raise ValueError(f"position {t} outside the KV cache (max_seq = {self.max_seq})")
+        self.position = int(t)
+
+
+class BatchDecodeEngine:
+    """Greedy decoding of up to `max_batch` (<= 8) sequences at once on `engine`'s weights.  admit() prefills a prompt into a free
+    slot, step() / run(n) decode every active row, finished() / tokens() / release() report and free slots."""
+
+    MAX_BATCH = 8
+    OUT_CAP = 256          # tokens per row between two host reads of the output
+    MULTI = llama.DecodeEngine.MULTI
+
+    def __init__(self, engine, max_batch=8, use_graph=True):
+        why = batch_unsupported(engine)
+        if why:
+            raise RuntimeError(why)
+        if not 1 <= int(max_batch) <= self.MAX_BATCH:
+            raise ValueError(f"max_batch must be 1..{self.MAX_BATCH}, got {max_batch}")
+        self.eng, self.model = engine, engine.m
+        self.lib, self.dev, self.use_graph = engine.lib, engine.dev, use_graph
+        s, dev = self.model.shape, engine.dev
+        M = self.n_slots = int(max_batch)
+        self.table = SlotTable(M)
+        f16, i32 = dict(dtype=torch.float16, device=dev), dict(dtype=torch.int32, device=dev)
+        kvd = s.n_kv_heads * s.head_dim
+        self.kc = [torch.zeros(M, s.n_kv_heads, s.max_seq, s.head_dim, **f16) for _ in range(s.n_layers)]
+        self.vc = [torch.zeros(M, s.n_kv_heads, s.max_seq, s.head_dim, **f16) for _ in range(s.n_layers)]
+        self.state = torch.zeros(4, M, **i32)                   # per slot: pos | limit | eos | done (one upload per admission)
+        self.pos, self.limit, self.eos, self.done = self.state.unbind(0)
+        self.slot_tab = torch.zeros(M, **i32)                   # row -> slot
+        self.tok = torch.zeros(M, dtype=torch.long, device=dev)         # per row: the token a pass consumes (and token end writes)
+        self.tok_slot = torch.zeros(M, dtype=torch.long, device=dev)    # per slot, between runs (rows change with the table)
+        self.out = torch.full((M, self.OUT_CAP), -1, dtype=torch.long, device=dev)
+        self.ctr = torch.zeros(2, **i32)                        # token end's step counter and arrival count
+        n_ssq = max(engine.n_ssq_tb, engine.n_ssq_lin)
+        ws = self.lib.qeft_attn_batch_workspace_bytes(s.n_heads, 8, M)
+        self.h32 = torch.zeros(M, s.hidden, dtype=torch.float32, device=dev)
+        self.xn = torch.zeros(M, s.hidden, **f16)
+        self.ssq = torch.zeros(M * n_ssq + 4, dtype=torch.float32, device=dev)
+        self.qkv = torch.zeros(M, s.hidden + 2 * kvd, **f16)
+        self.att = torch.zeros(M, s.hidden, **f16)
+        self.act = torch.zeros(M, s.inter, **f16)
+        self.hn = torch.zeros(M, s.hidden, **f16)
+        self.rope = torch.zeros(M, 128, dtype=torch.float32, device=dev)
+        self.ws = torch.zeros(max(ws, 16) // 4, dtype=torch.float32, device=dev)
+        self.logits_m = torch.zeros(M, s.vocab, **f16)
+        self.graphs = {}
+        self.rows = []                                          # the row table of the last pass
+
+    # -- slots ---------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def admit(self, prompt, max_new_tokens, eos_id=None):
+        """Prefill `prompt` into a free slot (llama.prefill on that slot's caches) and return the slot.  Its first token is the
+        argmax of the prompt's last logits.  Raises RuntimeError when no slot is free, ValueError when the prompt does not fit."""
+        toks = torch.as_tensor(prompt, dtype=torch.long).flatten()
+        T = int(toks.numel())
+        limit = length_limit(T, int(max_new_tokens), self.model.shape.max_seq)
+        self.eng._check_fresh()
+        eos = int(eos_id) if eos_id is not None else -1
+        slot = self.table.take(T, limit, eos)
+        try:
+            view = _SlotView(self, slot)
+            logits = llama.prefill(self.model, toks.to(self.dev), engine=view)
+            assert view.position == T
+            first = torch.argmax(logits[-1])
+            self.tok_slot[slot] = first
+            f = int(first.item())
+            code = stop_code(f, T, limit, eos)
+            self.state[:, slot] = torch.tensor([T, limit, eos, code], dtype=torch.int32)
+        except BaseException:
+            self.table.release(slot)
+            raise
+        self.table.record(slot, [f], T, code)
+        return slot
+
+    def finished(self):
+        """{slot: "eos" | "length"} of the sequences that stopped and are not yet released."""
+        return self.table.finished()
+
+    def tokens(self, slot):
+        """The tokens `slot`'s sequence has generated so far (the first one from its prompt included)."""
+        return list(self.table.get(slot).tokens)
+
+    def release(self, slot):
+        """Free `slot` (finished or not)."""
+        self.table.release(slot)
+        self.state[3, slot] = 2
+
+    def logits(self, slot):
+        """fp16 logits of `slot`'s row in the last pass."""
+        return self.logits_m[self.rows.index(slot)]
+
+    # -- passes --------------------------------------------------------------------------------------------------------------
+    def _split_for(self, pos):
+        return self.eng._split_for(pos)
+
+    @torch.no_grad()
+    def _launch(self, m, split):
+        """One token of m rows: token begin -> per layer q|k|v, attention, o_proj (+ residual, norm split), gate|up (SiLU
+        epilogue), down_proj (+ residual, next norm split) -> final norm + head -> token end."""
+        s, lib, ck, eng = self.model.shape, self.lib, _lib.check, self.eng
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        g, no, eps = s.group_size, s.n_out, s.rms_eps
+        layers = self.model.model.layers
+        kvd = s.n_kv_heads * s.head_dim
+        nq = s.hidden + 2 * kvd
+        xn, ssq, h32 = self.xn.data_ptr(), self.ssq.data_ptr(), self.h32.data_ptr()
+        slots, pos, done = self.slot_tab.data_ptr(), self.pos.data_ptr(), self.done.data_ptr()
+
+        def lin(op, x, y, mode=0, residual=None, ssq_in=None, n_ssq=0, gamma_out=None):
+            return lib.qeft_decode_linear_m(x, op.qweight.data_ptr(), op.sz_packed.data_ptr(), op.oweight.data_ptr() if no else None,
+                                            None, y, op.outfeatures, op.infeatures, g, no, mode, residual, ssq_in, n_ssq, eps,
+                                            gamma_out, xn if gamma_out else None, ssq if gamma_out else None, m, st)
+        ck(lib.qeft_token_begin_norm_batch(self.model.model.embed_tokens.weight.data_ptr(), self.tok.data_ptr(), eng.rope_tab.data_ptr(),
+                                           slots, pos, h32, self.rope.data_ptr(), layers[0].input_layernorm.weight.data_ptr(), xn, ssq,
+                                           s.hidden, s.vocab, s.max_seq, self.n_slots, m, st))
+        n_ssq = eng.n_ssq_tb
+        qp = self.qkv.data_ptr()
+        for li, L in enumerate(layers):
+            pk = eng.v3ops[li]
+            ck(lin(pk["qkv"], xn, qp, ssq_in=ssq, n_ssq=n_ssq))
+            ck(lib.qeft_rope_attn_decode_batch(qp, qp + s.hidden * 2, qp + (s.hidden + kvd) * 2, nq, self.rope.data_ptr(),
+                                               self.rope.data_ptr() + 64 * 4, 128, m, self.kc[li].data_ptr(), self.vc[li].data_ptr(),
+                                               slots, pos, done, eng.att_pos[li].data_ptr() if eng.att_pos[li] is not None else None,
+                                               self.att.data_ptr(), s.hidden, self.ws.data_ptr(), split, self.n_slots, s.n_heads,
+                                               s.n_kv_heads, s.max_seq, m, st))
+            ck(lin(pk["o"], self.att.data_ptr(), h32, residual=h32, gamma_out=L.post_attention_layernorm.weight.data_ptr()))
+            n_ssq = eng.n_ssq_lin
+            ck(lin(pk["gu"], xn, self.act.data_ptr(), mode=1, ssq_in=ssq, n_ssq=n_ssq))
+            nxt = layers[li + 1].input_layernorm.weight.data_ptr() if li + 1 < len(layers) else None
+            ck(lin(pk["d"], self.act.data_ptr(), h32, residual=h32, gamma_out=nxt))
+        w = self.model.lm_head.weight
+        if s.hidden in (512, 1024, 2048, 4096, 5120, 8192) and w.dtype == torch.float16 and w.is_contiguous() \
+                and os.environ.get("QEFT_LM_HEAD_TORCH") != "1":
+            ck(lib.qeft_lm_head_f16_m(h32, self.model.model.norm.weight.data_ptr(), w.data_ptr(), self.logits_m.data_ptr(), s.hidden,
+                                      s.vocab, eps, m, st))
+        else:           # head widths the fused kernel does not take: as DecodeEngine._launch_verify
+            ck(lib.qeft_rmsnorm_f32(h32, self.model.model.norm.weight.data_ptr(), self.hn.data_ptr(), m, s.hidden, eps, st))
+            torch.matmul(self.hn[:m], w.t(), out=self.logits_m[:m])
+        ck(lib.qeft_token_end_batch(self.logits_m.data_ptr(), slots, self.tok.data_ptr(), pos, self.limit.data_ptr(),
+                                    self.eos.data_ptr(), done, self.out.data_ptr(), self.ctr.data_ptr(), s.vocab, self.OUT_CAP,
+                                    self.n_slots, m, st))
+
+    def _capture(self, m, split, n_tok):
+        """A graph of n_tok passes of m rows (after a warm-up pass on a side stream, as torch requires; the warm-up's state
+        changes are undone -- the K/V rows it wrote are rewritten by the real pass)."""
+        cur = torch.cuda.current_stream(self.dev)
+        side = torch.cuda.Stream(self.dev)
+        side.wait_stream(cur)
+        saved = [t.clone() for t in (self.state, self.tok, self.ctr, self.out)]
+        with torch.cuda.stream(side):
+            self._launch(m, split)
+        cur.wait_stream(side)
+        torch.cuda.synchronize(self.dev)
+        for t, v in zip((self.state, self.tok, self.ctr, self.out), saved):
+            t.copy_(v)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for _ in range(n_tok):
+                self._launch(m, split)
+        for t, v in zip((self.state, self.tok, self.ctr, self.out), saved):
+            t.copy_(v)
+        return graph
+
+    def _pass(self, m, split, n_tok):
+        if self.use_graph:
+            key = (m, split, n_tok)
+            g = self.graphs.get(key)
+            if g is None:
+                g = self.graphs[key] = self._capture(m, split, n_tok)
+            g.replay()
+        else:
+            for _ in range(n_tok):
+                self._launch(m, split)
+
+    @torch.no_grad()
+    def _decode(self, n, feed=None):
+        """Up to n tokens for every active row (fewer when every row has reached its length limit); the host reads the output
+        once per OUT_CAP tokens and at the end.  feed: {slot: token} consumed instead of the slots' pending tokens."""
+        rows = self.table.rows()
+        if not rows or n <= 0:
+            return
+        self.eng._check_fresh()
+        m = len(rows)
+        if feed:
+            idx = torch.tensor(list(feed), dtype=torch.long)
+            self.tok_slot[idx.to(self.dev)] = torch.tensor([int(v) for v in feed.values()], dtype=torch.long).to(self.dev)
+        self.slot_tab[:m].copy_(torch.tensor(rows, dtype=torch.int32))
+        sel = self.slot_tab[:m].long()
+        self.tok[:m] = self.tok_slot[sel]
+        self.rows = rows
+        # host bound of each row's position (exact unless the row stopped at EOS): picks the attention split
+        hp = {s: self.table.get(s).pos for s in rows}
+        lim = {s: self.table.get(s).limit for s in rows}
+        multi = self.use_graph and self.MULTI > 1 and os.environ.get("QEFT_MULTI_TOKEN_GRAPH") != "0"
+        left = n
+        while left > 0:
+            self.ctr.zero_()
+            chunk, t = min(left, self.OUT_CAP), 0
+            while t < chunk:
+                live = [s for s in rows if hp[s] < lim[s]]
+                if not live:
+                    break
+                p = max(hp[s] for s in live)
+                sp = self._split_for(p)
+                k = self.MULTI if multi and chunk - t >= self.MULTI and self._split_for(p + self.MULTI - 1) == sp else 1
+                self._pass(m, sp, k)
+                for s in rows:
+                    hp[s] = min(hp[s] + k, lim[s])
+                t += k
+            if t:
+                self._collect(rows, t)
+            left -= chunk
+            if t < chunk or not any(s in self.table.rows() for s in rows):
+                break
+        self.tok_slot[sel] = self.tok[:m]
+
+    def _collect(self, rows, n_tok):
+        out = self.out[:len(rows), :n_tok].cpu()
+        st = self.state.cpu()
+        for r, s in enumerate(rows):
+            self.table.record(s, [int(x) for x in out[r].tolist() if x >= 0], int(st[0, s]), int(st[3, s]))
+
+    def step(self, feed=None):
+        """One token for every active row.  feed: {slot: token} to consume instead of the slots' own last tokens (teacher
+        forcing); logits(slot) then holds the row's logits."""
+        self._decode(1, feed)
+
+    def run(self, n):
+        """n tokens for every active row (graphs of MULTI tokens where the attention split allows); rows stop on the device at
+        EOS or at their length limit, a row at max_seq finishes with "length"."""
+        self._decode(n)
+
+
+def generate_batch(engine, prompts, max_new_tokens, eos_id=None, max_batch=8, use_graph=True):
+    """Greedy continuous batching: every prompt decoded to at most max_new_tokens tokens (stopping at eos_id), up to max_batch
+    at a time; a waiting prompt is admitted as soon as a slot frees up.  Returns the token lists in prompt order."""
+    prompts = list(prompts)
+    if not prompts:
+        return []
+    be = BatchDecodeEngine(engine, max_batch=max(1, min(int(max_batch), len(prompts))), use_graph=use_graph)
+    waiting = collections.deque(enumerate(prompts))
+    results, owner = [None] * len(prompts), {}
+    while waiting or owner:
+        while waiting and be.table.free_count():
+            i, p = waiting.popleft()
+            owner[be.admit(p, max_new_tokens, eos_id)] = i
+        be.run(2 * be.MULTI)
+        for s in list(be.finished()):
+            results[owner.pop(s)] = be.tokens(s)
+            be.release(s)
+    return results

@@ -60,6 +60,16 @@ hipError_t lm_head_m_launch(const void* h32, const void* gamma, const void* W, v
                             hipStream_t st);
 hipError_t verify_greedy_launch(const void* logits, const void* tokens, int m, int vocab, int greedy, void* out_tokens, int* n_acc,
                                 void* tok, int* pos, hipStream_t st);
+hipError_t token_begin_norm_b_launch(const void* embed, const void* toks, const void* rope_tab, const int* slot_tab,  // decode_batch.hip
+                                     const int* pos_tab, void* h, void* rope_rows, const void* gamma, void* hnorm, float* ssq_out,
+                                     int hidden, int vocab, int max_seq, int n_slots, int m, hipStream_t st);
+size_t attn_b_workspace_bytes(int n_heads, int S, int m);
+hipError_t rope_attn_b_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
+                              int tab_stride, int tab_rows, void* kc, void* vc, const int* slot_tab, const int* pos_tab,
+                              const int* done, const int* out_pos, void* out, int out_stride, void* ws, int n_slots, int n_heads,
+                              int n_kv, int max_seq, int S, int m, hipStream_t st);
+hipError_t token_end_b_launch(const void* logits, const int* slot_tab, void* tok, int* pos_tab, const int* limit, const int* eos,
+                              int* done, void* out, int* ctr, int vocab, int out_cap, int n_slots, int m, hipStream_t st);
 extern unsigned long long* g_attn_dbg;
 hipError_t dequant_w4_launch(const void* qw, const void* scales, const void* zeros, const void* ow, void* out, int N,
                              int K, int G, int n_out, hipStream_t st);
@@ -963,6 +973,52 @@ int qeft_verify_greedy(const void* logits, const void* tokens, int m, int vocab,
     if (!pos || (greedy && (!logits || !tokens || !out_tokens || !n_accepted || !tok))) return QEFT_ERR_NULL;
     if (greedy && !aligned16(logits)) return QEFT_ERR_ALIGN;
     return finish(qeft::verify_greedy_launch(logits, tokens, m, vocab, greedy, out_tokens, n_accepted, tok, pos, (hipStream_t)stream));
+}
+
+// ---- batched decoding (m = 1..8 rows of m different sequences, row r in cache slot slots[r]): decode_batch.hip
+int qeft_token_begin_norm_batch(const void* embed, const void* tokens, const void* rope_tab, const int* slots, const int* pos, void* h,
+                                void* rope_rows, const void* gamma, void* h_norm, float* ssq_out, int hidden, int vocab, int max_seq,
+                                int n_slots, int m, qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (hidden < 8 || hidden % 8 != 0 || vocab < 1 || max_seq < 1 || n_slots < 1) return QEFT_ERR_SHAPE;
+    if (!embed || !tokens || !rope_tab || !slots || !pos || !h || !rope_rows || !gamma || !h_norm || !ssq_out) return QEFT_ERR_NULL;
+    if (!aligned16(embed) || !aligned16(h) || !aligned16(gamma) || !aligned16(h_norm)) return QEFT_ERR_ALIGN;
+    return finish(qeft::token_begin_norm_b_launch(embed, tokens, rope_tab, slots, pos, h, rope_rows, gamma, h_norm, ssq_out, hidden,
+                                                  vocab, max_seq, n_slots, m, (hipStream_t)stream));
+}
+
+int qeft_attn_batch_workspace_bytes(int n_heads, int n_split, int m) {
+    if (n_heads < 1 || n_heads > 4096 || n_split < 1 || n_split > 8 || !verify_m_ok(m)) return 0;
+    return (int)qeft::attn_b_workspace_bytes(n_heads, n_split, m);
+}
+
+int qeft_rope_attn_decode_batch(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
+                                int tab_stride, int tab_rows, void* k_cache, void* v_cache, const int* slots, const int* pos,
+                                const int* done, const int* out_pos, void* out, int out_stride, void* workspace, int n_split,
+                                int n_slots, int n_heads, int n_kv_heads, int max_seq, int m, qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0 || n_heads > 4096 || max_seq < 16 || max_seq % 16 != 0 ||
+        max_seq > 32768 || n_slots < 1 || n_slots > 4096)
+        return QEFT_ERR_SHAPE;
+    if (tab_rows != m && tab_rows < max_seq) return QEFT_ERR_SHAPE;
+    if (tab_stride < 64 || qkv_stride < 1 || out_stride < 1 || (!out_pos && out_stride < n_heads * 128)) return QEFT_ERR_SHAPE;
+    if (n_split != 1 && n_split != 2 && n_split != 4 && n_split != 8) return QEFT_ERR_SHAPE;
+    if (!q || !k || !v || !cos_tab || !sin_tab || !k_cache || !v_cache || !slots || !pos || !out) return QEFT_ERR_NULL;
+    if (n_split > 1 && !workspace) return QEFT_ERR_NULL;
+    if (!aligned16(k_cache) || !aligned16(v_cache) || !aligned16(workspace)) return QEFT_ERR_ALIGN;
+    return finish(qeft::rope_attn_b_launch(q, k, v, qkv_stride, cos_tab, sin_tab, tab_stride, tab_rows, k_cache, v_cache, slots, pos,
+                                           done, out_pos, out, out_stride, workspace, n_slots, n_heads, n_kv_heads, max_seq, n_split, m,
+                                           (hipStream_t)stream));
+}
+
+int qeft_token_end_batch(const void* logits, const int* slots, void* tokens, int* pos, const int* limit, const int* eos, int* done,
+                         void* out, int* counter, int vocab, int out_cap, int n_slots, int m, qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (vocab < 1 || out_cap < 1 || n_slots < 1) return QEFT_ERR_SHAPE;
+    if (!logits || !slots || !tokens || !pos || !limit || !eos || !done || !out || !counter) return QEFT_ERR_NULL;
+    if (!aligned16(logits)) return QEFT_ERR_ALIGN;
+    return finish(qeft::token_end_b_launch(logits, slots, tokens, pos, limit, eos, done, out, counter, vocab, out_cap, n_slots, m,
+                                           (hipStream_t)stream));
 }
 
 

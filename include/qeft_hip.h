@@ -392,6 +392,28 @@ int qeft_rope_attn_decode_batch(const void* q, const void* k, const void* v, int
 int qeft_token_end_batch(const void* logits, const int* slots, void* tokens, int* pos, const int* limit, const int* eos, int* done,
                          void* out, int* counter, int vocab, int out_cap, int n_slots, int m, qeft_stream_t stream);
 
+/* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py).  A parameter record is int32 [8] in device memory:
+ * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
+ *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;
+ *     otherwise weights w = exp((l - max l) / T) in fp32 (NaN: weight 0, never drawn; -0 == +0);
+ *   top_k (0 or >= vocab: off): keep every logit >= the k-th largest (ties at the boundary kept);
+ *   top_p (1: off): keep token j iff the top-k survivors' weight above l_j (strictly greater logits) is below top_p * Z, Z their
+ *     total weight;
+ *   draw: x0 = word 0 of Philox4x32-10 at counter (p, 0, 0, 0), key (seed lo, seed hi), u = x0 / 2^32; the token is the first
+ *     kept token in index order whose inclusive cumulative weight exceeds u * Z_kept.  p is the position the drawn token will
+ *     occupy.  The result depends only on (row, record, p): not on m, the row index, the slot or a replay.
+ * Records live on the device, so a captured graph picks up new parameters without a recapture.  logits, params 16-byte aligned.
+ * qeft_sample: m >= 1 rows, row r uses params[r] and p = positions[r] (int32 [m]); tokens_out int64 [m].
+ * qeft_token_end_sample: qeft_token_end(greedy = 1)'s contract (*tok = the token, *pos += 1) with p = *pos + 1.
+ * qeft_token_end_sample_batch: qeft_token_end_batch's contract exactly, with row r drawing with params[slots[r]] (params: records
+ *   [n_slots][8]) at p = pos[slots[r]] + 1. */
+int qeft_sample(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens_out,
+                qeft_stream_t stream);
+int qeft_token_end_sample(const void* logits, void* tok, int* pos, int vocab, const int* params, qeft_stream_t stream);
+int qeft_token_end_sample_batch(const void* logits, const int* slots, void* tokens, int* pos, const int* limit, const int* eos,
+                                int* done, void* out, int* counter, const int* params, int vocab, int out_cap, int n_slots, int m,
+                                qeft_stream_t stream);
+
 /* One-shot all-reduce of the tensor-parallel decode path (csrc/oneshot.hip; no reference counterpart --
  * the reference places whole layers on GPUs, qeft/utils/modelutils.py:21-57).  In-place fp32 sum of t[n] over `world` ranks
  * (one process per GPU) by ONE kernel per rank: every rank writes its partial as 8-byte {value, tag} granules into slot `rank`

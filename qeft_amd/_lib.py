@@ -81,6 +81,9 @@ SIGNATURES = {
     "qeft_attn_batch_workspace_bytes": [_i, _i, _i],
     "qeft_rope_attn_decode_batch": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
     "qeft_token_end_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "qeft_sample": [_p, _i, _i, _p, _p, _p, _p],
+    "qeft_token_end_sample": [_p, _p, _p, _i, _p, _p],
+    "qeft_token_end_sample_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "qeft_oneshot_mailbox_bytes": [_i, _i],
     "qeft_oneshot_max_world": [],
     "qeft_oneshot_mailbox_alloc": [_i, _i, ctypes.POINTER(ctypes.c_void_p)],

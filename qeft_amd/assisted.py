@@ -89,7 +89,10 @@ class EngineDraft:
 def assisted_generate(engine, draft, first_token, n_tokens, k, context=None):
     """Greedy assisted generation of n_tokens tokens after first_token (the token at engine.host_pos; `context`: the tokens at
     positions 0 .. host_pos - 1, which a draft may use).  Each pass verifies the last token and up to min(k, 7) drafts.
-    Returns (tokens, accepted) -- the n_tokens generated tokens, and per pass the number of drafts the target accepted."""
+    Returns (tokens, accepted) -- the n_tokens generated tokens, and per pass the number of drafts the target accepted.
+    Greedy only: raises ValueError on an engine with sampling set (the verify pass accepts drafts by the argmax)."""
+    if getattr(engine, "sampling", None) is not None:
+        raise ValueError("assisted_generate is greedy only: this engine has sampling set (engine.set_sampling(None) first)")
     engine.greedy = True
     ctx = [int(t) for t in (context if context is not None else [])] + [int(first_token)]
     out, accepted = [], []

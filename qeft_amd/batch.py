@@ -1,4 +1,5 @@
-"""Batched decoding: one greedy token for each of up to 8 independent sequences per weight pass.
+"""Batched decoding: one token (greedy or sampled) for each of up to 8 independent sequences per weight pass (DESIGN.md §4.7,
+§4.8).
 
 `BatchDecodeEngine` is built on a single-GPU `DecodeEngine` (4-bit weights, v3 engine) and shares its fused operands, rotary
 table and library handle, so the weights are not copied again.  It owns per-slot KV caches ([n_slots][n_kv][max_seq][128] per
@@ -10,6 +11,9 @@ limit.  A stopped row keeps its position, cache and token; later passes of the s
 
 A sequence's tokens are the argmax of its prompt's last logits (what prefill + DecodeEngine give) followed by one token per
 pass; it holds at most `max_new_tokens` of them: its length limit is position min(prompt length + max_new_tokens - 1, max_seq).
+A sequence admitted with SamplingParams (qeft_amd/sampling.py) draws its tokens instead, the first one from the prompt's last
+logits at position T (the prompt's length), each later one on the device at the position it will occupy; greedy and sampled
+sequences share passes.
 """
 import collections
 import os
@@ -18,6 +22,7 @@ import types
 import torch
 
 from . import _lib, llama
+from .sampling import SamplingParams, sample
 
 REASONS = {1: "eos", 2: "length"}       # the device's done codes
 
@@ -107,7 +112,7 @@ class _SlotView:
 
 
 class BatchDecodeEngine:
-    """Greedy decoding of up to `max_batch` (<= 8) sequences at once on `engine`'s weights.  admit() prefills a prompt into a free
+    """Greedy or sampled decoding of up to `max_batch` (<= 8) sequences at once on `engine`'s weights.  admit() prefills a prompt into a free
     slot, step() / run(n) decode every active row, finished() / tokens() / release() report and free slots."""
 
     MAX_BATCH = 8
@@ -129,8 +134,12 @@ class BatchDecodeEngine:
         kvd = s.n_kv_heads * s.head_dim
         self.kc = [torch.zeros(M, s.n_kv_heads, s.max_seq, s.head_dim, **f16) for _ in range(s.n_layers)]
         self.vc = [torch.zeros(M, s.n_kv_heads, s.max_seq, s.head_dim, **f16) for _ in range(s.n_layers)]
-        self.state = torch.zeros(4, M, **i32)                   # per slot: pos | limit | eos | done (one upload per admission)
+        # per slot: pos | limit | eos | done, then the sampling records [M][8] (sampling.py); one upload per admission
+        self._slot_words = torch.zeros(4 * M + 8 * M, **i32)
+        self.state = self._slot_words[:4 * M].view(4, M)
         self.pos, self.limit, self.eos, self.done = self.state.unbind(0)
+        self.params = self._slot_words[4 * M:].view(M, 8)
+        self.sampled = [False] * M                              # per slot: a sampled sequence (temperature > 0)
         self.slot_tab = torch.zeros(M, **i32)                   # row -> slot
         self.tok = torch.zeros(M, dtype=torch.long, device=dev)         # per row: the token a pass consumes (and token end writes)
         self.tok_slot = torch.zeros(M, dtype=torch.long, device=dev)    # per slot, between runs (rows change with the table)
@@ -153,24 +162,34 @@ class BatchDecodeEngine:
 
     # -- slots ---------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def admit(self, prompt, max_new_tokens, eos_id=None):
+    def admit(self, prompt, max_new_tokens, eos_id=None, sampling=None):
         """Prefill `prompt` into a free slot (llama.prefill on that slot's caches) and return the slot.  Its first token is the
-        argmax of the prompt's last logits.  Raises RuntimeError when no slot is free, ValueError when the prompt does not fit."""
+        argmax of the prompt's last logits, or with `sampling` (SamplingParams, temperature > 0) drawn from them at position T.
+        Raises RuntimeError when no slot is free, ValueError when the prompt does not fit."""
         toks = torch.as_tensor(prompt, dtype=torch.long).flatten()
         T = int(toks.numel())
         limit = length_limit(T, int(max_new_tokens), self.model.shape.max_seq)
+        if sampling is not None and not isinstance(sampling, SamplingParams):
+            raise TypeError(f"sampling must be a SamplingParams or None, got {type(sampling).__name__}")
         self.eng._check_fresh()
         eos = int(eos_id) if eos_id is not None else -1
+        sampling = sampling.resolved() if sampling is not None else None
+        drawn = sampling is not None and not sampling.greedy
         slot = self.table.take(T, limit, eos)
         try:
             view = _SlotView(self, slot)
             logits = llama.prefill(self.model, toks.to(self.dev), engine=view)
             assert view.position == T
-            first = torch.argmax(logits[-1])
+            first = sample(logits[-1], sampling, T)[0] if drawn else torch.argmax(logits[-1])
             self.tok_slot[slot] = first
             f = int(first.item())
             code = stop_code(f, T, limit, eos)
-            self.state[:, slot] = torch.tensor([T, limit, eos, code], dtype=torch.int32)
+            M = self.n_slots
+            rec = sampling.record() if sampling is not None else [0] * 8
+            idx = [slot, M + slot, 2 * M + slot, 3 * M + slot] + list(range(4 * M + 8 * slot, 4 * M + 8 * slot + 8))
+            words = torch.tensor([idx, [T, limit, eos, code] + rec], dtype=torch.int64).to(self.dev)
+            self._slot_words.index_copy_(0, words[0], words[1].int())
+            self.sampled[slot] = drawn
         except BaseException:
             self.table.release(slot)
             raise
@@ -189,6 +208,7 @@ class BatchDecodeEngine:
         """Free `slot` (finished or not)."""
         self.table.release(slot)
         self.state[3, slot] = 2
+        self.sampled[slot] = False
 
     def logits(self, slot):
         """fp16 logits of `slot`'s row in the last pass."""
@@ -199,9 +219,10 @@ class BatchDecodeEngine:
         return self.eng._split_for(pos)
 
     @torch.no_grad()
-    def _launch(self, m, split):
+    def _launch(self, m, split, sampled=False):
         """One token of m rows: token begin -> per layer q|k|v, attention, o_proj (+ residual, norm split), gate|up (SiLU
-        epilogue), down_proj (+ residual, next norm split) -> final norm + head -> token end."""
+        epilogue), down_proj (+ residual, next norm split) -> final norm + head -> token end (sampled: each row draws with its
+        slot's record; greedy rows' records have temperature 0, the argmax)."""
         s, lib, ck, eng = self.model.shape, self.lib, _lib.check, self.eng
         st = torch.cuda.current_stream(self.dev).cuda_stream
         g, no, eps = s.group_size, s.n_out, s.rms_eps
@@ -241,11 +262,16 @@ class BatchDecodeEngine:
         else:           # head widths the fused kernel does not take: as DecodeEngine._launch_verify
             ck(lib.qeft_rmsnorm_f32(h32, self.model.model.norm.weight.data_ptr(), self.hn.data_ptr(), m, s.hidden, eps, st))
             torch.matmul(self.hn[:m], w.t(), out=self.logits_m[:m])
-        ck(lib.qeft_token_end_batch(self.logits_m.data_ptr(), slots, self.tok.data_ptr(), pos, self.limit.data_ptr(),
-                                    self.eos.data_ptr(), done, self.out.data_ptr(), self.ctr.data_ptr(), s.vocab, self.OUT_CAP,
-                                    self.n_slots, m, st))
+        if sampled:
+            ck(lib.qeft_token_end_sample_batch(self.logits_m.data_ptr(), slots, self.tok.data_ptr(), pos, self.limit.data_ptr(),
+                                               self.eos.data_ptr(), done, self.out.data_ptr(), self.ctr.data_ptr(),
+                                               self.params.data_ptr(), s.vocab, self.OUT_CAP, self.n_slots, m, st))
+        else:
+            ck(lib.qeft_token_end_batch(self.logits_m.data_ptr(), slots, self.tok.data_ptr(), pos, self.limit.data_ptr(),
+                                        self.eos.data_ptr(), done, self.out.data_ptr(), self.ctr.data_ptr(), s.vocab, self.OUT_CAP,
+                                        self.n_slots, m, st))
 
-    def _capture(self, m, split, n_tok):
+    def _capture(self, m, split, n_tok, sampled=False):
         """A graph of n_tok passes of m rows (after a warm-up pass on a side stream, as torch requires; the warm-up's state
         changes are undone -- the K/V rows it wrote are rewritten by the real pass)."""
         cur = torch.cuda.current_stream(self.dev)
@@ -253,7 +279,7 @@ class BatchDecodeEngine:
         side.wait_stream(cur)
         saved = [t.clone() for t in (self.state, self.tok, self.ctr, self.out)]
         with torch.cuda.stream(side):
-            self._launch(m, split)
+            self._launch(m, split, sampled)
         cur.wait_stream(side)
         torch.cuda.synchronize(self.dev)
         for t, v in zip((self.state, self.tok, self.ctr, self.out), saved):
@@ -261,21 +287,21 @@ class BatchDecodeEngine:
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             for _ in range(n_tok):
-                self._launch(m, split)
+                self._launch(m, split, sampled)
         for t, v in zip((self.state, self.tok, self.ctr, self.out), saved):
             t.copy_(v)
         return graph
 
-    def _pass(self, m, split, n_tok):
+    def _pass(self, m, split, n_tok, sampled=False):
         if self.use_graph:
-            key = (m, split, n_tok)
+            key = (m, split, n_tok, "sample") if sampled else (m, split, n_tok)
             g = self.graphs.get(key)
             if g is None:
-                g = self.graphs[key] = self._capture(m, split, n_tok)
+                g = self.graphs[key] = self._capture(m, split, n_tok, sampled)
             g.replay()
         else:
             for _ in range(n_tok):
-                self._launch(m, split)
+                self._launch(m, split, sampled)
 
     @torch.no_grad()
     def _decode(self, n, feed=None):
@@ -297,6 +323,7 @@ class BatchDecodeEngine:
         hp = {s: self.table.get(s).pos for s in rows}
         lim = {s: self.table.get(s).limit for s in rows}
         multi = self.use_graph and self.MULTI > 1 and os.environ.get("QEFT_MULTI_TOKEN_GRAPH") != "0"
+        sampled = any(self.sampled[s] for s in rows)
         left = n
         while left > 0:
             self.ctr.zero_()
@@ -308,7 +335,7 @@ class BatchDecodeEngine:
                 p = max(hp[s] for s in live)
                 sp = self._split_for(p)
                 k = self.MULTI if multi and chunk - t >= self.MULTI and self._split_for(p + self.MULTI - 1) == sp else 1
-                self._pass(m, sp, k)
+                self._pass(m, sp, k, sampled)
                 for s in rows:
                     hp[s] = min(hp[s] + k, lim[s])
                 t += k
@@ -336,19 +363,24 @@ class BatchDecodeEngine:
         self._decode(n)
 
 
-def generate_batch(engine, prompts, max_new_tokens, eos_id=None, max_batch=8, use_graph=True):
-    """Greedy continuous batching: every prompt decoded to at most max_new_tokens tokens (stopping at eos_id), up to max_batch
-    at a time; a waiting prompt is admitted as soon as a slot frees up.  Returns the token lists in prompt order."""
+def generate_batch(engine, prompts, max_new_tokens, eos_id=None, max_batch=8, use_graph=True, sampling=None):
+    """Continuous batching: every prompt decoded to at most max_new_tokens tokens (stopping at eos_id), up to max_batch at a
+    time; a waiting prompt is admitted as soon as a slot frees up.  sampling: None (greedy), one SamplingParams for every
+    prompt (a None seed is drawn per prompt) or a list with one entry (SamplingParams or None) per prompt.  Returns the token
+    lists in prompt order."""
     prompts = list(prompts)
     if not prompts:
         return []
+    per = list(sampling) if isinstance(sampling, (list, tuple)) else [sampling] * len(prompts)
+    if len(per) != len(prompts):
+        raise ValueError(f"{len(per)} sampling entries for {len(prompts)} prompts")
     be = BatchDecodeEngine(engine, max_batch=max(1, min(int(max_batch), len(prompts))), use_graph=use_graph)
     waiting = collections.deque(enumerate(prompts))
     results, owner = [None] * len(prompts), {}
     while waiting or owner:
         while waiting and be.table.free_count():
             i, p = waiting.popleft()
-            owner[be.admit(p, max_new_tokens, eos_id)] = i
+            owner[be.admit(p, max_new_tokens, eos_id, sampling=per[i])] = i
         be.run(2 * be.MULTI)
         for s in list(be.finished()):
             results[owner.pop(s)] = be.tokens(s)

@@ -71,6 +71,12 @@ hipError_t rope_attn_b_launch(const void* q, const void* k, const void* v, int q
 hipError_t token_end_b_launch(const void* logits, const int* slot_tab, void* tok, int* pos_tab, const int* limit, const int* eos,
                               int* done, void* out, int* ctr, int vocab, int out_cap, int n_slots, int m, hipStream_t st);
 extern unsigned long long* g_attn_dbg;
+hipError_t sample_launch(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens,  // decode_sample.hip
+                         hipStream_t st);
+hipError_t token_end_sample_launch(const void* logits, void* tok, int* pos, const int* params, int vocab, hipStream_t st);
+hipError_t token_end_sample_b_launch(const void* logits, const int* slot_tab, void* tok, int* pos_tab, const int* limit, const int* eos,
+                                     int* done, void* out, int* ctr, const int* params, int vocab, int out_cap, int n_slots, int m,
+                                     hipStream_t st);
 hipError_t dequant_w4_launch(const void* qw, const void* scales, const void* zeros, const void* ow, void* out, int N,
                              int K, int G, int n_out, hipStream_t st);
 hipError_t pack_oweight_launch(const void* ow, void* il, int N, int R, hipStream_t st);
@@ -1019,6 +1025,34 @@ int qeft_token_end_batch(const void* logits, const int* slots, void* tokens, int
     if (!aligned16(logits)) return QEFT_ERR_ALIGN;
     return finish(qeft::token_end_b_launch(logits, slots, tokens, pos, limit, eos, done, out, counter, vocab, out_cap, n_slots, m,
                                            (hipStream_t)stream));
+}
+
+// ---- sampled token end (decode_sample.hip)
+int qeft_sample(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens_out,
+                qeft_stream_t stream) {
+    if (m < 1) return QEFT_ERR_BATCH;
+    if (vocab < 1) return QEFT_ERR_SHAPE;
+    if (!logits || !params || !positions || !tokens_out) return QEFT_ERR_NULL;
+    if (!aligned16(logits) || !aligned16(params)) return QEFT_ERR_ALIGN;
+    return finish(qeft::sample_launch(logits, vocab, m, params, positions, tokens_out, (hipStream_t)stream));
+}
+
+int qeft_token_end_sample(const void* logits, void* tok, int* pos, int vocab, const int* params, qeft_stream_t stream) {
+    if (vocab < 1) return QEFT_ERR_SHAPE;
+    if (!logits || !tok || !pos || !params) return QEFT_ERR_NULL;
+    if (!aligned16(logits) || !aligned16(params)) return QEFT_ERR_ALIGN;
+    return finish(qeft::token_end_sample_launch(logits, tok, pos, params, vocab, (hipStream_t)stream));
+}
+
+int qeft_token_end_sample_batch(const void* logits, const int* slots, void* tokens, int* pos, const int* limit, const int* eos,
+                                int* done, void* out, int* counter, const int* params, int vocab, int out_cap, int n_slots, int m,
+                                qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (vocab < 1 || out_cap < 1 || n_slots < 1) return QEFT_ERR_SHAPE;
+    if (!logits || !slots || !tokens || !pos || !limit || !eos || !done || !out || !counter || !params) return QEFT_ERR_NULL;
+    if (!aligned16(logits) || !aligned16(params)) return QEFT_ERR_ALIGN;
+    return finish(qeft::token_end_sample_b_launch(logits, slots, tokens, pos, limit, eos, done, out, counter, params, vocab, out_cap,
+                                                  n_slots, m, (hipStream_t)stream));
 }
 
 

@@ -496,6 +496,8 @@ class DecodeEngine:
         self.host_pos = 0          # host mirror of self.pos (chooses the split; any split is correct at any position)
         self.graphs = {}
         self.greedy = False
+        self.sampling = None        # SamplingParams (seed resolved) while sampled decoding is set (set_sampling)
+        self.sample_rec = torch.zeros(8, dtype=torch.int32, device=dev)     # its device record (graphs read it at replay)
         self.graph = None
         self.use_graph = use_graph
         # v3 path (single GPU, 4 bits, the shapes gemv_v3.h takes): raw-x GEMVs with the norms / SiLU on the producers'
@@ -840,8 +842,17 @@ class DecodeEngine:
         ck(lib.qeft_rmsnorm(h.data_ptr(), None, self.m.model.norm.weight.data_ptr(), None, self.hn.data_ptr(), 1,
                             s.hidden, s.rms_eps, st))
         torch.matmul(self.hn, self.m.lm_head.weight.t(), out=self.logits)
-        ck(lib.qeft_token_end(self.logits.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), s.vocab,
-                              1 if self.greedy else 0, st))
+        self._token_end(st)
+
+    def _token_end(self, st):
+        """tok = the next token (with sampling set: drawn at pos + 1 from the device record; else the argmax if greedy); pos += 1"""
+        s, lib, ck = self.m.shape, self.lib, _lib.check
+        if self.sampling is not None:
+            ck(lib.qeft_token_end_sample(self.logits.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), s.vocab,
+                                         self.sample_rec.data_ptr(), st))
+        else:
+            ck(lib.qeft_token_end(self.logits.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), s.vocab,
+                                  1 if self.greedy else 0, st))
 
     def _token_tail(self, h32, st):
         """final RMSNorm + fp16 lm_head (one launch where the head's width is one the fused kernel takes) + token end"""
@@ -854,8 +865,7 @@ class DecodeEngine:
         else:
             ck(lib.qeft_rmsnorm_f32(h32, self.m.model.norm.weight.data_ptr(), self.hn.data_ptr(), 1, s.hidden, s.rms_eps, st))
             torch.matmul(self.hn, w.t(), out=self.logits)
-        ck(lib.qeft_token_end(self.logits.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), s.vocab,
-                              1 if self.greedy else 0, st))
+        self._token_end(st)
 
     @torch.no_grad()
     def _launch_token_v3(self, linears_only=False, only=None):
@@ -978,16 +988,19 @@ class DecodeEngine:
         self.tok.copy_(tok0)
         if linears_only:
             return graph
-        # a graph bakes in the attention split AND whether token_end writes the greedy token
-        self.graph = self.graphs[(self.attn_split, bool(self.greedy))] = graph
+        # a graph bakes in the attention split AND which token end runs (argmax, none, or a draw)
+        self.graph = self.graphs[self._step_key(self.attn_split)] = graph
         return graph
+
+    def _step_key(self, split):
+        return (split, "sample") if self.sampling is not None else (split, bool(self.greedy))
 
     def precapture(self, max_pos):
         """Capture the graphs of every attention split the positions [host_pos, max_pos) will use (so that none is
         captured inside a timed region)."""
         for sp in sorted({self._split_for(p) for p in (self.host_pos, 255, 256, 1535, 1536, max_pos - 1)
                           if self.host_pos <= p < max_pos}):
-            if (sp, bool(self.greedy)) not in self.graphs:
+            if self._step_key(sp) not in self.graphs:
                 self.capture(split=sp)
 
     def _check_fresh(self):
@@ -995,15 +1008,35 @@ class DecodeEngine:
             raise RuntimeError("the model's outlier weights were replaced (checkpoint.replace_oweight) after this DecodeEngine "
                                "derived its operands from them: build a new DecodeEngine")
 
+    def set_sampling(self, params):
+        """Sampled decoding (a qeft_amd.sampling.SamplingParams) from here on, or None for today's token end (argmax when
+        `greedy`).  While set, every token end draws the next token on the device at the position it will occupy; a None seed
+        is drawn from torch's default generator now.  The record lives in a device buffer that captured graphs read, so new
+        parameters need no recapture.  Tensor-parallel ranks hold bit-identical logits and, with the same record, draw the same
+        token without a collective; so a tensor-parallel engine takes an explicit seed (the same on every rank) and raises
+        ValueError for seed=None, which each rank would draw from its own generator."""
+        if params is None:
+            self.sampling = None
+            return
+        from .sampling import SamplingParams
+        if not isinstance(params, SamplingParams):
+            raise TypeError(f"set_sampling takes a SamplingParams or None, got {type(params).__name__}")
+        if self.tp and params.seed is None:
+            raise ValueError("a tensor-parallel engine needs an explicit sampling seed, the same on every rank (seed=None would "
+                             "be drawn from each rank's own generator and the ranks could decode different tokens)")
+        params = params.resolved()
+        self.sample_rec.copy_(torch.tensor(params.record(), dtype=torch.int32))
+        self.sampling = params
+
     def step(self):
-        """Run one token: consumes self.tok at position self.pos, leaves logits (and, if greedy, the next token)."""
+        """Run one token: consumes self.tok at position self.pos, leaves logits (and, if greedy or sampling, the next token)."""
         if self.host_pos >= self.m.shape.max_seq:
             # the device side would skip the attention (stale output) and keep counting: refuse instead
             raise RuntimeError(f"KV cache full: position {self.host_pos} >= max_seq {self.m.shape.max_seq}")
         self._check_fresh()
         sp = self._split_for(self.host_pos)
         if self.use_graph:
-            g = self.graphs.get((sp, bool(self.greedy)))
+            g = self.graphs.get(self._step_key(sp))
             if g is None:
                 g = self.capture(split=sp)
             g.replay()
@@ -1012,21 +1045,22 @@ class DecodeEngine:
             self._launch_token()
         self.host_pos += 1
 
-    MULTI = int(os.environ.get("QEFT_MULTI_TOKENS", "8"))       # tokens per multi-token graph (greedy decoding only; 16 / 32 measured in round 4)
+    MULTI = int(os.environ.get("QEFT_MULTI_TOKENS", "8"))       # tokens per multi-token graph (greedy or sampled decoding; 16 / 32 measured in round 4)
 
     def run(self, n_tokens):
-        """Greedy decoding of n_tokens tokens (self.greedy must be set): like n_tokens calls of step(), but with hipGraphs of
-        MULTI tokens where the positions allow it -- token_end writes the next token and position on the device, so
-        consecutive tokens need nothing from the host, and one replay per 8 tokens saves 7 of 8 inter-replay gaps (about
-        1 % of a 7B token).  logits hold the last token's values."""
-        assert self.greedy, "run() feeds every token's argmax to the next: greedy decoding only"
+        """Greedy or sampled decoding of n_tokens tokens (self.greedy or set_sampling() must be set): like n_tokens calls of
+        step(), but with hipGraphs of MULTI tokens where the positions allow it -- the token end writes the next token and
+        position on the device, so consecutive tokens need nothing from the host, and one replay per 8 tokens saves 7 of 8
+        inter-replay gaps (about 1 % of a 7B token).  logits hold the last token's values."""
+        assert self.greedy or self.sampling is not None, \
+            "run() feeds every token's successor to the next: greedy or sampled decoding only"
         self._check_fresh()
         multi_ok = self.use_graph and os.environ.get("QEFT_MULTI_TOKEN_GRAPH") != "0"
         while n_tokens > 0:
             p, m = self.host_pos, self.MULTI
             sp = self._split_for(p)
             if multi_ok and n_tokens >= m and p + m <= self.m.shape.max_seq and self._split_for(p + m - 1) == sp:
-                key = (sp, True, m)
+                key = (sp, "sample", m) if self.sampling is not None else (sp, True, m)
                 g = self.graphs.get(key)
                 if g is None:
                     g = self.graphs[key] = self._capture_multi(m, sp)

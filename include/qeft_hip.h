@@ -406,13 +406,22 @@ int qeft_token_end_batch(const void* logits, const int* slots, void* tokens, int
  * qeft_sample: m >= 1 rows, row r uses params[r] and p = positions[r] (int32 [m]); tokens_out int64 [m].
  * qeft_token_end_sample: qeft_token_end(greedy = 1)'s contract (*tok = the token, *pos += 1) with p = *pos + 1.
  * qeft_token_end_sample_batch: qeft_token_end_batch's contract exactly, with row r drawing with params[slots[r]] (params: records
- *   [n_slots][8]) at p = pos[slots[r]] + 1. */
+ *   [n_slots][8]) at p = pos[slots[r]] + 1.
+ * qeft_verify_sample: qeft_verify_greedy(greedy = 1)'s contract for m = 1..8 rows of ONE sequence with the argmax replaced by the
+ *   draw: a[i] = the token of logits row i with the record params (one record) at p = *pos + i + 1, i.e. what
+ *   qeft_token_end_sample would draw there; n = longest prefix with a[i] == tokens[i + 1]; out_tokens[0..n] = tokens[1..n], a[n];
+ *   *n_accepted = n; *tok = a[n]; *pos += n + 1.  T == 0 gives qeft_verify_greedy's outputs bit for bit.  One block per row;
+ *   work: QEFT_VERIFY_SAMPLE_WORK int32 in device memory, zeroed once by the caller: work[0..m) = a[i] of the last call,
+ *   work[8] the launch's arrival count (0 again after every call, so graph replays need no memset), the rest unused. */
+#define QEFT_VERIFY_SAMPLE_WORK 16
 int qeft_sample(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens_out,
                 qeft_stream_t stream);
 int qeft_token_end_sample(const void* logits, void* tok, int* pos, int vocab, const int* params, qeft_stream_t stream);
 int qeft_token_end_sample_batch(const void* logits, const int* slots, void* tokens, int* pos, const int* limit, const int* eos,
                                 int* done, void* out, int* counter, const int* params, int vocab, int out_cap, int n_slots, int m,
                                 qeft_stream_t stream);
+int qeft_verify_sample(const void* logits, const void* tokens, int m, int vocab, const int* params, int* work, void* out_tokens,
+                       int* n_accepted, void* tok, int* pos, qeft_stream_t stream);
 
 /* One-shot all-reduce of the tensor-parallel decode path (csrc/oneshot.hip; no reference counterpart --
  * the reference places whole layers on GPUs, qeft/utils/modelutils.py:21-57).  In-place fp32 sum of t[n] over `world` ranks

@@ -84,6 +84,7 @@ SIGNATURES = {
     "qeft_sample": [_p, _i, _i, _p, _p, _p, _p],
     "qeft_token_end_sample": [_p, _p, _p, _i, _p, _p],
     "qeft_token_end_sample_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "qeft_verify_sample": [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     "qeft_oneshot_mailbox_bytes": [_i, _i],
     "qeft_oneshot_max_world": [],
     "qeft_oneshot_mailbox_alloc": [_i, _i, ctypes.POINTER(ctypes.c_void_p)],

@@ -74,6 +74,8 @@ extern unsigned long long* g_attn_dbg;
 hipError_t sample_launch(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens,  // decode_sample.hip
                          hipStream_t st);
 hipError_t token_end_sample_launch(const void* logits, void* tok, int* pos, const int* params, int vocab, hipStream_t st);
+hipError_t verify_sample_launch(const void* logits, const void* tokens, int m, int vocab, const int* params, int* work, void* out_tokens,
+                                int* n_acc, void* tok, int* pos, hipStream_t st);
 hipError_t token_end_sample_b_launch(const void* logits, const int* slot_tab, void* tok, int* pos_tab, const int* limit, const int* eos,
                                      int* done, void* out, int* ctr, const int* params, int vocab, int out_cap, int n_slots, int m,
                                      hipStream_t st);
@@ -1055,5 +1057,14 @@ int qeft_token_end_sample_batch(const void* logits, const int* slots, void* toke
                                                   n_slots, m, (hipStream_t)stream));
 }
 
+int qeft_verify_sample(const void* logits, const void* tokens, int m, int vocab, const int* params, int* work, void* out_tokens,
+                       int* n_accepted, void* tok, int* pos, qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (vocab < 1) return QEFT_ERR_SHAPE;
+    if (!logits || !tokens || !params || !work || !out_tokens || !n_accepted || !tok || !pos) return QEFT_ERR_NULL;
+    if (!aligned16(logits) || !aligned16(params)) return QEFT_ERR_ALIGN;
+    return finish(qeft::verify_sample_launch(logits, tokens, m, vocab, params, work, out_tokens, n_accepted, tok, pos,
+                                             (hipStream_t)stream));
+}
 
 }  // extern "C"

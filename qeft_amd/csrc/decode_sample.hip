@@ -3,6 +3,7 @@
 //   sample             row r of `logits` with parameter record r, drawn at positions[r] -> tokens[r]      (m rows, any m >= 1)
 //   token_end_sample   token_end's contract (tok, *pos += 1) with a draw at *pos + 1                       (one row)
 //   token_end_sample_b token_end_b's contract (slot table, out / counter tickets, stops) with params[slot]  (m <= 8 rows)
+//   verify_sample      verify_greedy's contract with row i of ONE sequence drawn at *pos + i + 1            (m <= 8 rows)
 // Parameter record (int32 [8]): temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved.
 //
 // Method, per row (one block of 1024 threads): every fp16 logit maps to an order-preserving 16-bit key (NaN -> 0, never kept;
@@ -435,6 +436,39 @@ __global__ __launch_bounds__(1024) void token_end_sample_b_kernel(const f16* __r
     }
 }
 
+// verify_greedy_kernel's contract (decode_verify.hip) with the argmax of row i replaced by the draw at *pos + i + 1 with the
+// sequence's record: what token_end_sample would draw there.  One block per row, so the m rows run side by side.  Block i leaves
+// a[i] in work[i] and takes a ticket in work[kVerifyTicket]; the last arriver forms the accepted prefix and re-arms the ticket.
+// Every thread has read *pos before its block arrives (sample_row synchronises), so the last arriver's store races with nothing.
+constexpr int kVerifyTicket = 8;
+
+template <bool REG>
+__global__ __launch_bounds__(1024) void verify_sample_kernel(const f16* __restrict__ logits, const long long* __restrict__ tokens,
+                                                             int vocab, const int* __restrict__ params, int* __restrict__ work,
+                                                             long long* __restrict__ out_tokens, int* __restrict__ n_acc,
+                                                             long long* __restrict__ tok, int* __restrict__ pos) {
+    __shared__ Smem sm;
+    const int row = blockIdx.x, m = gridDim.x;
+    const int p0 = *pos;
+    const int a = sample_row<REG>(sm, logits + (size_t)row * vocab, vocab, params, row_x0(params, p0 + row + 1));
+    if (threadIdx.x != 0) return;
+    __hip_atomic_store(work + row, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int ticket = __hip_atomic_fetch_add(work + kVerifyTicket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (ticket != m - 1) return;
+    __hip_atomic_store(work + kVerifyTicket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int n = 0;
+    int an = __hip_atomic_load(work, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (n < m - 1 && (long long)an == tokens[n + 1]) {
+        out_tokens[n] = tokens[n + 1];
+        ++n;
+        an = __hip_atomic_load(work + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    out_tokens[n] = an;
+    *n_acc = n;
+    *tok = an;
+    *pos = p0 + n + 1;
+}
+
 }  // namespace
 
 hipError_t sample_launch(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens, hipStream_t st) {
@@ -455,6 +489,14 @@ hipError_t token_end_sample_b_launch(const void* logits, const int* slot_tab, vo
     auto kern = vocab <= kRegChunks * kChunk ? token_end_sample_b_kernel<true> : token_end_sample_b_kernel<false>;
     hipLaunchKernelGGL(kern, dim3(m), dim3(kThreads), 0, st, (const f16*)logits, slot_tab, (long long*)tok, pos_tab, limit, eos, done,
                        (long long*)out, ctr, params, vocab, out_cap, n_slots);
+    return hipGetLastError();
+}
+
+hipError_t verify_sample_launch(const void* logits, const void* tokens, int m, int vocab, const int* params, int* work, void* out_tokens,
+                                int* n_acc, void* tok, int* pos, hipStream_t st) {
+    auto kern = vocab <= kRegChunks * kChunk ? verify_sample_kernel<true> : verify_sample_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(m), dim3(kThreads), 0, st, (const f16*)logits, (const long long*)tokens, vocab, params, work,
+                       (long long*)out_tokens, n_acc, (long long*)tok, pos);
     return hipGetLastError();
 }
 

@@ -1127,7 +1127,8 @@ class DecodeEngine:
             rope=torch.zeros(M, 128, dtype=torch.float32, device=dev),
             ws=torch.zeros(max(ws, 16) // 4, dtype=torch.float32, device=dev),
             out=torch.zeros(M, dtype=torch.long, device=dev),
-            n_acc=torch.zeros(1, dtype=torch.int32, device=dev))
+            n_acc=torch.zeros(1, dtype=torch.int32, device=dev),
+            work=torch.zeros(16, dtype=torch.int32, device=dev))       # qeft_verify_sample's draws and ticket (re-arms itself)
         self._vb = vb
         self.logits_m = torch.zeros(M, s.vocab, **f16)
         return vb
@@ -1135,7 +1136,8 @@ class DecodeEngine:
     @torch.no_grad()
     def _launch_verify(self, m, split, greedy):
         """m-row launch sequence: token begin (m rows) -> per layer q|k|v, multi-query attention, o_proj (+ residual, norm split),
-        gate|up (SiLU epilogue), down_proj (+ residual, next norm split) on m-row GEMVs -> final norm + head (m rows) -> verify."""
+        gate|up (SiLU epilogue), down_proj (+ residual, next norm split) on m-row GEMVs -> final norm + head (m rows) -> verify
+        (greedy == "sample": the sampled verify end, every row drawn with the device record)."""
         s, lib, ck, vb = self.m.shape, self.lib, _lib.check, self._vb
         st = torch.cuda.current_stream(self.dev).cuda_stream
         g, no, eps = s.group_size, s.n_out, s.rms_eps
@@ -1174,6 +1176,11 @@ class DecodeEngine:
         else:           # head widths the fused kernel does not take: as _token_tail
             ck(lib.qeft_rmsnorm_f32(h32, self.m.model.norm.weight.data_ptr(), vb.hn.data_ptr(), m, s.hidden, eps, st))
             torch.matmul(vb.hn[:m], w.t(), out=self.logits_m[:m])
+        if greedy == "sample":
+            ck(lib.qeft_verify_sample(self.logits_m.data_ptr(), vb.toks.data_ptr(), m, s.vocab, self.sample_rec.data_ptr(),
+                                      vb.work.data_ptr(), vb.out.data_ptr(), vb.n_acc.data_ptr(), self.tok.data_ptr(),
+                                      self.pos.data_ptr(), st))
+            return
         ck(lib.qeft_verify_greedy(self.logits_m.data_ptr(), vb.toks.data_ptr(), m, s.vocab, 1 if greedy else 0, vb.out.data_ptr(),
                                   vb.n_acc.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), st))
 
@@ -1202,6 +1209,22 @@ class DecodeEngine:
         of drafts that equal the target's own greedy choice (longest prefix), accepted = those n drafts + the target's token
         after them (n + 1 tokens) -- and advances host_pos by n + 1, with tok = the last accepted token (step() goes on from
         there).  Not greedy: advances by m, exactly as m teacher-forced step() calls; returns None."""
+        return self._verify_pass(tokens, bool(self.greedy))
+
+    @torch.no_grad()
+    def verify_sample(self, tokens):
+        """verify() under sampling (set_sampling() must be set): row i is drawn with the engine's record at position
+        host_pos + i + 1 -- the token a sampled step() would draw there -- and the drafts are accepted while they equal these
+        draws.  Returns (n, accepted) as greedy verify() does and advances host_pos by n + 1, tok = the last accepted token.
+        Every emitted token is the target's own draw on a history of its own draws, so a sequence of passes emits the token
+        stream of sampled run() with the same record, whatever the drafts (up to the rounding of m-row against one-row
+        launches).  The record is read at replay: new parameters need no recapture."""
+        if self.sampling is None:
+            raise RuntimeError("verify_sample needs sampling parameters: call set_sampling(SamplingParams(...)) first")
+        return self._verify_pass(tokens, "sample")
+
+    def _verify_pass(self, tokens, greedy):
+        """One verify pass; greedy: False (teacher-forced rows), True (accept by the argmax) or "sample" (accept by the draw)."""
         why = self._verify_unsupported()
         if why:
             raise RuntimeError(why)
@@ -1215,7 +1238,6 @@ class DecodeEngine:
         vb = self._verify_bufs()
         vb.toks[:m].copy_(toks)
         sp = self._split_for(self.host_pos + m - 1)
-        greedy = bool(self.greedy)
         if self.use_graph:
             key = ("verify", m, sp, greedy)
             g = self.graphs.get(key)

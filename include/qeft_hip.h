@@ -179,7 +179,11 @@ int qeft_silu_mul(const void* gate, const void* up, void* out, int n, qeft_strea
 
 /* One decode token of one sequence: rotary on q/k at position *pos (device int), append k/v to the caches
  * [n_kv][max_seq][128] and compute softmax(q.K^T/sqrt(128)).V (role of single_query_attention,
- * qeft/kernel/attention/ft_attention.cpp:110-181, neox rotary).  head_dim is 128, max_seq % 16 == 0.
+ * qeft/kernel/attention/ft_attention.cpp:110-181, neox rotary).  head_dim is 128, max_seq % 16 == 0 and
+ * 16 <= max_seq <= 32768 (QEFT_ERR_SHAPE otherwise): the kernel keeps one raw fp32 score per cache row in LDS,
+ * (max_seq + 16) * 4 + 9232 bytes, 140 368 at 32768 of the 160 KiB a gfx950 CU has (above 64 KiB, max_seq >= 14064, the
+ * launch raises the kernel's dynamic-LDS limit first).  qeft_single_query_attention[_alibi], qeft_rope_attn_decode_m and
+ * qeft_rope_attn_decode_batch share the ceiling, so that a cache one of them serves can be served by all.
  * cos/sin: fp32 [tab_rows][64], tab_rows >= max_seq (row *pos is used), or tab_rows == 1: the caller has already
  * selected the row of this position (the kernel then has no load that waits for *pos before the rotary).
  * out_pos (optional int32 [n_heads*128]): element i of the attention output is stored at out[out_pos[i]].  With
@@ -187,7 +191,8 @@ int qeft_silu_mul(const void* gate, const void* up, void* out, int n, qeft_strea
  * n_split in {1, 2, 4, 8}: blocks per head (the context is dealt over them; the last block to finish merges the
  * head, in a fixed order).  n_split > 1 needs `workspace`: qeft_attn_workspace_bytes(n_heads, n_split) bytes of
  * device memory, 16-byte aligned, ZERO before the first call and not shared by launches that may overlap; the
- * kernel leaves it ready for the next call. */
+ * kernel leaves it ready for the next call.  A workspace sized for n_split = 8 serves every n_split, in any order (the
+ * arrival counters sit in front of the records, where no split's records reach). */
 int qeft_attn_workspace_bytes(int n_heads, int n_split);   /* 0 for n_split == 1 or bad arguments */
 int qeft_rope_attn_decode(const void* q, const void* k, const void* v, const void* cos_tab, const void* sin_tab,
                           int tab_rows, void* k_cache, void* v_cache, const int* pos, const int* out_pos, void* out,
@@ -198,7 +203,7 @@ int qeft_rope_attn_decode(const void* q, const void* k, const void* v, const voi
  *   k_cache_ft  fp16 [n_kv][128/8][max_seq][8]   (FasterTransformer key layout, ft_attention.cpp:131-133)
  *   v_cache     fp16 [n_kv][max_seq][128]
  * one sequence, head_dim 128, neox rotary from the cos/sin table (tab_rows as above), one block per head, natural output
- * order.  The Python shim loops over the batch and raises for ALiBi / other head sizes / interleaved rotary. */
+ * order, max_seq % 16 == 0 and at most 32768 as above.  The Python shim loops over the batch and raises for ALiBi / other head sizes / interleaved rotary. */
 int qeft_single_query_attention(const void* q, const void* k, const void* v, const void* cos_tab, const void* sin_tab,
                                 int tab_rows, void* k_cache_ft, void* v_cache, const int* pos, void* out, int n_heads,
                                 int n_kv_heads, int max_seq, qeft_stream_t stream);
@@ -344,6 +349,7 @@ int qeft_token_end(const void* logits, void* tok, int* pos, int vocab, int greed
  *   qkv_stride elements apart, out rows out_stride; cos / sin: tab_rows == m -> row i (tab_stride floats apart) is position
  *   *pos + i, tab_rows >= max_seq -> indexed by position.  n_split 1 / 2 / 4 / 8 blocks per kv head; n_split > 1 needs a
  *   zeroed workspace of qeft_attn_m_workspace_bytes(n_heads, n_split, m) bytes (its counters re-arm themselves).
+ *   max_seq % 16 == 0, 16 <= max_seq <= 32768 (the ceiling of qeft_rope_attn_decode, QEFT_ERR_SHAPE above it).
  * qeft_lm_head_f16_m: qeft_lm_head_f16 on m rows: logits [m][vocab] from h32 [m][hidden]; the head streams once.
  * qeft_verify_greedy: greedy: argmax a[i] of every logits row (lowest index among equal maxima), n = longest prefix with
  *   a[i] == tokens[i + 1]; out_tokens[0..n] = tokens[1..n], a[n]; *n_accepted = n; *tok = a[n]; *pos += n + 1.
@@ -376,7 +382,8 @@ int qeft_verify_greedy(const void* logits, const void* tokens, int m, int vocab,
  *   over keys [0, p] of slot s.  A row with done[s] != 0 (done may be NULL) or p outside [0, max_seq) writes nothing to the cache
  *   and zeros to its output.  q / k / v / out / rotary rows as qeft_rope_attn_decode_m (tab_rows == m: row r; tab_rows >= max_seq:
  *   indexed by p).  n_split 1 / 2 / 4 / 8 blocks per (row, kv head); n_split > 1 needs a zeroed workspace of
- *   qeft_attn_batch_workspace_bytes(n_heads, n_split, m) bytes (its counters re-arm themselves).
+ *   qeft_attn_batch_workspace_bytes(n_heads, n_split, m) bytes (its counters re-arm themselves).  max_seq % 16 == 0,
+ *   16 <= max_seq <= 32768 (the ceiling of qeft_rope_attn_decode, QEFT_ERR_SHAPE above it).
  * qeft_token_end_batch: k = counter[0] (counter: device int32 [2], zeroed; counter[1] is the launch's own arrival count).  Row r,
  *   slot s: done[s] != 0 -> out[r][k] = -1 only.  Otherwise a = argmax(logits[r]) (lowest index among equal maxima),
  *   tokens[r] = a (int64), out[r][k] = a (int64, out rows out_cap apart, written for k < out_cap), pos[s] += 1, and done[s] = 1 if

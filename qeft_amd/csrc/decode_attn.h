@@ -25,13 +25,18 @@ __device__ __forceinline__ void st_agent(float* p, float v) { __hip_atomic_store
 __device__ __forceinline__ float ld_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 constexpr int kAttnRec = 132;   // floats per (head, split) record of the workspace: acc[128], max, sum, pad
+// The arrival counters sit IN FRONT of the records, at an offset that does not depend on S: one workspace sized for the largest
+// split then serves every smaller one in any order (the decode engine goes 8 -> 4 -> 1 when a long sequence is followed by a new
+// one).  Behind the records they landed, for a smaller S, inside the records a larger S had left: a ticket read from there never
+// equals S - 1 and no block merges the head.
+__host__ __device__ constexpr size_t attn_ctr_floats(int n_heads) { return ((size_t)n_heads + 3) / 4 * 4; }
 
 // Single-token attention for one sequence.  grid = n_heads * S, block = 256 (4 waves), head_dim = 128.
 //   q,k,v  : this token's projections [n_heads*128], [n_kv*128], [n_kv*128] (fp16)
 //   cos/sin: [tab_rows][64] fp32 rotary table; tab_rows == 1: the row of THIS position, selected by the caller
 //   kc, vc : caches [n_kv][max_seq][128] fp16;  *pos_ptr = index of this token (0-based)
 //   out    : [n_heads*128] fp16, element i stored at out_pos[i] when out_pos is given
-//   ws     : S > 1 only: [n_heads*S][kAttnRec] floats + [n_heads] uint32 arrival counters (zero before first use)
+//   ws     : S > 1 only: [attn_ctr_floats(n_heads)] uint32 arrival counters (zero before first use), then [n_heads*S][kAttnRec] floats
 // 32 blocks pulling a whole head's K and V each are bound by what ONE CU can load (~100 KB took ~4 us), so a head is
 // split over S blocks and the kernel is organised around latency:
 //   * everything that does not depend on `pos` is requested first -- q/k/v, out_pos and, unconditionally, the K
@@ -291,7 +296,7 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
         return;
     }
     // ---- publish this split's record, take a ticket; the last arriver merges the head
-    float* rec = ws + (size_t)(h * S + sp) * kAttnRec;
+    float* rec = ws + attn_ctr_floats(n_heads) + (size_t)(h * S + sp) * kAttnRec;
     if (t < HD) st_agent(rec + t, acc);
     if (t == 0) {
         st_agent(rec + HD, M);
@@ -300,7 +305,7 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     mark(7);
-    unsigned* ctr = (unsigned*)(ws + (size_t)n_heads * S * kAttnRec) + h;
+    unsigned* ctr = (unsigned*)ws + h;
     if (t == 0) {
         const unsigned ticket = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         last_ticket = (ticket == (unsigned)(S - 1));
@@ -316,7 +321,7 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
     }
     if (!last_ticket) return;
     if (t < HD) {
-        const float* r0 = ws + (size_t)h * S * kAttnRec;
+        const float* r0 = ws + attn_ctr_floats(n_heads) + (size_t)h * S * kAttnRec;
         float Mh = -3.0e38f;
         for (int j = 0; j < S; ++j) Mh = fmaxf(Mh, ld_agent(r0 + j * kAttnRec + HD));
         float a2 = 0.f, d2 = 0.f;

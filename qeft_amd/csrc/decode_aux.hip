@@ -360,7 +360,7 @@ hipError_t silu_mul_launch(const void* gate, const void* up, void* out, int n, h
 }
 
 unsigned long long* g_attn_dbg = nullptr;   // lab only: per-wave phase stamps
-size_t attn_workspace_bytes(int n_heads, int S) { return S > 1 ? ((size_t)n_heads * S * kAttnRec + n_heads) * 4 : 0; }
+size_t attn_workspace_bytes(int n_heads, int S) { return S > 1 ? (attn_ctr_floats(n_heads) + (size_t)n_heads * S * kAttnRec) * 4 : 0; }
 
 hipError_t rope_attn_decode_launch(const void* q, const void* k, const void* v, const void* cs, const void* sn, void* kc,
                                    void* vc, const int* pos, const int* out_pos, void* out, void* ws, int n_heads,

@@ -146,6 +146,35 @@ def test_round2_entries_reject_bad_arguments_without_a_gpu():
     assert lib.qeft_decode_linear_blocks(5120) == 160          # between 256 and 512 row sets: two per block
 
 
+def test_attention_entries_refuse_a_cache_above_the_ceiling(lib):
+    """include/qeft_hip.h: max_seq <= 32768 on the four attention entries that share a cache (the one-token kernel keeps one
+    raw fp32 score per cache row in LDS).  32768 + 16 is a multiple of 16 and nothing else about the call is wrong, so the
+    ceiling alone answers QEFT_ERR_SHAPE, before any pointer is looked at; at 32768 the same calls pass the shape checks
+    (their NULL cache is what is refused then)."""
+    P, ERR_SHAPE, ERR_NULL = 1 << 20, 2, 4
+    heads, kv = 32, 8
+
+    def calls(max_seq, kc):
+        return {
+            "qeft_rope_attn_decode": lib.qeft_rope_attn_decode(P, P, P, P, P, 1, kc, P, P, None, P, P, 8, heads, kv, max_seq, None),
+            "qeft_rope_attn_decode_m": lib.qeft_rope_attn_decode_m(P, P, P, 6144, P, P, 128, 4, kc, P, P, None, P, heads * 128, P, 8,
+                                                                   heads, kv, max_seq, 4, None),
+            "qeft_rope_attn_decode_batch": lib.qeft_rope_attn_decode_batch(P, P, P, 6144, P, P, 128, 4, kc, P, P, P, P, None, P,
+                                                                           heads * 128, P, 8, 8, heads, kv, max_seq, 4, None),
+            "qeft_single_query_attention": lib.qeft_single_query_attention(P, P, P, P, P, 1, kc, P, P, P, heads, kv, max_seq, None),
+            "qeft_single_query_attention_alibi": lib.qeft_single_query_attention_alibi(P, P, P, P, P, 1, kc, P, P, P, heads, kv,
+                                                                                       max_seq, P, None),
+        }
+    for name, code in calls(32768 + 16, P).items():
+        assert code == ERR_SHAPE, (name, code)
+    for name, code in calls(32768, None).items():
+        assert code == ERR_NULL, (name, code)
+    # the whole-table rotary form at the ceiling's far side: still the shape, not the table
+    assert lib.qeft_rope_attn_decode(P, P, P, P, P, 32768 + 16, P, P, P, None, P, P, 8, heads, kv, 32768 + 16, None) == ERR_SHAPE
+    text = re.sub(r"\s*\n \*\s*", " ", open(os.path.join(ROOT, "include", "qeft_hip.h")).read())
+    assert text.count("max_seq <= 32768") >= 3 and "at most 32768" in text        # stated where the entries are declared
+
+
 def test_gemm_workspace_follows_the_row_routing(lib):
     """No compute: the split-K workspace the shim asks for matches where gemm_impl will send the rows -- up to 16 rows of a shape
     the decode GEMV serves ride on it (no workspace), 17 .. 64 rows take the weight-stationary tier (gemm_ws.hip, one launch, no

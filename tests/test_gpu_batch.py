@@ -348,6 +348,58 @@ def test_engine_stops_inside_a_multi_token_graph(model2):
     assert be.out[0, :8].tolist()[k_eos:] == [-1] * (8 - k_eos)
 
 
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_engine_rows_cross_the_split_switches_and_reuse_a_long_slot(use_graph):
+    """Long, ragged rows on a 2048-row cache: prompts of 5, 250, 1530 and 1000 tokens teacher-forced for 12 passes, so that one
+    row crosses position 256 and one 1536 inside the run (the pass's split is the longest row's: 4, then 8, which leaves the
+    5-token row's splits without keys).  Then the 1530-token slot is released and a 3-token prompt admitted into it, with the old
+    sequence's K/V still behind it, for 8 more passes.  Every row against the single-sequence engine on that sequence alone."""
+    from qeft_amd.batch import BatchDecodeEngine
+    from qeft_amd.llama import DecodeEngine, QuantLlama, tiny_shape
+    shape = tiny_shape(n_layers=2, hidden=256, inter=512, n_heads=2, vocab=384, max_seq=2048)
+    model = QuantLlama(shape, DEV, seed=11)
+    lengths = [5, 250, 1530, 1000]
+    prompts = _prompts(shape.vocab, lengths, seed=12)
+    feeds = _prompts(shape.vocab, [20, 20, 12, 20], seed=13)
+    be = BatchDecodeEngine(DecodeEngine(model, use_graph=True), max_batch=4, use_graph=use_graph)
+    slots = [be.admit(p, 100) for p in prompts]
+    got = {j: [] for j in range(5)}
+
+    def passes(n, live):
+        for _ in range(n):
+            be.step({slots[j]: int(feeds[j][len(got[j])]) for j in live})
+            for j in live:
+                got[j].append(be.logits(slots[j]).float().clone())
+    passes(12, [0, 1, 2, 3])
+    if use_graph:
+        assert {k[:2] for k in be.graphs} == {(4, 4), (4, 8)}, sorted(be.graphs)      # (rows, split): 1530..1535, then 1536..1541
+    long_slot = slots[2]
+    stale = be.kc[0][long_slot][:, 3:1542].abs().sum().item()
+    be.release(long_slot)
+    prompts.append(_prompts(shape.vocab, [3], seed=14)[0])
+    feeds.append(_prompts(shape.vocab, [8], seed=15)[0])
+    slots.append(be.admit(prompts[4], 100))
+    assert slots[4] == long_slot and stale > 0
+    assert be.kc[0][long_slot][:, 3:1542].abs().sum().item() == stale               # the old sequence's keys are still there
+    passes(8, [0, 1, 3, 4])
+    if use_graph:
+        assert {k[:2] for k in be.graphs} == {(4, 4), (4, 8)}, sorted(be.graphs)      # now the longest row is at 1012..1019: split 4
+    torch.cuda.synchronize()
+    worst = {}
+    for j in range(5):
+        _, ref = _single(model, prompts[j], feed=feeds[j][:len(got[j])])
+        ref, g = torch.stack(ref), torch.stack(got[j])
+        assert torch.isfinite(g).all(), j
+        worst[j] = (g - ref).abs().max().item() / ref.abs().max().item()
+    print(f"[batch long graph={use_graph}] prompts {lengths} + [3 into the released slot]: teacher-forced max|d|/max|ref| = "
+          + ", ".join(f"{worst[j]:.3e}" for j in range(5)))
+    assert max(worst.values()) < REL_TOL, worst
+    for key in [key for key in _SINGLE if key[0] == id(model)]:      # this model goes away: so do its cached single-sequence runs
+        del _SINGLE[key]
+    del be, model
+    torch.cuda.empty_cache()
+
+
 def test_generate_batch_continuous():
     from qeft_amd.batch import generate_batch
     from qeft_amd.llama import DecodeEngine, QuantLlama, tiny_shape

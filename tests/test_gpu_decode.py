@@ -495,6 +495,67 @@ def test_multi_token_graphs_equal_single_token_steps():
         assert torch.equal(a.kc[li][:, :24], b.kc[li][:, :24]) and torch.equal(a.vc[li][:, :24], b.vc[li][:, :24])
 
 
+def test_split_4_after_split_8_on_one_engine():
+    """A smaller split after a larger one on the engine's one attention workspace, in bench.py's order: precapture() warms the
+    graphs of splits 1, 4 and 8 up (the 8-block launch last), then the run starts at position 0 and reaches the 4-block graph
+    with the workspace as the 8-block launch left it.  With the one-token kernel's arrival counters behind records sized by
+    the split, the 4-block launch found the 8-block records where its counters should be, no block drew the last ticket and
+    the attention output stayed what the previous token had left.  Same launches as a fresh engine: bit-equal logits."""
+    from qeft_amd.llama import DecodeEngine, QuantLlama, tiny_shape
+    shape = tiny_shape(n_layers=2, hidden=256, inter=512, n_heads=2, vocab=384, max_seq=2048)
+    model = QuantLlama(shape, DEV, seed=8)
+    tokens = torch.randint(0, shape.vocab, (300,), generator=torch.Generator().manual_seed(6))
+    ref = DecodeEngine(model, use_graph=True).teacher_forced_logits(tokens)
+    eng = DecodeEngine(model, use_graph=True)
+    eng.greedy = False
+    eng.precapture(1600)
+    assert sorted(eng.graphs) == [(1, False), (4, False), (8, False)]
+    got = eng.teacher_forced_logits(tokens)
+    torch.cuda.synchronize()
+    assert torch.isfinite(got).all()
+    assert torch.equal(got[:256], ref[:256])
+    assert torch.equal(got[256:], ref[256:]), (got[256:] - ref[256:]).abs().max().item()
+
+
+@pytest.mark.parametrize("prompt_len,lo,hi", [(240, 1, 4), (1520, 4, 8)])
+def test_multi_token_graphs_around_a_split_switch(prompt_len, lo, hi, monkeypatch):
+    """run() across an attention-split switch (256 and 1536): an 8-token graph bakes its split in, so the rule
+    _split_for(p + MULTI - 1) == split sends the tokens just before a switch through one-token graphs.  40 greedy tokens after
+    a prefill of prompt_len, as run(3) + run(37): the 3 tokens put the run off the multiple of 8 the switch sits on (from
+    prompt_len itself every 8-token graph would end exactly at it and the rule would never bite), then one 8-token graph of the
+    low split, 5 one-token replays of the low split up to the switch and three 8-token graphs of the high split.  Without the
+    rule the 37 would be four 8-token graphs and five one-token steps of the HIGH split.  Against the same 40 tokens from
+    one-token graphs alone: both issue identical launches, so tokens, logits and caches are equal bit for bit."""
+    from qeft_amd.llama import DecodeEngine, QuantLlama, prefill, tiny_shape
+    shape = tiny_shape(n_layers=2, hidden=256, inter=512, n_heads=2, vocab=512, max_seq=2048)
+    model = QuantLlama(shape, DEV, seed=5)
+    prompt = torch.randint(0, shape.vocab, (prompt_len,), generator=torch.Generator().manual_seed(prompt_len)).to(DEV)
+    assert DecodeEngine.MULTI == 8 and (prompt_len + 3 + 8 + 5) in (256, 1536)
+
+    def decode(multi):
+        monkeypatch.setenv("QEFT_MULTI_TOKEN_GRAPH", "1" if multi else "0")
+        eng = DecodeEngine(model, use_graph=True)
+        logits = prefill(model, prompt, engine=eng)
+        eng.greedy = True
+        eng.tok.fill_(int(torch.argmax(logits[-1]).item()))
+        toks = []
+        for n in (3, 37):
+            eng.run(n)
+            toks.append(int(eng.tok.item()))
+        torch.cuda.synchronize()
+        return eng, toks
+    b, tb = decode(True)
+    a, ta = decode(False)
+    print(f"[multi-token] prefill {prompt_len}: graphs {sorted(b.graphs, key=str)} vs single-token {sorted(a.graphs, key=str)}")
+    assert set(a.graphs) == {(lo, True), (hi, True)}
+    assert set(b.graphs) == {(lo, True), (lo, True, 8), (hi, True, 8)}, sorted(b.graphs, key=str)
+    assert ta == tb and a.host_pos == b.host_pos == prompt_len + 40
+    assert torch.equal(a.logits, b.logits) and torch.equal(a.pos, b.pos) and torch.equal(a.tok, b.tok)
+    for li in range(shape.n_layers):
+        assert torch.equal(a.kc[li], b.kc[li]) and torch.equal(a.vc[li], b.vc[li])
+        assert a.kc[li][:, prompt_len:prompt_len + 40].abs().sum().item() > 0 and a.kc[li][:, prompt_len + 40:].eq(0).all()
+
+
 @pytest.mark.parametrize("D,B,H,Hkv,rot,neox,alibi", [(64, 2, 4, 2, 64, True, False), (96, 1, 4, 4, 32, False, True), (32, 1, 8, 8, 0, True, False),
                                                        (256, 2, 2, 1, 256, True, False), (80, 1, 4, 2, 80, True, True), (192, 1, 2, 2, 64, True, False)])
 def test_shim_single_query_attention_other_head_sizes(D, B, H, Hkv, rot, neox, alibi):

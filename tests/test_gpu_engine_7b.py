@@ -76,6 +76,23 @@ def test_engine_7b_crosses_position_256(model7b):
     _compare(got[250:], ref[250:], tokens[250:], nll=False)
 
 
+def test_engine_7b_crosses_position_1536(model7b):
+    """1600 tokens: the engine goes from the 1-block-per-head graph to the 4-block one at position 256 and to the 8-block one at
+    1536 (the split bench.py's contexts run with); the whole run and the positions around and past the second switch."""
+    from qeft_amd.llama import DecodeEngine
+    model, dense = model7b
+    eng = DecodeEngine(model, use_graph=True)
+    tokens = torch.randint(0, model.shape.vocab, (1600,), generator=torch.Generator().manual_seed(4)).to(DEV)
+    got = eng.teacher_forced_logits(tokens)
+    splits = {key[0] for key in eng.graphs}
+    print(f"[7b parity] graphs captured and replayed over 1600 tokens: {sorted(eng.graphs)}")
+    assert splits == {1, 4, 8}, sorted(eng.graphs)
+    ref = model.forward_dense_reference(tokens, dense)
+    torch.cuda.synchronize()
+    _compare(got, ref, tokens)
+    _compare(got[1500:], ref[1500:], tokens[1500:], nll=False)
+
+
 def test_prefill_7b_shape(model7b, monkeypatch):
     """BASELINE config 3 composed at full size: a 2048-token prompt through prefill() -- the launches the bench's
     prefill_2048.whole_model number is made of (q|k|v as one operand with N = 12288, gate|up interleaved in blocks of 64 with the

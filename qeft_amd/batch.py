@@ -131,7 +131,6 @@ class BatchDecodeEngine:
         M = self.n_slots = int(max_batch)
         self.table = SlotTable(M)
         f16, i32 = dict(dtype=torch.float16, device=dev), dict(dtype=torch.int32, device=dev)
-        kvd = s.n_kv_heads * s.head_dim
         self.kc = [torch.zeros(M, s.n_kv_heads, s.max_seq, s.head_dim, **f16) for _ in range(s.n_layers)]
         self.vc = [torch.zeros(M, s.n_kv_heads, s.max_seq, s.head_dim, **f16) for _ in range(s.n_layers)]
         # per slot: pos | limit | eos | done, then the sampling records [M][8] (sampling.py); one upload per admission
@@ -145,18 +144,8 @@ class BatchDecodeEngine:
         self.tok_slot = torch.zeros(M, dtype=torch.long, device=dev)    # per slot, between runs (rows change with the table)
         self.out = torch.full((M, self.OUT_CAP), -1, dtype=torch.long, device=dev)
         self.ctr = torch.zeros(2, **i32)                        # token end's step counter and arrival count
-        n_ssq = max(engine.n_ssq_tb, engine.n_ssq_lin)
-        ws = self.lib.qeft_attn_batch_workspace_bytes(s.n_heads, 8, M)
-        self.h32 = torch.zeros(M, s.hidden, dtype=torch.float32, device=dev)
-        self.xn = torch.zeros(M, s.hidden, **f16)
-        self.ssq = torch.zeros(M * n_ssq + 4, dtype=torch.float32, device=dev)
-        self.qkv = torch.zeros(M, s.hidden + 2 * kvd, **f16)
-        self.att = torch.zeros(M, s.hidden, **f16)
-        self.act = torch.zeros(M, s.inter, **f16)
-        self.hn = torch.zeros(M, s.hidden, **f16)
-        self.rope = torch.zeros(M, 128, dtype=torch.float32, device=dev)
-        self.ws = torch.zeros(max(ws, 16) // 4, dtype=torch.float32, device=dev)
-        self.logits_m = torch.zeros(M, s.vocab, **f16)
+        self.b = llama.m_row_buffers(engine, M, self.lib.qeft_attn_batch_workspace_bytes(s.n_heads, 8, M))
+        self.logits_m = self.b.logits
         self.graphs = {}
         self.rows = []                                          # the row table of the last pass
 
@@ -220,48 +209,27 @@ class BatchDecodeEngine:
 
     @torch.no_grad()
     def _launch(self, m, split, sampled=False):
-        """One token of m rows: token begin -> per layer q|k|v, attention, o_proj (+ residual, norm split), gate|up (SiLU
-        epilogue), down_proj (+ residual, next norm split) -> final norm + head -> token end (sampled: each row draws with its
-        slot's record; greedy rows' records have temperature 0, the argmax)."""
-        s, lib, ck, eng = self.model.shape, self.lib, _lib.check, self.eng
+        """One token of m rows: token begin -> the engine's layers (DecodeEngine._v3_layers) on m-row GEMVs with the batched
+        attention between them -> final norm + head -> token end (sampled: each row draws with its slot's record; greedy rows'
+        records have temperature 0, the argmax)."""
+        s, lib, ck, eng, b = self.model.shape, self.lib, _lib.check, self.eng, self.b
         st = torch.cuda.current_stream(self.dev).cuda_stream
-        g, no, eps = s.group_size, s.n_out, s.rms_eps
-        layers = self.model.model.layers
         kvd = s.n_kv_heads * s.head_dim
         nq = s.hidden + 2 * kvd
-        xn, ssq, h32 = self.xn.data_ptr(), self.ssq.data_ptr(), self.h32.data_ptr()
+        h32, qp, rope = b.h32.data_ptr(), b.qkv.data_ptr(), b.rope.data_ptr()
         slots, pos, done = self.slot_tab.data_ptr(), self.pos.data_ptr(), self.done.data_ptr()
-
-        def lin(op, x, y, mode=0, residual=None, ssq_in=None, n_ssq=0, gamma_out=None):
-            return lib.qeft_decode_linear_m(x, op.qweight.data_ptr(), op.sz_packed.data_ptr(), op.oweight.data_ptr() if no else None,
-                                            None, y, op.outfeatures, op.infeatures, g, no, mode, residual, ssq_in, n_ssq, eps,
-                                            gamma_out, xn if gamma_out else None, ssq if gamma_out else None, m, st)
         ck(lib.qeft_token_begin_norm_batch(self.model.model.embed_tokens.weight.data_ptr(), self.tok.data_ptr(), eng.rope_tab.data_ptr(),
-                                           slots, pos, h32, self.rope.data_ptr(), layers[0].input_layernorm.weight.data_ptr(), xn, ssq,
-                                           s.hidden, s.vocab, s.max_seq, self.n_slots, m, st))
-        n_ssq = eng.n_ssq_tb
-        qp = self.qkv.data_ptr()
-        for li, L in enumerate(layers):
-            pk = eng.v3ops[li]
-            ck(lin(pk["qkv"], xn, qp, ssq_in=ssq, n_ssq=n_ssq))
-            ck(lib.qeft_rope_attn_decode_batch(qp, qp + s.hidden * 2, qp + (s.hidden + kvd) * 2, nq, self.rope.data_ptr(),
-                                               self.rope.data_ptr() + 64 * 4, 128, m, self.kc[li].data_ptr(), self.vc[li].data_ptr(),
-                                               slots, pos, done, eng.att_pos[li].data_ptr() if eng.att_pos[li] is not None else None,
-                                               self.att.data_ptr(), s.hidden, self.ws.data_ptr(), split, self.n_slots, s.n_heads,
+                                           slots, pos, h32, rope, self.model.model.layers[0].input_layernorm.weight.data_ptr(),
+                                           b.xn.data_ptr(), b.ssq.data_ptr(), s.hidden, s.vocab, s.max_seq, self.n_slots, m, st))
+
+        def attn(li):
+            ck(lib.qeft_rope_attn_decode_batch(qp, qp + s.hidden * 2, qp + (s.hidden + kvd) * 2, nq, rope, rope + 64 * 4, 128, m,
+                                               self.kc[li].data_ptr(), self.vc[li].data_ptr(), slots, pos, done,
+                                               eng.att_pos[li].data_ptr() if eng.att_pos[li] is not None else None,
+                                               b.att.data_ptr(), s.hidden, b.ws.data_ptr(), split, self.n_slots, s.n_heads,
                                                s.n_kv_heads, s.max_seq, m, st))
-            ck(lin(pk["o"], self.att.data_ptr(), h32, residual=h32, gamma_out=L.post_attention_layernorm.weight.data_ptr()))
-            n_ssq = eng.n_ssq_lin
-            ck(lin(pk["gu"], xn, self.act.data_ptr(), mode=1, ssq_in=ssq, n_ssq=n_ssq))
-            nxt = layers[li + 1].input_layernorm.weight.data_ptr() if li + 1 < len(layers) else None
-            ck(lin(pk["d"], self.act.data_ptr(), h32, residual=h32, gamma_out=nxt))
-        w = self.model.lm_head.weight
-        if s.hidden in (512, 1024, 2048, 4096, 5120, 8192) and w.dtype == torch.float16 and w.is_contiguous() \
-                and os.environ.get("QEFT_LM_HEAD_TORCH") != "1":
-            ck(lib.qeft_lm_head_f16_m(h32, self.model.model.norm.weight.data_ptr(), w.data_ptr(), self.logits_m.data_ptr(), s.hidden,
-                                      s.vocab, eps, m, st))
-        else:           # head widths the fused kernel does not take: as DecodeEngine._launch_verify
-            ck(lib.qeft_rmsnorm_f32(h32, self.model.model.norm.weight.data_ptr(), self.hn.data_ptr(), m, s.hidden, eps, st))
-            torch.matmul(self.hn[:m], w.t(), out=self.logits_m[:m])
+        eng._v3_layers(b, eng._lin_m(b, m, st), attn)
+        eng._head(h32, b.hn, self.logits_m, m, st)
         if sampled:
             ck(lib.qeft_token_end_sample_batch(self.logits_m.data_ptr(), slots, self.tok.data_ptr(), pos, self.limit.data_ptr(),
                                                self.eos.data_ptr(), done, self.out.data_ptr(), self.ctr.data_ptr(),
@@ -271,33 +239,14 @@ class BatchDecodeEngine:
                                         self.eos.data_ptr(), done, self.out.data_ptr(), self.ctr.data_ptr(), s.vocab, self.OUT_CAP,
                                         self.n_slots, m, st))
 
-    def _capture(self, m, split, n_tok, sampled=False):
-        """A graph of n_tok passes of m rows (after a warm-up pass on a side stream, as torch requires; the warm-up's state
-        changes are undone -- the K/V rows it wrote are rewritten by the real pass)."""
-        cur = torch.cuda.current_stream(self.dev)
-        side = torch.cuda.Stream(self.dev)
-        side.wait_stream(cur)
-        saved = [t.clone() for t in (self.state, self.tok, self.ctr, self.out)]
-        with torch.cuda.stream(side):
-            self._launch(m, split, sampled)
-        cur.wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        for t, v in zip((self.state, self.tok, self.ctr, self.out), saved):
-            t.copy_(v)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for _ in range(n_tok):
-                self._launch(m, split, sampled)
-        for t, v in zip((self.state, self.tok, self.ctr, self.out), saved):
-            t.copy_(v)
-        return graph
-
     def _pass(self, m, split, n_tok, sampled=False):
+        """n_tok passes of m rows; with graphs, one graph per (m, split, n_tok, token end), captured on first use."""
         if self.use_graph:
             key = (m, split, n_tok, "sample") if sampled else (m, split, n_tok)
             g = self.graphs.get(key)
             if g is None:
-                g = self.graphs[key] = self._capture(m, split, n_tok, sampled)
+                g = self.graphs[key] = llama.capture_graph(self.dev, lambda: self._launch(m, split, sampled), n_tok,
+                                                           (self.state, self.tok, self.ctr, self.out))
             g.replay()
         else:
             for _ in range(n_tok):

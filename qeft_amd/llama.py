@@ -15,6 +15,7 @@ used by the tests and by `eval_nll` as the parity target ("PPL vs reference" on 
 import ctypes
 import os
 import math
+import types
 from dataclasses import dataclass
 
 import torch
@@ -103,6 +104,23 @@ class _Norm(nn.Module):
         self.weight = nn.Parameter(weight, requires_grad=False)
 
 
+# the seven quantized linears of a decoder layer: (HF group attribute, HF name)
+LINEARS = (("self_attn", "q_proj"), ("self_attn", "k_proj"), ("self_attn", "v_proj"), ("self_attn", "o_proj"),
+           ("mlp", "gate_proj"), ("mlp", "up_proj"), ("mlp", "down_proj"))
+
+
+def layer_linears(L):
+    """(HF name, module) of the seven linears of decoder layer L."""
+    return ((nm, getattr(getattr(L, grp), nm)) for grp, nm in LINEARS)
+
+
+def _inverse_permutation(reorder_ids):
+    """inv with inv[reorder_ids[j]] = j: natural index -> the column o_proj holds it in (outliers last)."""
+    inv = torch.empty_like(reorder_ids)
+    inv[reorder_ids] = torch.arange(reorder_ids.numel(), device=inv.device)
+    return inv
+
+
 class QuantLlama(nn.Module):
     """Module tree with HF's attribute names; every decoder linear is a packed QuantLinear."""
 
@@ -141,13 +159,15 @@ class QuantLlama(nn.Module):
             L.post_attention_layernorm = _Norm((1.0 + 0.1 * torch.randn(s.hidden, generator=gen)).half().to(device))
             layers.append(L)
         self.model.layers = nn.ModuleList(layers)
+        self._finish(device)
+
+    def _finish(self, device):
+        """Common end of both constructors: frozen parameters and the rotary tables [max_seq][head_dim / 2]."""
         for prm in self.parameters():
             prm.requires_grad_(False)
-        half = s.head_dim // 2
-        inv = 1.0 / (s.rope_theta ** (torch.arange(0, half, dtype=torch.float64) / half))
-        ang = torch.arange(s.max_seq, dtype=torch.float64)[:, None] * inv[None, :]
-        self.register_buffer("rope_cos", ang.cos().float().to(device), persistent=False)
-        self.register_buffer("rope_sin", ang.sin().float().to(device), persistent=False)
+        cos, sin = qeft_cuda.rope_cos_sin(self.shape.rope_theta, self.shape.head_dim // 2, self.shape.max_seq)
+        self.register_buffer("rope_cos", cos.to(device), persistent=False)
+        self.register_buffer("rope_sin", sin.to(device), persistent=False)
 
     # ------------------------------------------------------------------ packed checkpoint -> model
     @classmethod
@@ -216,16 +236,14 @@ class QuantLlama(nn.Module):
         for li in range(n_layers):
             L = _Layer()
             L.self_attn, L.mlp = _Attn(), _Mlp()
-            for grp, mod, names in (("self_attn", L.self_attn, ("q_proj", "k_proj", "v_proj", "o_proj")),
-                                    ("mlp", L.mlp, ("gate_proj", "up_proj", "down_proj"))):
-                for nm in names:
-                    full = f"model.layers.{li}.{grp}.{nm}"
-                    qi = infos[full]
-                    n_rows = sd[full + ".scales"].shape[1]
-                    k_cols = hidden if nm != "down_proj" else inter
-                    g = qi.group_size if qi.group_size and qi.group_size > 0 else -1
-                    setattr(mod, nm, QuantLinear(int(qi.bits), k_cols, n_rows, (full + ".bias") in sd, torch.float16, int(qi.n_out),
-                                                 g, bool(getattr(qi, "reorder", True)), full))
+            for grp, nm in LINEARS:
+                full = f"model.layers.{li}.{grp}.{nm}"
+                qi = infos[full]
+                n_rows = sd[full + ".scales"].shape[1]
+                k_cols = hidden if nm != "down_proj" else inter
+                g = qi.group_size if qi.group_size and qi.group_size > 0 else -1
+                setattr(getattr(L, grp), nm, QuantLinear(int(qi.bits), k_cols, n_rows, (full + ".bias") in sd, torch.float16,
+                                                         int(qi.n_out), g, bool(getattr(qi, "reorder", True)), full))
             L.input_layernorm = _Norm(torch.empty(hidden, dtype=torch.float16))
             L.post_attention_layernorm = _Norm(torch.empty(hidden, dtype=torch.float16))
             layers.append(L)
@@ -237,32 +255,22 @@ class QuantLlama(nn.Module):
         self.unexpected_keys = list(unexpected)      # e.g. rotary inv_freq buffers of an HF export: not used here
         self.to(device)
         for L in self.model.layers:
-            for mod in (L.self_attn.q_proj, L.self_attn.k_proj, L.self_attn.v_proj, L.self_attn.o_proj, L.mlp.gate_proj,
-                        L.mlp.up_proj, L.mlp.down_proj):
+            for _, mod in layer_linears(L):
                 mod.set_kernel()
-        for prm in self.parameters():
-            prm.requires_grad_(False)
-        half = shape.head_dim // 2
-        inv = 1.0 / (rope_theta ** (torch.arange(0, half, dtype=torch.float64) / half))
-        ang = torch.arange(max_seq, dtype=torch.float64)[:, None] * inv[None, :]
-        self.register_buffer("rope_cos", ang.cos().float().to(device), persistent=False)
-        self.register_buffer("rope_sin", ang.sin().float().to(device), persistent=False)
+        self._finish(device)
         return self
 
     # ------------------------------------------------------------------ dense fp32 reference
     @torch.no_grad()
     def dense_weights(self):
         """Dense dequantised fp32 weights per layer (through the HIP dequant kernel, itself bit-exact vs the oracle)."""
-        from . import qeft_cuda
         out = []
         for L in self.model.layers:
             d = {}
-            for grp, names in (("self_attn", ("q_proj", "k_proj", "v_proj", "o_proj")), ("mlp", ("gate_proj", "up_proj", "down_proj"))):
-                for n in names:
-                    ql = getattr(getattr(L, grp), n)
-                    qw = ql._qweight4().clone() if ql.bits == 3 else ql.qweight
-                    d[n] = qeft_cuda.dequantize_weight_4bit_qeft(qw, ql.scales, ql.scaled_zeros,
-                                                                 ql.oweight if ql.outlierfeatures else None).float()
+            for n, ql in layer_linears(L):
+                qw = ql._qweight4().clone() if ql.bits == 3 else ql.qweight
+                d[n] = qeft_cuda.dequantize_weight_4bit_qeft(qw, ql.scales, ql.scaled_zeros,
+                                                             ql.oweight if ql.outlierfeatures else None).float()
             out.append(d)
         return out
 
@@ -410,6 +418,50 @@ def _ptr_array(tensors):
     for i, t in enumerate(tensors):
         arr[i] = t.data_ptr() if t is not None else None
     return arr
+
+
+def capture_graph(dev, launch, n, keep):
+    """n calls of launch() as one hipGraph.  torch wants the launches to have run once before the capture: a warm-up call on a
+    side stream forked off the current one, joined again and synchronised.  The tensors of `keep` (the state a launch advances:
+    position, token, counters) hold their values of now after the warm-up and after the capture; whatever else the warm-up wrote
+    (K/V rows at the current positions, logits) is rewritten by the first replay."""
+    cur, side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+    saved = [t.clone() for t in keep]
+
+    def restore():
+        for t, v in zip(keep, saved):
+            t.copy_(v)
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        launch()
+    cur.wait_stream(side)
+    torch.cuda.synchronize(dev)
+    restore()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(n):
+            launch()
+    restore()
+    return graph
+
+
+def m_row_buffers(eng, M, attn_ws_bytes):
+    """The static buffers of an m-row v3 pass (m <= M) on `eng`'s weights, [M] rows each: the verify pass and the batch engine
+    each hold one set and add their own state to it."""
+    s, dev = eng.m.shape, eng.dev
+    f16, f32 = dict(dtype=torch.float16, device=dev), dict(dtype=torch.float32, device=dev)
+    kvd = s.n_kv_heads * s.head_dim
+    return types.SimpleNamespace(
+        h32=torch.zeros(M, s.hidden, **f32),
+        xn=torch.zeros(M, s.hidden, **f16),
+        ssq=torch.zeros(M * max(eng.n_ssq_tb, eng.n_ssq_lin) + 4, **f32),
+        qkv=torch.zeros(M, s.hidden + 2 * kvd, **f16),
+        att=torch.zeros(M, s.hidden, **f16),
+        act=torch.zeros(M, s.inter, **f16),
+        hn=torch.zeros(M, s.hidden, **f16),
+        rope=torch.zeros(M, 128, **f32),
+        ws=torch.zeros(max(attn_ws_bytes, 16) // 4, **f32),
+        logits=torch.zeros(M, s.vocab, **f16))
 
 
 class DecodeEngine:
@@ -580,13 +632,14 @@ class DecodeEngine:
             self.qkv_out = torch.zeros(s.hidden + 2 * kvd, **f16)      # q | k | v of one launch; self.q / k / v are views
             self.q, self.k, self.v = self.qkv_out[:s.hidden], self.qkv_out[s.hidden:s.hidden + kvd], self.qkv_out[s.hidden + kvd:]
             self.v3ops = []
+            # the one-token buffers under the names the layer stack reads (_v3_layers; the m-row sets: m_row_buffers)
+            self.row1 = types.SimpleNamespace(h32=self.h32, xn=self.xn, ssq=self.ssq, qkv=self.qkv_out, att=self.att, act=self.act)
         # per-layer local linears + argument packs (host arrays of device pointers must stay alive)
         self.lin = []
         self.packs = []
         self.att_pos = []   # per layer: where attention output element i goes so that o_proj needs no gather
         for L in model.model.layers:
-            a, mlp = L.self_attn, L.mlp
-            names = dict(q=a.q_proj, k=a.k_proj, v=a.v_proj, o=a.o_proj, g=mlp.gate_proj, u=mlp.up_proj, d=mlp.down_proj)
+            names = {nm[0]: ql for nm, ql in layer_linears(L)}      # q, k, v, o, g(ate), u(p), d(own)
             if self.tp3:
                 self.tp3ops.append(self._build_tp3_layer(names))
                 continue
@@ -594,18 +647,12 @@ class DecodeEngine:
                 names = {kk: shard_quantlinear(vv, self.rank, P).to(dev) for kk, vv in names.items()}
             self.lin.append(names)
             o = names["o"]
-            if hasattr(o, "reorder_ids"):
-                inv = torch.empty_like(o.reorder_ids)
-                inv[o.reorder_ids] = torch.arange(o.reorder_ids.numel(), device=inv.device)
-                self.att_pos.append(inv.to(torch.int32).to(dev))
-            else:
-                self.att_pos.append(None)
+            self.att_pos.append(_inverse_permutation(o.reorder_ids).to(torch.int32).to(dev) if hasattr(o, "reorder_ids") else None)
             qkv = [names["q"], names["k"], names["v"]]
             gu = [names["g"], names["u"]]
             no = s.n_out
             if self.v3:
                 # derived operands (qeft_amd/fuse.py): q|k|v concatenated, gate|up pair-interleaved for the SiLU epilogue
-                from . import fuse
                 self.v3ops.append(dict(qkv=fuse.concat_linears(qkv), o=fuse.single(names["o"]),
                                        gu=fuse.pair_interleave(*gu), d=fuse.single(names["d"])))
             if tp:
@@ -632,16 +679,11 @@ class DecodeEngine:
     def _build_tp3_layer(self, names):
         """Operands of one decoder layer for this rank (Megatron pairing, fuse.py): row shards of q|k|v and gate|up, column
         shards of o_proj and down_proj with their zero-initialised x vectors (only owned positions are ever written)."""
-        from . import fuse
         from .sharded import shard_quantlinear
         s, P, rk, dev = self.m.shape, self.P, self.rank, self.dev
         row = {kk: shard_quantlinear(names[kk], rk, P).to(dev) for kk in ("q", "k", "v", "g", "u")}
         o, d = names["o"], names["d"]
-        if hasattr(o, "reorder_ids"):                   # natural index -> o_proj's column (outliers last)
-            inv = torch.empty_like(o.reorder_ids)
-            inv[o.reorder_ids] = torch.arange(o.reorder_ids.numel(), device=inv.device)
-        else:
-            inv = torch.arange(s.hidden, device=dev)
+        inv = _inverse_permutation(o.reorder_ids) if hasattr(o, "reorder_ids") else torch.arange(s.hidden, device=dev)
         o_op, att_pos = fuse.column_shard(o, inv[rk * self.hs:(rk + 1) * self.hs])
         d_op, d_pos = fuse.column_shard(d, torch.arange(rk * self.its, (rk + 1) * self.its, device=dev))
         lead = int(d_pos[0])
@@ -736,7 +778,6 @@ class DecodeEngine:
     @torch.no_grad()
     def _launch_token(self, linears_only=False, only=None):
         """only (with linears_only): launch just one GEMV of every layer -- "qkv", "o", "gu" or "d" -- for per-kernel timing."""
-        import torch.distributed as dist
         self.n_collectives = 0
         if self.v3:
             return self._launch_token_v3(linears_only, only)
@@ -780,20 +821,9 @@ class DecodeEngine:
             if not linears_only:
                 if tp:      # local heads only: q/k/v slices straight from the grouped GEMV, natural output order
                     qp = self.qkv_loc.data_ptr()
-                    ck(lib.qeft_rope_attn_decode(qp, qp + self.hs * 2, qp + (self.hs + self.kvs) * 2,
-                                                 self.rope_row.data_ptr(), self.rope_row.data_ptr() + 64 * 4, 1,
-                                                 self.kc[li].data_ptr(), self.vc[li].data_ptr(), self.pos.data_ptr(), None,
-                                                 self.att_loc.data_ptr(),
-                                                 self.attn_ws.data_ptr() if self.attn_ws is not None else None,
-                                                 self.attn_split, self.heads_l, self.kv_heads_l, s.max_seq, st))
+                    self._attn(li, qp, qp + self.hs * 2, qp + (self.hs + self.kvs) * 2, None, self.att_loc, st)
                 else:
-                    ck(lib.qeft_rope_attn_decode(self.q.data_ptr(), self.k.data_ptr(), self.v.data_ptr(),
-                                                 self.rope_row.data_ptr(), self.rope_row.data_ptr() + 64 * 4, 1,
-                                                 self.kc[li].data_ptr(), self.vc[li].data_ptr(), self.pos.data_ptr(),
-                                                 self.att_pos[li].data_ptr() if self.att_pos[li] is not None else None,
-                                                 self.att.data_ptr(),
-                                                 self.attn_ws.data_ptr() if self.attn_ws is not None else None,
-                                                 self.attn_split, s.n_heads, s.n_kv_heads, s.max_seq, st))
+                    self._attn(li, self.q.data_ptr(), self.k.data_ptr(), self.v.data_ptr(), self.att_pos[li], self.att, st)
             if tp:
                 self._all_gather(self.att, self.att_loc)      # natural head order (ranks own consecutive heads)
             o = lin["o"]
@@ -854,63 +884,99 @@ class DecodeEngine:
             ck(lib.qeft_token_end(self.logits.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), s.vocab,
                                   1 if self.greedy else 0, st))
 
-    def _token_tail(self, h32, st):
-        """final RMSNorm + fp16 lm_head (one launch where the head's width is one the fused kernel takes) + token end"""
+    def _attn(self, li, q, k, v, att_pos, out, st):
+        """Layer li's one-token attention: rotary on q / k (device pointers; this rank's heads), K/V append at pos, attention
+        over the cache, the output written to `out` at the indices `att_pos` (None: natural order)."""
+        rope = self.rope_row.data_ptr()
+        _lib.check(self.lib.qeft_rope_attn_decode(q, k, v, rope, rope + 64 * 4, 1, self.kc[li].data_ptr(), self.vc[li].data_ptr(),
+                                                  self.pos.data_ptr(), att_pos.data_ptr() if att_pos is not None else None,
+                                                  out.data_ptr(), self.attn_ws.data_ptr(), self.attn_split, self.heads_l,
+                                                  self.kv_heads_l, self.m.shape.max_seq, st))
+
+    def _head(self, h32, hn, logits, m, st):
+        """Final RMSNorm of the fp32 residual rows at h32 (a device pointer) + fp16 lm_head -> logits[:m]: one launch where the
+        head's width is one the fused kernel takes, else the norm into hn[:m] and torch's matmul.  m None: the one-token entry;
+        m rows: the m-row entry (m = 1 included)."""
         s, lib, ck = self.m.shape, self.lib, _lib.check
-        w = self.m.lm_head.weight
+        w, gamma = self.m.lm_head.weight, self.m.model.norm.weight.data_ptr()
         if s.hidden in (512, 1024, 2048, 4096, 5120, 8192) and w.dtype == torch.float16 and w.is_contiguous() \
                 and os.environ.get("QEFT_LM_HEAD_TORCH") != "1":
-            ck(lib.qeft_lm_head_f16(h32, self.m.model.norm.weight.data_ptr(), w.data_ptr(), self.logits.data_ptr(), s.hidden, s.vocab,
-                                    s.rms_eps, st))
+            if m is None:
+                ck(lib.qeft_lm_head_f16(h32, gamma, w.data_ptr(), logits.data_ptr(), s.hidden, s.vocab, s.rms_eps, st))
+            else:
+                ck(lib.qeft_lm_head_f16_m(h32, gamma, w.data_ptr(), logits.data_ptr(), s.hidden, s.vocab, s.rms_eps, m, st))
         else:
-            ck(lib.qeft_rmsnorm_f32(h32, self.m.model.norm.weight.data_ptr(), self.hn.data_ptr(), 1, s.hidden, s.rms_eps, st))
-            torch.matmul(self.hn, w.t(), out=self.logits)
+            ck(lib.qeft_rmsnorm_f32(h32, gamma, hn.data_ptr(), m or 1, s.hidden, s.rms_eps, st))
+            if m is None:
+                torch.matmul(hn, w.t(), out=logits)
+            else:
+                torch.matmul(hn[:m], w.t(), out=logits[:m])
+
+    def _token_tail(self, h32, st):
+        """final RMSNorm + fp16 lm_head + token end"""
+        self._head(h32, self.hn, self.logits, None, st)
         self._token_end(st)
 
-    @torch.no_grad()
-    def _launch_token_v3(self, linears_only=False, only=None):
-        """One token on the v3 GEMV (gemv_v3.h): every quantized linear reads its fp16 input vector as it is; the RMSNorms
-        are split into (h * gamma, partial sums of h^2) on the producer's epilogue and a deferred 1/rms on the consumer's;
-        SiLU(gate) * up is formed in the gate|up launch; the residual stream h32 stays fp32."""
-        s, lib, ck = self.m.shape, self.lib, _lib.check
-        st = torch.cuda.current_stream(self.dev).cuda_stream
+    def _lin_m(self, b, m, st):
+        """lin(op, x, y, ...) of an m-row pass on the buffer set b: one launch of the m-row v3 GEMV (arguments as lin in
+        _launch_token_v3)."""
+        s, lib = self.m.shape, self.lib
         g, no, eps = s.group_size, s.n_out, s.rms_eps
-        layers = self.m.model.layers
-        xn, ssq, h32 = self.xn.data_ptr(), self.ssq.data_ptr(), self.h32.data_ptr()
-
-        entry = lib.qeft_decode_linear_w3 if self.bits == 3 else lib.qeft_decode_linear
+        xn, ssq = b.xn.data_ptr(), b.ssq.data_ptr()
 
         def lin(op, x, y, mode=0, residual=None, ssq_in=None, n_ssq=0, gamma_out=None):
-            return entry(x, op.qweight.data_ptr(), op.sz_packed.data_ptr(),
-                                          op.oweight.data_ptr() if no else None, None, y, op.outfeatures, op.infeatures, g, no,
-                                          mode, residual, ssq_in, n_ssq, eps, gamma_out, xn if gamma_out else None,
-                                          ssq if gamma_out else None, st)
+            return lib.qeft_decode_linear_m(x, op.qweight.data_ptr(), op.sz_packed.data_ptr(), op.oweight.data_ptr() if no else None,
+                                            None, y, op.outfeatures, op.infeatures, g, no, mode, residual, ssq_in, n_ssq, eps,
+                                            gamma_out, xn if gamma_out else None, ssq if gamma_out else None, m, st)
+        return lin
 
-        def pick(tag):
-            return lin if only in (None, tag) else (lambda *a, **kw: 0)
-        if not linears_only:
-            ck(lib.qeft_token_begin_norm(self.m.model.embed_tokens.weight.data_ptr(), self.tok.data_ptr(),
-                                         self.rope_tab.data_ptr(), self.pos.data_ptr(), h32, self.rope_row.data_ptr(),
-                                         layers[0].input_layernorm.weight.data_ptr(), xn, ssq, s.hidden, s.vocab, s.max_seq, st))
+    def _v3_layers(self, b, lin, attn, only=None):
+        """The decoder layers of one v3 pass (gemv_v3.h) on the buffer set b (h32, xn, ssq, qkv, att, act): per layer q|k|v,
+        attn(li), o_proj (+ residual; the post-attention norm's gamma out), gate|up (SiLU epilogue), down_proj (+ residual; the
+        next layer's gamma out, none after the last).  Every quantized linear reads its fp16 input vector as it is: the RMSNorms
+        are split into (h * gamma -> xn, partial sums of h^2 -> ssq) on the producer's epilogue and a deferred 1/rms on the
+        consumer's (token begin leaves n_ssq_tb partial sums per row, a linear n_ssq_lin); the residual stream h32 stays fp32.
+        lin(op, x, y, mode, residual, ssq_in, n_ssq, gamma_out) is the path's linear launch, attn(li) its attention (None: no
+        attention); only: launch just the linears with that tag ("qkv", "o", "gu" or "d")."""
+        ck, layers = _lib.check, self.m.model.layers
+        xn, ssq, h32 = b.xn.data_ptr(), b.ssq.data_ptr(), b.h32.data_ptr()
+        qkv, att, act = b.qkv.data_ptr(), b.att.data_ptr(), b.act.data_ptr()
+
+        lin_qkv, lin_o, lin_gu, lin_d = (lin if only in (None, tag) else (lambda *a, **kw: 0) for tag in ("qkv", "o", "gu", "d"))
         n_ssq = self.n_ssq_tb
         for li, L in enumerate(layers):
             pk = self.v3ops[li]
-            ck(pick("qkv")(pk["qkv"], xn, self.qkv_out.data_ptr(), ssq_in=ssq, n_ssq=n_ssq))
-            if not linears_only:
-                ck(lib.qeft_rope_attn_decode(self.q.data_ptr(), self.k.data_ptr(), self.v.data_ptr(),
-                                             self.rope_row.data_ptr(), self.rope_row.data_ptr() + 64 * 4, 1,
-                                             self.kc[li].data_ptr(), self.vc[li].data_ptr(), self.pos.data_ptr(),
-                                             self.att_pos[li].data_ptr() if self.att_pos[li] is not None else None,
-                                             self.att.data_ptr(),
-                                             self.attn_ws.data_ptr() if self.attn_ws is not None else None,
-                                             self.attn_split, s.n_heads, s.n_kv_heads, s.max_seq, st))
-            ck(pick("o")(pk["o"], self.att.data_ptr(), h32, residual=h32, gamma_out=L.post_attention_layernorm.weight.data_ptr()))
+            ck(lin_qkv(pk["qkv"], xn, qkv, ssq_in=ssq, n_ssq=n_ssq))
+            if attn is not None:
+                attn(li)
+            ck(lin_o(pk["o"], att, h32, residual=h32, gamma_out=L.post_attention_layernorm.weight.data_ptr()))
             n_ssq = self.n_ssq_lin
-            ck(pick("gu")(pk["gu"], xn, self.act.data_ptr(), mode=1, ssq_in=ssq, n_ssq=n_ssq))
+            ck(lin_gu(pk["gu"], xn, act, mode=1, ssq_in=ssq, n_ssq=n_ssq))
             nxt = layers[li + 1].input_layernorm.weight.data_ptr() if li + 1 < len(layers) else None
-            ck(pick("d")(pk["d"], self.act.data_ptr(), h32, residual=h32, gamma_out=nxt))
+            ck(lin_d(pk["d"], act, h32, residual=h32, gamma_out=nxt))
+
+    @torch.no_grad()
+    def _launch_token_v3(self, linears_only=False, only=None):
+        """One token on the v3 GEMV: token begin, the layers (_v3_layers) on the one-token entries, head and token end.
+        linears_only: the layers' GEMVs alone."""
+        s, lib, ck, b = self.m.shape, self.lib, _lib.check, self.row1
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        g, no, eps = s.group_size, s.n_out, s.rms_eps
+        xn, ssq, h32 = b.xn.data_ptr(), b.ssq.data_ptr(), b.h32.data_ptr()
+        entry = lib.qeft_decode_linear_w3 if self.bits == 3 else lib.qeft_decode_linear
+
+        def lin(op, x, y, mode=0, residual=None, ssq_in=None, n_ssq=0, gamma_out=None):
+            return entry(x, op.qweight.data_ptr(), op.sz_packed.data_ptr(), op.oweight.data_ptr() if no else None, None, y,
+                         op.outfeatures, op.infeatures, g, no, mode, residual, ssq_in, n_ssq, eps, gamma_out,
+                         xn if gamma_out else None, ssq if gamma_out else None, st)
         if linears_only:
-            return
+            return self._v3_layers(b, lin, None, only)
+        ck(lib.qeft_token_begin_norm(self.m.model.embed_tokens.weight.data_ptr(), self.tok.data_ptr(), self.rope_tab.data_ptr(),
+                                     self.pos.data_ptr(), h32, self.rope_row.data_ptr(),
+                                     self.m.model.layers[0].input_layernorm.weight.data_ptr(), xn, ssq, s.hidden, s.vocab,
+                                     s.max_seq, st))
+        q, k, v = self.q.data_ptr(), self.k.data_ptr(), self.v.data_ptr()
+        self._v3_layers(b, lin, lambda li: self._attn(li, q, k, v, self.att_pos[li], self.att, st), only)
         self._token_tail(h32, st)
 
     @torch.no_grad()
@@ -949,12 +1015,7 @@ class DecodeEngine:
             pk = self.tp3ops[li]
             ck(pick("qkv", hnorm)(pk["qkv"], cur, L.input_layernorm.weight, qp))
             if not linears_only:
-                ck(lib.qeft_rope_attn_decode(qp, qp + self.hs * 2, qp + (self.hs + self.kvs) * 2,
-                                             self.rope_row.data_ptr(), self.rope_row.data_ptr() + 64 * 4, 1,
-                                             self.kc[li].data_ptr(), self.vc[li].data_ptr(), self.pos.data_ptr(),
-                                             pk["att_pos"].data_ptr(), pk["x_o"].data_ptr(),
-                                             self.attn_ws.data_ptr() if self.attn_ws is not None else None,
-                                             self.attn_split, self.heads_l, self.kv_heads_l, s.max_seq, st))
+                self._attn(li, qp, qp + self.hs * 2, qp + (self.hs + self.kvs) * 2, pk["att_pos"], pk["x_o"], st)
             ck(pick("o", partial)(pk["o"], pk["x_o"].data_ptr(), cur, oth))
             if not linears_only:
                 self._all_reduce(oth)
@@ -972,20 +1033,7 @@ class DecodeEngine:
         """Capture one token into a hipGraph (after a warm-up launch on a side stream, as torch requires).  `split`:
         attention blocks per head baked into this graph (default: what the current position asks for)."""
         self.attn_split = split or self._split_for(self.host_pos)
-        side = torch.cuda.Stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        pos0, tok0 = self.pos.clone(), self.tok.clone()
-        with torch.cuda.stream(side):
-            self._launch_token(linears_only, only)
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        self.pos.copy_(pos0)
-        self.tok.copy_(tok0)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self._launch_token(linears_only, only)
-        self.pos.copy_(pos0)
-        self.tok.copy_(tok0)
+        graph = capture_graph(self.dev, lambda: self._launch_token(linears_only, only), 1, (self.pos, self.tok))
         if linears_only:
             return graph
         # a graph bakes in the attention split AND which token end runs (argmax, none, or a draw)
@@ -1063,34 +1111,14 @@ class DecodeEngine:
                 key = (sp, "sample", m) if self.sampling is not None else (sp, True, m)
                 g = self.graphs.get(key)
                 if g is None:
-                    g = self.graphs[key] = self._capture_multi(m, sp)
+                    self.attn_split = sp
+                    g = self.graphs[key] = capture_graph(self.dev, self._launch_token, m, (self.pos, self.tok))
                 g.replay()
                 self.host_pos += m
                 n_tokens -= m
             else:
                 self.step()
                 n_tokens -= 1
-
-    def _capture_multi(self, m, split):
-        self.attn_split = split
-        side = torch.cuda.Stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        pos0, tok0 = self.pos.clone(), self.tok.clone()
-        with torch.cuda.stream(side):
-            self._launch_token()
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        self.pos.copy_(pos0)
-        self.tok.copy_(tok0)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for _ in range(m):
-                self._launch_token()
-        # the capture itself executes nothing, but the warm-up launch above wrote one token's K/V at pos0 (rewritten by the
-        # real run) and advanced pos / tok: restore them
-        self.pos.copy_(pos0)
-        self.tok.copy_(tok0)
-        return graph
 
     # -- verify pass: m <= 8 tokens of this sequence in one launch sequence (assisted decoding, qeft_amd/assisted.py) ---------
     VERIFY_MAX = 8
@@ -1109,73 +1137,37 @@ class DecodeEngine:
         vb = getattr(self, "_vb", None)
         if vb is not None:
             return vb
-        import types
         s, dev, M = self.m.shape, self.dev, self.VERIFY_MAX
-        kvd = s.n_kv_heads * s.head_dim
-        f16 = dict(dtype=torch.float16, device=dev)
-        n_ssq = max(self.n_ssq_tb, self.n_ssq_lin)
-        ws = self.lib.qeft_attn_m_workspace_bytes(s.n_heads, 8, M)
-        vb = types.SimpleNamespace(
-            toks=torch.zeros(M, dtype=torch.long, device=dev),
-            h32=torch.zeros(M, s.hidden, dtype=torch.float32, device=dev),
-            xn=torch.zeros(M, s.hidden, **f16),
-            ssq=torch.zeros(M * n_ssq + 4, dtype=torch.float32, device=dev),
-            qkv=torch.zeros(M, s.hidden + 2 * kvd, **f16),
-            att=torch.zeros(M, s.hidden, **f16),
-            act=torch.zeros(M, s.inter, **f16),
-            hn=torch.zeros(M, s.hidden, **f16),
-            rope=torch.zeros(M, 128, dtype=torch.float32, device=dev),
-            ws=torch.zeros(max(ws, 16) // 4, dtype=torch.float32, device=dev),
-            out=torch.zeros(M, dtype=torch.long, device=dev),
-            n_acc=torch.zeros(1, dtype=torch.int32, device=dev),
-            work=torch.zeros(16, dtype=torch.int32, device=dev))       # qeft_verify_sample's draws and ticket (re-arms itself)
-        self._vb = vb
-        self.logits_m = torch.zeros(M, s.vocab, **f16)
+        vb = m_row_buffers(self, M, self.lib.qeft_attn_m_workspace_bytes(s.n_heads, 8, M))
+        vb.toks = torch.zeros(M, dtype=torch.long, device=dev)
+        vb.out = torch.zeros(M, dtype=torch.long, device=dev)
+        vb.n_acc = torch.zeros(1, dtype=torch.int32, device=dev)
+        vb.work = torch.zeros(16, dtype=torch.int32, device=dev)        # qeft_verify_sample's draws and ticket (re-arms itself)
+        self._vb, self.logits_m = vb, vb.logits
         return vb
 
     @torch.no_grad()
     def _launch_verify(self, m, split, greedy):
-        """m-row launch sequence: token begin (m rows) -> per layer q|k|v, multi-query attention, o_proj (+ residual, norm split),
-        gate|up (SiLU epilogue), down_proj (+ residual, next norm split) on m-row GEMVs -> final norm + head (m rows) -> verify
-        (greedy == "sample": the sampled verify end, every row drawn with the device record)."""
+        """m-row launch sequence: token begin (m rows) -> the layers (_v3_layers) on m-row GEMVs with the multi-query attention
+        between them -> final norm + head (m rows) -> verify (greedy == "sample": the sampled verify end, every row drawn with
+        the device record)."""
         s, lib, ck, vb = self.m.shape, self.lib, _lib.check, self._vb
         st = torch.cuda.current_stream(self.dev).cuda_stream
-        g, no, eps = s.group_size, s.n_out, s.rms_eps
-        layers = self.m.model.layers
         kvd = s.n_kv_heads * s.head_dim
         nq = s.hidden + 2 * kvd
-        xn, ssq, h32 = vb.xn.data_ptr(), vb.ssq.data_ptr(), vb.h32.data_ptr()
-
-        def lin(op, x, y, mode=0, residual=None, ssq_in=None, n_ssq=0, gamma_out=None):
-            return lib.qeft_decode_linear_m(x, op.qweight.data_ptr(), op.sz_packed.data_ptr(), op.oweight.data_ptr() if no else None,
-                                            None, y, op.outfeatures, op.infeatures, g, no, mode, residual, ssq_in, n_ssq, eps,
-                                            gamma_out, xn if gamma_out else None, ssq if gamma_out else None, m, st)
+        h32, qp, rope = vb.h32.data_ptr(), vb.qkv.data_ptr(), vb.rope.data_ptr()
         ck(lib.qeft_token_begin_norm_m(self.m.model.embed_tokens.weight.data_ptr(), vb.toks.data_ptr(), self.rope_tab.data_ptr(),
-                                       self.pos.data_ptr(), h32, vb.rope.data_ptr(), layers[0].input_layernorm.weight.data_ptr(),
-                                       xn, ssq, s.hidden, s.vocab, s.max_seq, m, st))
-        n_ssq = self.n_ssq_tb
-        qp = vb.qkv.data_ptr()
-        for li, L in enumerate(layers):
-            pk = self.v3ops[li]
-            ck(lin(pk["qkv"], xn, qp, ssq_in=ssq, n_ssq=n_ssq))
-            ck(lib.qeft_rope_attn_decode_m(qp, qp + s.hidden * 2, qp + (s.hidden + kvd) * 2, nq, vb.rope.data_ptr(),
-                                           vb.rope.data_ptr() + 64 * 4, 128, m, self.kc[li].data_ptr(), self.vc[li].data_ptr(),
-                                           self.pos.data_ptr(), self.att_pos[li].data_ptr() if self.att_pos[li] is not None else None,
+                                       self.pos.data_ptr(), h32, rope, self.m.model.layers[0].input_layernorm.weight.data_ptr(),
+                                       vb.xn.data_ptr(), vb.ssq.data_ptr(), s.hidden, s.vocab, s.max_seq, m, st))
+
+        def attn(li):
+            ck(lib.qeft_rope_attn_decode_m(qp, qp + s.hidden * 2, qp + (s.hidden + kvd) * 2, nq, rope, rope + 64 * 4, 128, m,
+                                           self.kc[li].data_ptr(), self.vc[li].data_ptr(), self.pos.data_ptr(),
+                                           self.att_pos[li].data_ptr() if self.att_pos[li] is not None else None,
                                            vb.att.data_ptr(), s.hidden, vb.ws.data_ptr(), split, s.n_heads, s.n_kv_heads, s.max_seq,
                                            m, st))
-            ck(lin(pk["o"], vb.att.data_ptr(), h32, residual=h32, gamma_out=L.post_attention_layernorm.weight.data_ptr()))
-            n_ssq = self.n_ssq_lin
-            ck(lin(pk["gu"], xn, vb.act.data_ptr(), mode=1, ssq_in=ssq, n_ssq=n_ssq))
-            nxt = layers[li + 1].input_layernorm.weight.data_ptr() if li + 1 < len(layers) else None
-            ck(lin(pk["d"], vb.act.data_ptr(), h32, residual=h32, gamma_out=nxt))
-        w = self.m.lm_head.weight
-        if s.hidden in (512, 1024, 2048, 4096, 5120, 8192) and w.dtype == torch.float16 and w.is_contiguous() \
-                and os.environ.get("QEFT_LM_HEAD_TORCH") != "1":
-            ck(lib.qeft_lm_head_f16_m(h32, self.m.model.norm.weight.data_ptr(), w.data_ptr(), self.logits_m.data_ptr(), s.hidden,
-                                      s.vocab, eps, m, st))
-        else:           # head widths the fused kernel does not take: as _token_tail
-            ck(lib.qeft_rmsnorm_f32(h32, self.m.model.norm.weight.data_ptr(), vb.hn.data_ptr(), m, s.hidden, eps, st))
-            torch.matmul(vb.hn[:m], w.t(), out=self.logits_m[:m])
+        self._v3_layers(vb, self._lin_m(vb, m, st), attn)
+        self._head(h32, vb.hn, self.logits_m, m, st)
         if greedy == "sample":
             ck(lib.qeft_verify_sample(self.logits_m.data_ptr(), vb.toks.data_ptr(), m, s.vocab, self.sample_rec.data_ptr(),
                                       vb.work.data_ptr(), vb.out.data_ptr(), vb.n_acc.data_ptr(), self.tok.data_ptr(),
@@ -1183,24 +1175,6 @@ class DecodeEngine:
             return
         ck(lib.qeft_verify_greedy(self.logits_m.data_ptr(), vb.toks.data_ptr(), m, s.vocab, 1 if greedy else 0, vb.out.data_ptr(),
                                   vb.n_acc.data_ptr(), self.tok.data_ptr(), self.pos.data_ptr(), st))
-
-    def _capture_verify(self, m, split, greedy):
-        side = torch.cuda.Stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        pos0, tok0 = self.pos.clone(), self.tok.clone()
-        with torch.cuda.stream(side):
-            self._launch_verify(m, split, greedy)
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        self.pos.copy_(pos0)
-        self.tok.copy_(tok0)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self._launch_verify(m, split, greedy)
-        # (the warm-up wrote K/V rows at pos0 .. pos0 + m - 1, rewritten by the real pass, and advanced pos / tok: restore them)
-        self.pos.copy_(pos0)
-        self.tok.copy_(tok0)
-        return graph
 
     @torch.no_grad()
     def verify(self, tokens):
@@ -1242,7 +1216,8 @@ class DecodeEngine:
             key = ("verify", m, sp, greedy)
             g = self.graphs.get(key)
             if g is None:
-                g = self.graphs[key] = self._capture_verify(m, sp, greedy)
+                # (the sampled end's vb.work / out / n_acc stay as the warm-up leaves them: the ticket re-arms itself)
+                g = self.graphs[key] = capture_graph(self.dev, lambda: self._launch_verify(m, sp, greedy), 1, (self.pos, self.tok))
             g.replay()
         else:
             self._launch_verify(m, sp, greedy)

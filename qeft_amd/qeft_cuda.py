@@ -420,6 +420,13 @@ def layernorm_forward_cuda(x, gamma, out, eps):
                                            _stream(x)))
 
 
+def rope_cos_sin(theta, half, rows):
+    """The neox rotary tables of `rows` positions: (cos, sin), fp32 [rows][half] on the CPU (angles formed in fp64)."""
+    inv = 1.0 / (float(theta) ** (torch.arange(0, half, dtype=torch.float64) / half))
+    ang = torch.arange(rows, dtype=torch.float64)[:, None] * inv[None, :]
+    return ang.cos().float(), ang.sin().float()
+
+
 _ROPE_TABLES = {}   # (device, rotary_dim, base, rows) -> fp32 [2][rows][64]: cos table, sin table
 
 
@@ -431,9 +438,7 @@ def _rope_table(device, dim, base, rows):
         if dim == 0:       # no rotary: identity rotation
             tab = torch.stack([torch.ones(rows, half), torch.zeros(rows, half)])
         else:
-            inv = 1.0 / (float(base) ** (torch.arange(0, half, dtype=torch.float64) / half))
-            ang = torch.arange(rows, dtype=torch.float64)[:, None] * inv[None, :]
-            tab = torch.stack([ang.cos(), ang.sin()])
+            tab = torch.stack(rope_cos_sin(base, half, rows))
         tab = _ROPE_TABLES[key] = tab.float().contiguous().to(device)
     return tab
 

@@ -6,8 +6,10 @@
 //   rope_attn_b          rotary + KV append + attention of row r over keys [0, pos[slot[r]]] of its own slot's cache
 //   token_end_b          per-row argmax -> tok[r], out[r][k]; pos[slot] += 1; EOS / length stop on the device
 // KV caches: [n_slots][n_kv][max_seq][128] fp16 per layer (one slot = the layout of DecodeEngine.kc[li]).
+// The token-begin body and the block argmax are shared with the verify pass (decode_verify.hip): decode_rows.h.
 #include "qeft_common.h"
 #include "decode_attn.h"      // wave_max, st_agent / ld_agent, kAttnRec
+#include "decode_rows.h"      // token_begin_norm_row, block_argmax_1024
 
 namespace qeft {
 
@@ -20,41 +22,18 @@ __device__ __forceinline__ int row_slot(const int* __restrict__ slot_tab, int ro
     return s >= 0 && s < n_slots ? s : -1;
 }
 
-// ---- token begin, one row per sequence.  grid = (blocks of the one-row launch, m), block 256; row = blockIdx.y.  The arithmetic
-// of token_begin_norm_m_kernel; only the rotary row's position differs (pos[slot[row]] instead of *pos + row).
+// ---- token begin, one row per sequence.  grid = (blocks of the one-row launch, m), block 256; row = blockIdx.y.  The rotary row is
+// that of pos[slot[row]].
 __global__ __launch_bounds__(256) void token_begin_norm_b_kernel(const f16* __restrict__ embed, const long long* __restrict__ toks,
                                                                  const float* __restrict__ rope_tab, const int* __restrict__ slot_tab,
                                                                  const int* __restrict__ pos_tab, float* __restrict__ h,
                                                                  float* __restrict__ rope_rows, const f16* __restrict__ gamma,
                                                                  f16* __restrict__ hnorm, float* __restrict__ ssq_out, int hidden,
                                                                  int vocab, int max_seq, int n_slots) {
-    __shared__ float sm[4];
-    const int row = blockIdx.y, nb = gridDim.x;
-    const long long tk = min(max(toks[row], 0ll), (long long)vocab - 1);
-    const int i = (blockIdx.x * 256 + threadIdx.x) * 8;
-    float* const hr = h + (size_t)row * hidden;
-    float ss = 0.f;
-    if (i < hidden) {
-        const h8 v = *(const h8*)(embed + (size_t)tk * hidden + i), g = *(const h8*)(gamma + i);
-        h8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            ss += (float)v[j] * (float)v[j];
-            o[j] = mul_f32_to_f16((float)v[j], (float)g[j]);
-            hr[i + j] = (float)v[j];
-        }
-        *(h8*)(hnorm + (size_t)row * hidden + i) = o;
-    }
-    ss = wave_sum(ss);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) sm[wave] = ss;
-    __syncthreads();
-    if (threadIdx.x == 0) ssq_out[(size_t)row * nb + blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
-    if (blockIdx.x == 0 && threadIdx.x < 128) {
+    token_begin_norm_row(embed, toks, rope_tab, h, rope_rows, gamma, hnorm, ssq_out, hidden, vocab, max_seq, [&](int row) {
         const int s = row_slot(slot_tab, row, n_slots);
-        const int p = min(max(s >= 0 ? pos_tab[s] : 0, 0), max_seq - 1);
-        rope_rows[(size_t)row * 128 + threadIdx.x] = rope_tab[(size_t)p * 128 + threadIdx.x];
-    }
+        return s >= 0 ? pos_tab[s] : 0;
+    });
 }
 
 hipError_t token_begin_norm_b_launch(const void* embed, const void* toks, const void* rope_tab, const int* slot_tab, const int* pos_tab,
@@ -371,36 +350,10 @@ __global__ __launch_bounds__(1024) void token_end_b_kernel(const f16* __restrict
     const int t = threadIdx.x, row = blockIdx.x;
     const int s = row_slot(slot_tab, row, n_slots);
     const bool active = s >= 0 && done[s] == 0;       // uniform over the block
-    float best = -INFINITY;
-    int idx = 0x7fffffff;
-    if (active) {
-        const f16* lg = logits + (size_t)row * vocab;
-        for (int i = t * 8; i < vocab; i += 1024 * 8) {
-            if (i + 8 <= vocab && (vocab & 7) == 0) {
-                const h8 v = *(const h8*)(lg + i);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if ((float)v[j] > best) { best = (float)v[j]; idx = i + j; }
-            } else {
-                for (int j = i; j < min(i + 8, vocab); ++j)
-                    if ((float)lg[j] > best) { best = (float)lg[j]; idx = j; }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o);
-            const int oi = __shfl_xor(idx, o);
-            if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
-        }
-        if ((t & 63) == 0) { bv[t >> 6] = best; bi[t >> 6] = idx; }
-        __syncthreads();
-    }
+    const int a = active ? block_argmax_1024(logits + (size_t)row * vocab, vocab, bv, bi) : 0;
     if (t != 0) return;
     const int k = ctr[0];
     if (active) {
-        for (int w = 1; w < 16; ++w)
-            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-        const int a = idx == 0x7fffffff ? 0 : idx;
         tok[row] = a;
         if (k >= 0 && k < out_cap) out[(size_t)row * out_cap + k] = a;
         const int np = pos_tab[s] + 1;

@@ -1,0 +1,78 @@
+// Device code that the m-row launches of the verify pass (decode_verify.hip) and of batched decoding (decode_batch.hip) share.
+//   token_begin_norm_row   the body of token_begin_norm_m / token_begin_norm_b (they differ in the rotary row's position)
+//   block_argmax_1024      the argmax of verify_greedy / token_end_b
+// The two attention kernels (rope_attn_m / rope_attn_b) are the same algorithm too, but stay written out in their files: moved
+// into shared device functions their R = 32 instantiation compiles to other code (profiles/attn_rows_refactor.log).
+#pragma once
+#include "qeft_common.h"
+
+namespace qeft {
+
+// ---- token begin of one row (grid = (pieces of 2048 elements, rows), block 256): embedding of toks[row] -> h32 row, the first
+// norm's producer form, the piece's sum of squares; block 0 copies the rotary row of position row_pos() (clamped to the table).
+template <class RowPos>
+__device__ __forceinline__ void token_begin_norm_row(const f16* __restrict__ embed, const long long* __restrict__ toks,
+                                                     const float* __restrict__ rope_tab, float* __restrict__ h,
+                                                     float* __restrict__ rope_rows, const f16* __restrict__ gamma,
+                                                     f16* __restrict__ hnorm, float* __restrict__ ssq_out, int hidden, int vocab,
+                                                     int max_seq, RowPos row_pos) {
+    __shared__ float sm[4];
+    const int row = blockIdx.y, nb = gridDim.x;
+    const long long tk = min(max(toks[row], 0ll), (long long)vocab - 1);
+    const int i = (blockIdx.x * 256 + threadIdx.x) * 8;
+    float* const hr = h + (size_t)row * hidden;
+    float ss = 0.f;
+    if (i < hidden) {
+        const h8 v = *(const h8*)(embed + (size_t)tk * hidden + i), g = *(const h8*)(gamma + i);
+        h8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            ss += (float)v[j] * (float)v[j];
+            o[j] = mul_f32_to_f16((float)v[j], (float)g[j]);
+            hr[i + j] = (float)v[j];
+        }
+        *(h8*)(hnorm + (size_t)row * hidden + i) = o;
+    }
+    ss = wave_sum(ss);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) sm[wave] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) ssq_out[(size_t)row * nb + blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
+    if (blockIdx.x == 0 && threadIdx.x < 128) {
+        const int p = min(max(row_pos(row), 0), max_seq - 1);
+        rope_rows[(size_t)row * 128 + threadIdx.x] = rope_tab[(size_t)p * 128 + threadIdx.x];
+    }
+}
+
+// ---- argmax of lg[0 .. vocab) by a block of 1024: the lowest index among equal maxima (0 when nothing compares greater than
+// -inf), as token_end.  bv / bi: [16] LDS.  Thread 0 holds the result; the caller owns the barrier before bv / bi are reused.
+__device__ __forceinline__ int block_argmax_1024(const f16* lg, int vocab, float* bv, int* bi) {
+    const int t = threadIdx.x;
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int i = t * 8; i < vocab; i += 1024 * 8) {
+        if (i + 8 <= vocab && (vocab & 7) == 0) {
+            const h8 v = *(const h8*)(lg + i);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if ((float)v[j] > best) { best = (float)v[j]; idx = i + j; }
+        } else {
+            for (int j = i; j < min(i + 8, vocab); ++j)
+                if ((float)lg[j] > best) { best = (float)lg[j]; idx = j; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o);
+        const int oi = __shfl_xor(idx, o);
+        if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
+    }
+    if ((t & 63) == 0) { bv[t >> 6] = best; bi[t >> 6] = idx; }
+    __syncthreads();
+    if (t == 0)
+        for (int w = 1; w < 16; ++w)
+            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
+    return idx == 0x7fffffff ? 0 : idx;
+}
+
+}  // namespace qeft

@@ -5,9 +5,11 @@
 //   lm_head_m            final RMSNorm + fp16 head for m rows: the head streams once
 //   verify_greedy        per-row argmax, longest accepted prefix, next token and position on the device
 // Every kernel follows the one-row kernel it extends (decode_aux.hip, decode_attn.h) in its arithmetic, so that a row of an
-// m-row launch reproduces the one-row launch where the summation order allows it.
+// m-row launch reproduces the one-row launch where the summation order allows it.  The token-begin body and the block argmax
+// are shared with the launches of batched decoding (decode_batch.hip): decode_rows.h.
 #include "qeft_common.h"
 #include "decode_attn.h"      // wave_max, st_agent / ld_agent, kAttnRec
+#include "decode_rows.h"      // token_begin_norm_row, block_argmax_1024
 
 namespace qeft {
 
@@ -20,32 +22,8 @@ __global__ __launch_bounds__(256) void token_begin_norm_m_kernel(const f16* __re
                                                                  float* __restrict__ h, float* __restrict__ rope_rows,
                                                                  const f16* __restrict__ gamma, f16* __restrict__ hnorm,
                                                                  float* __restrict__ ssq_out, int hidden, int vocab, int max_seq) {
-    __shared__ float sm[4];
-    const int row = blockIdx.y, nb = gridDim.x;
-    const long long tk = min(max(toks[row], 0ll), (long long)vocab - 1);
-    const int i = (blockIdx.x * 256 + threadIdx.x) * 8;
-    float* const hr = h + (size_t)row * hidden;
-    float ss = 0.f;
-    if (i < hidden) {
-        const h8 v = *(const h8*)(embed + (size_t)tk * hidden + i), g = *(const h8*)(gamma + i);
-        h8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            ss += (float)v[j] * (float)v[j];
-            o[j] = mul_f32_to_f16((float)v[j], (float)g[j]);
-            hr[i + j] = (float)v[j];
-        }
-        *(h8*)(hnorm + (size_t)row * hidden + i) = o;
-    }
-    ss = wave_sum(ss);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) sm[wave] = ss;
-    __syncthreads();
-    if (threadIdx.x == 0) ssq_out[(size_t)row * nb + blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
-    if (blockIdx.x == 0 && threadIdx.x < 128) {
-        const int p = min(max(*pos + row, 0), max_seq - 1);
-        rope_rows[(size_t)row * 128 + threadIdx.x] = rope_tab[(size_t)p * 128 + threadIdx.x];
-    }
+    token_begin_norm_row(embed, toks, rope_tab, h, rope_rows, gamma, hnorm, ssq_out, hidden, vocab, max_seq,
+                         [&](int row) { return *pos + row; });
 }
 
 hipError_t token_begin_norm_m_launch(const void* embed, const void* toks, const void* rope_tab, const int* pos, void* h,
@@ -452,33 +430,8 @@ __global__ __launch_bounds__(1024) void verify_greedy_kernel(const f16* __restri
         return;
     }
     for (int row = 0; row < m; ++row) {
-        const f16* lg = logits + (size_t)row * vocab;
-        float best = -INFINITY;
-        int idx = 0x7fffffff;
-        for (int i = t * 8; i < vocab; i += 1024 * 8) {
-            if (i + 8 <= vocab && (vocab & 7) == 0) {
-                const h8 v = *(const h8*)(lg + i);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if ((float)v[j] > best) { best = (float)v[j]; idx = i + j; }
-            } else {
-                for (int j = i; j < min(i + 8, vocab); ++j)
-                    if ((float)lg[j] > best) { best = (float)lg[j]; idx = j; }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o);
-            const int oi = __shfl_xor(idx, o);
-            if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
-        }
-        if ((t & 63) == 0) { bv[t >> 6] = best; bi[t >> 6] = idx; }
-        __syncthreads();
-        if (t == 0) {
-            for (int w = 1; w < 16; ++w)
-                if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-            am[row] = idx == 0x7fffffff ? 0 : idx;
-        }
+        const int a = block_argmax_1024(logits + (size_t)row * vocab, vocab, bv, bi);
+        if (t == 0) am[row] = a;
         __syncthreads();
     }
     if (t == 0) {

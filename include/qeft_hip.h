@@ -399,6 +399,36 @@ int qeft_rope_attn_decode_batch(const void* q, const void* k, const void* v, int
 int qeft_token_end_batch(const void* logits, const int* slots, void* tokens, int* pos, const int* limit, const int* eos, int* done,
                          void* out, int* counter, int vocab, int out_cap, int n_slots, int m, qeft_stream_t stream);
 
+/* FP8 KV cache (csrc/decode_attn_kv8.hip; DecodeEngine / BatchDecodeEngine with kv_dtype="fp8").  Per layer and slot:
+ *   K codes, V codes   uint8 [n_kv_heads][max_seq][128], OCP e4m3fn (not fnuz)
+ *   K scales, V scales fp32  [n_kv_heads][max_seq], one per (kv head, position) row
+ * with [n_slots] in front of each for the batch entry.  132 bytes per row where the fp16 cache has 256.
+ * THE RECIPE for a row x[128] -- the fp16 values an fp16 cache would hold: K after rotary and rounding to fp16, V the fp16
+ * projection -- in fp32 arithmetic:
+ *   1. amax = max |x_i|.
+ *   2. amax == 0: scale = 0 and every code is 0.
+ *   3. otherwise inv = 448.0f / amax and scale = amax / 448.0f (correctly rounded fp32 divides; the build uses no fast-math), and
+ *      code_i = e4m3fn, round to nearest even, of clamp(x_i * inv, -448, 448).
+ * The value of an element is float(code) * scale.  Both entries below run this recipe through one device function.
+ * qeft_rope_attn_decode_kv8: qeft_rope_attn_decode_batch over such a cache, same arguments and rules (row r in slot slots[r] at
+ *   p = pos[slots[r]]; a row with a bad slot, done != 0 or p outside [0, max_seq) writes nothing to the cache and zeros to its
+ *   output; n_split 1 / 2 / 4 / 8 with a zeroed workspace of qeft_attn_kv8_workspace_bytes(n_heads, n_split, m) bytes, whose
+ *   counters re-arm themselves and which, sized for 8, serves every split in any order; head_dim 128, max_seq % 16 == 0,
+ *   16 <= max_seq <= 32768).  The launch quantises the new K / V row, appends codes and scale at p, and attends over rows [0, p]
+ *   AS THE CACHE HOLDS THEM, its own row included (dequantised), so a token contributes the same whether prefill or a decode step
+ *   wrote it.  m = 1, n_slots = 1, slots = {0} serves a single sequence.  Codes 16-byte aligned, scales 4-byte aligned.
+ * qeft_kv8_store_rows: quantise n_rows already rotated K rows and V rows (fp16 [n_rows][>= n_kv_heads * 128], rows row_stride
+ *   elements apart: views of a fused q|k|v GEMM output) into ONE cache (no slot dimension) at positions p0 .. p0 + n_rows - 1;
+ *   p0 >= 0, n_rows >= 1, p0 + n_rows <= max_seq (QEFT_ERR_SHAPE otherwise). */
+int qeft_attn_kv8_workspace_bytes(int n_heads, int n_split, int m);   /* 0 for n_split == 1 or bad arguments */
+int qeft_rope_attn_decode_kv8(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
+                              int tab_stride, int tab_rows, void* k_codes, void* v_codes, void* k_scales, void* v_scales,
+                              const int* slots, const int* pos, const int* done, const int* out_pos, void* out, int out_stride,
+                              void* workspace, int n_split, int n_slots, int n_heads, int n_kv_heads, int max_seq, int m,
+                              qeft_stream_t stream);
+int qeft_kv8_store_rows(const void* k_rows, const void* v_rows, int row_stride, void* k_codes, void* v_codes, void* k_scales,
+                        void* v_scales, int n_kv_heads, int max_seq, int p0, int n_rows, qeft_stream_t stream);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py).  A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

@@ -80,6 +80,9 @@ SIGNATURES = {
     "qeft_token_begin_norm_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "qeft_attn_batch_workspace_bytes": [_i, _i, _i],
     "qeft_rope_attn_decode_batch": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
+    "qeft_attn_kv8_workspace_bytes": [_i, _i, _i],
+    "qeft_rope_attn_decode_kv8": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
+    "qeft_kv8_store_rows": [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "qeft_token_end_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "qeft_sample": [_p, _i, _i, _p, _p, _p, _p],
     "qeft_token_end_sample": [_p, _p, _p, _i, _p, _p],

@@ -3,9 +3,9 @@
 
 `BatchDecodeEngine` is built on a single-GPU `DecodeEngine` (4-bit weights, v3 engine) and shares its fused operands, rotary
 table and library handle, so the weights are not copied again.  It owns per-slot KV caches ([n_slots][n_kv][max_seq][128] per
-layer), the per-slot position and stop state on the device, its buffers and its graphs; it never touches the engine's own
-caches, position or graphs.  One pass launches, for the m active rows (row r serves slot rows[r]): the batched token begin, per
-layer the verify pass's m-row linears with the batched attention between them (each row in its own slot at its own position),
+layer, fp16 or -- on an engine built with kv_dtype="fp8" -- e4m3 codes with a scale per row), the per-slot
+position and stop state on the device, its buffers and its graphs; it never touches the engine's own caches, position or
+graphs.  One pass launches, for the m active rows (row r serves slot rows[r]): the batched token begin, per layer the verify pass's m-row linears with the batched attention between them (each row in its own slot at its own position),
 the m-row head and the batched token end, which stops a row on the device when it emits its EOS token or reaches its length
 limit.  A stopped row keeps its position, cache and token; later passes of the same graph leave it alone.
 
@@ -28,8 +28,9 @@ REASONS = {1: "eos", 2: "length"}       # the device's done codes
 
 
 def batch_unsupported(engine):
-    """Why `engine` cannot serve batched decoding (the verify pass's conditions: one GPU, 4-bit weights, v3 engine), or None."""
-    why = engine._verify_unsupported()
+    """Why `engine` cannot serve batched decoding (the m-row pass's conditions, which the verify pass shares: one GPU, 4-bit
+    weights, v3 engine; the KV cache type is the verify pass's own condition), or None."""
+    why = (getattr(engine, "_m_row_unsupported", None) or engine._verify_unsupported)()
     return why.replace("the verify pass", "batched decoding") if why else None
 
 
@@ -100,8 +101,11 @@ class _SlotView:
     P = 1
 
     def __init__(self, batch, slot):
+        self.lib = batch.lib
         self.kc = [k[slot] for k in batch.kc]
         self.vc = [v[slot] for v in batch.vc]
+        self.ks = [x[slot] for x in batch.ks] if batch.ks is not None else None
+        self.vs = [x[slot] for x in batch.vs] if batch.vs is not None else None
         self.max_seq = batch.model.shape.max_seq
         self.position = None
 
@@ -109,6 +113,10 @@ class _SlotView:
         if not 0 <= int(t) <= self.max_seq:
             raise ValueError(f"position {t} outside the KV cache (max_seq = {self.max_seq})")
         self.position = int(t)
+
+    def store_kv(self, li, k, v, T):
+        llama.store_kv_rows(self.lib, k, v, self.kc[li], self.vc[li], self.ks[li] if self.ks is not None else None,
+                            self.vs[li] if self.vs is not None else None, T)
 
 
 class BatchDecodeEngine:
@@ -130,9 +138,12 @@ class BatchDecodeEngine:
         s, dev = self.model.shape, engine.dev
         M = self.n_slots = int(max_batch)
         self.table = SlotTable(M)
-        f16, i32 = dict(dtype=torch.float16, device=dev), dict(dtype=torch.int32, device=dev)
-        self.kc = [torch.zeros(M, s.n_kv_heads, s.max_seq, s.head_dim, **f16) for _ in range(s.n_layers)]
-        self.vc = [torch.zeros(M, s.n_kv_heads, s.max_seq, s.head_dim, **f16) for _ in range(s.n_layers)]
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.kv_dtype = engine.kv_dtype                         # the cache type of the engine it is built on
+        fp8 = self.kv_dtype == "fp8"
+        caches = [llama.kv_cache_arrays(self.kv_dtype, (M,), s.n_kv_heads, s.max_seq, dev) for _ in range(s.n_layers)]
+        self.kc, self.vc = [c[0] for c in caches], [c[1] for c in caches]
+        self.ks, self.vs = ([c[2] for c in caches], [c[3] for c in caches]) if fp8 else (None, None)
         # per slot: pos | limit | eos | done, then the sampling records [M][8] (sampling.py); one upload per admission
         self._slot_words = torch.zeros(4 * M + 8 * M, **i32)
         self.state = self._slot_words[:4 * M].view(4, M)
@@ -144,7 +155,8 @@ class BatchDecodeEngine:
         self.tok_slot = torch.zeros(M, dtype=torch.long, device=dev)    # per slot, between runs (rows change with the table)
         self.out = torch.full((M, self.OUT_CAP), -1, dtype=torch.long, device=dev)
         self.ctr = torch.zeros(2, **i32)                        # token end's step counter and arrival count
-        self.b = llama.m_row_buffers(engine, M, self.lib.qeft_attn_batch_workspace_bytes(s.n_heads, 8, M))
+        ws_bytes = self.lib.qeft_attn_kv8_workspace_bytes if fp8 else self.lib.qeft_attn_batch_workspace_bytes
+        self.b = llama.m_row_buffers(engine, M, ws_bytes(s.n_heads, 8, M))
         self.logits_m = self.b.logits
         self.graphs = {}
         self.rows = []                                          # the row table of the last pass
@@ -223,9 +235,15 @@ class BatchDecodeEngine:
                                            b.xn.data_ptr(), b.ssq.data_ptr(), s.hidden, s.vocab, s.max_seq, self.n_slots, m, st))
 
         def attn(li):
+            opos = eng.att_pos[li].data_ptr() if eng.att_pos[li] is not None else None
+            if self.ks is not None:
+                ck(lib.qeft_rope_attn_decode_kv8(qp, qp + s.hidden * 2, qp + (s.hidden + kvd) * 2, nq, rope, rope + 64 * 4, 128, m,
+                                                 self.kc[li].data_ptr(), self.vc[li].data_ptr(), self.ks[li].data_ptr(),
+                                                 self.vs[li].data_ptr(), slots, pos, done, opos, b.att.data_ptr(), s.hidden,
+                                                 b.ws.data_ptr(), split, self.n_slots, s.n_heads, s.n_kv_heads, s.max_seq, m, st))
+                return
             ck(lib.qeft_rope_attn_decode_batch(qp, qp + s.hidden * 2, qp + (s.hidden + kvd) * 2, nq, rope, rope + 64 * 4, 128, m,
-                                               self.kc[li].data_ptr(), self.vc[li].data_ptr(), slots, pos, done,
-                                               eng.att_pos[li].data_ptr() if eng.att_pos[li] is not None else None,
+                                               self.kc[li].data_ptr(), self.vc[li].data_ptr(), slots, pos, done, opos,
                                                b.att.data_ptr(), s.hidden, b.ws.data_ptr(), split, self.n_slots, s.n_heads,
                                                s.n_kv_heads, s.max_seq, m, st))
         eng._v3_layers(b, eng._lin_m(b, m, st), attn)

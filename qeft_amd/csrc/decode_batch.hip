@@ -9,18 +9,12 @@
 // The token-begin body and the block argmax are shared with the verify pass (decode_verify.hip): decode_rows.h.
 #include "qeft_common.h"
 #include "decode_attn.h"      // wave_max, st_agent / ld_agent, kAttnRec
-#include "decode_rows.h"      // token_begin_norm_row, block_argmax_1024
+#include "decode_rows.h"      // token_begin_norm_row, block_argmax_1024, row_slot, attn_b_ctr_floats
 
 namespace qeft {
 
 typedef float fx2 __attribute__((ext_vector_type(2)));
 int token_begin_norm_blocks(int hidden);      // decode_aux.hip
-
-// slot of row `row`, or -1 for a slot outside [0, n_slots) (such a row is left alone)
-__device__ __forceinline__ int row_slot(const int* __restrict__ slot_tab, int row, int n_slots) {
-    const int s = slot_tab[row];
-    return s >= 0 && s < n_slots ? s : -1;
-}
 
 // ---- token begin, one row per sequence.  grid = (blocks of the one-row launch, m), block 256; row = blockIdx.y.  The rotary row is
 // that of pos[slot[row]].
@@ -56,8 +50,6 @@ hipError_t token_begin_norm_b_launch(const void* embed, const void* toks, const 
 // of the records, at an offset that does not depend on (m, S)).
 // A row whose slot is outside [0, n_slots), is done (done[slot] != 0), or whose p is outside [0, max_seq) writes nothing to the
 // cache and zeros to its output.
-__host__ __device__ constexpr size_t attn_b_ctr_floats(int n_heads) { return ((size_t)8 * n_heads + 15) / 16 * 16; }
-
 template <int R>
 __global__ __launch_bounds__(256) void rope_attn_b_kernel(const int* __restrict__ slot_tab, const int* __restrict__ pos_tab,
                                                           const int* __restrict__ done, const int* __restrict__ out_pos,

@@ -1,12 +1,23 @@
 // Device code that the m-row launches of the verify pass (decode_verify.hip) and of batched decoding (decode_batch.hip) share.
 //   token_begin_norm_row   the body of token_begin_norm_m / token_begin_norm_b (they differ in the rotary row's position)
 //   block_argmax_1024      the argmax of verify_greedy / token_end_b
+//   row_slot, attn_b_ctr_floats   the slot table and the workspace layout of the batched attention kernels (fp16 cache:
+//                          decode_batch.hip; e4m3 cache: decode_attn_kv8.hip)
 // The two attention kernels (rope_attn_m / rope_attn_b) are the same algorithm too, but stay written out in their files: moved
 // into shared device functions their R = 32 instantiation compiles to other code (profiles/attn_rows_refactor.log).
 #pragma once
 #include "qeft_common.h"
 
 namespace qeft {
+
+// slot of row `row`, or -1 for a slot outside [0, n_slots) (such a row is left alone)
+__device__ __forceinline__ int row_slot(const int* __restrict__ slot_tab, int row, int n_slots) {
+    const int s = slot_tab[row];
+    return s >= 0 && s < n_slots ? s : -1;
+}
+
+// floats in front of the split records of a batched attention workspace: the arrival counters, one per (row, kv head, chunk)
+__host__ __device__ constexpr size_t attn_b_ctr_floats(int n_heads) { return ((size_t)8 * n_heads + 15) / 16 * 16; }
 
 // ---- token begin of one row (grid = (pieces of 2048 elements, rows), block 256): embedding of toks[row] -> h32 row, the first
 // norm's producer form, the piece's sum of squares; block 0 copies the rotary row of position row_pos() (clamped to the table).

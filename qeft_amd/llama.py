@@ -392,8 +392,7 @@ def prefill(model: "QuantLlama", tokens, engine=None):
             k = rope(at.k_proj(x).view(T, s.n_kv_heads, 128))
             v = at.v_proj(x).view(T, s.n_kv_heads, 128)
         if engine is not None:
-            engine.kc[li][:, :T] = k.transpose(0, 1)
-            engine.vc[li][:, :T] = v.transpose(0, 1)
+            engine.store_kv(li, k, v, T)
         rep = s.n_heads // s.n_kv_heads
         kk, vv = (k, v) if rep == 1 else (k.repeat_interleave(rep, 1), v.repeat_interleave(rep, 1))
         # 4-D operands: torch routes an unbatched [H, T, 128] call to its math path (1.6 ms per layer at T = 2048 on this
@@ -411,6 +410,33 @@ def prefill(model: "QuantLlama", tokens, engine=None):
         engine.set_position(T)
     _, hn = _add_rmsnorm(h, delta, model.model.norm.weight, s.rms_eps)
     return torch.matmul(hn, model.lm_head.weight.t())
+
+
+KV_DTYPES = ("fp16", "fp8")
+
+
+def kv_cache_arrays(kv_dtype, lead, n_kv, max_seq, dev):
+    """One layer's KV cache, `lead` = () for one sequence or (n_slots,): fp16 -> (K, V) [.., n_kv, max_seq, 128] fp16; fp8 -> (K
+    codes, V codes, K scales, V scales): uint8 [.., n_kv, max_seq, 128] e4m3 and fp32 [.., n_kv, max_seq] (include/qeft_hip.h)."""
+    if kv_dtype == "fp8":
+        codes = lambda: torch.zeros(*lead, n_kv, max_seq, 128, dtype=torch.uint8, device=dev)      # noqa: E731
+        scales = lambda: torch.zeros(*lead, n_kv, max_seq, dtype=torch.float32, device=dev)        # noqa: E731
+        return codes(), codes(), scales(), scales()
+    return tuple(torch.zeros(*lead, n_kv, max_seq, 128, dtype=torch.float16, device=dev) for _ in range(2))
+
+
+def store_kv_rows(lib, k, v, kc, vc, ks, vs, T):
+    """The prefill hand-over into ONE sequence's cache of one layer: rotated keys k and values v, [T, n_kv, 128] fp16 (views of
+    the fused q|k|v output are taken as they are), to positions [0, T).  ks is None: the fp16 cache, a slice assignment; else
+    the e4m3 cache through qeft_kv8_store_rows."""
+    if ks is None:
+        kc[:, :T] = k.transpose(0, 1)
+        vc[:, :T] = v.transpose(0, 1)
+        return
+    if not (k.stride(2) == 1 and k.stride(1) == 128 and v.stride() == k.stride()):
+        k, v = k.contiguous(), v.contiguous()
+    _lib.check(lib.qeft_kv8_store_rows(k.data_ptr(), v.data_ptr(), k.stride(0), kc.data_ptr(), vc.data_ptr(), ks.data_ptr(),
+                                       vs.data_ptr(), kc.shape[0], kc.shape[1], 0, T, torch.cuda.current_stream(k.device).cuda_stream))
 
 
 def _ptr_array(tensors):
@@ -476,14 +502,19 @@ class DecodeEngine:
     shapes) keep the round-1 scheme: every linear row-sharded, 4 all-gathers per layer.
     """
 
-    def __init__(self, model: QuantLlama, use_graph=True, tp_group=None, collective="rccl"):
-        """collective (tensor-parallel only): "rccl" = torch.distributed's all_reduce on the group (RCCL ring over xGMI; gloo in the
+    def __init__(self, model: QuantLlama, use_graph=True, tp_group=None, collective="rccl", kv_dtype="fp16"):
+        """kv_dtype: "fp16", or "fp8" -- the KV cache as e4m3 codes with one fp32 scale per (position, kv head) row (132 bytes
+        where fp16 has 256), on the single-GPU v3 engine; the verify pass does not run on it.
+        collective (tensor-parallel only): "rccl" = torch.distributed's all_reduce on the group (RCCL ring over xGMI; gloo in the
         one-GPU rehearsals), "oneshot" = the hand-written single-kernel all-reduce over IPC-mapped mailboxes (qeft_amd/oneshot.py,
         SURVEY.md section 8e: the decode payload is 16 KB, latency-bound); `self.collective` says which one runs -- a request for
         "oneshot" that cannot be served raises; "auto" tries it, checks it against the group's own all_reduce on a probe vector and
         falls back to "rccl" on every rank alike, leaving the reason in `self.collective_note`."""
         import torch.distributed as dist
         from .sharded import shard_quantlinear
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype
         self.m = model
         s = model.shape
         dev = model.lm_head.weight.device
@@ -531,8 +562,13 @@ class DecodeEngine:
         self.act_loc = torch.zeros(self.its, **f16) if tp else self.act
         self.hn = torch.zeros(1, s.hidden, **f16)
         self.logits = torch.zeros(1, s.vocab, **f16)
-        self.kc = [torch.zeros(self.kv_heads_l, s.max_seq, s.head_dim, **f16) for _ in range(s.n_layers)]
-        self.vc = [torch.zeros(self.kv_heads_l, s.max_seq, s.head_dim, **f16) for _ in range(s.n_layers)]
+        if kv_dtype == "fp8" and tp:
+            raise ValueError(self._kv8_needs("this engine is tensor-parallel"))
+        # per layer: fp16 K, V; or e4m3 K codes, V codes (kc, vc) with their fp32 row scales (ks, vs)
+        caches = [kv_cache_arrays(kv_dtype, (), self.kv_heads_l, s.max_seq, dev) for _ in range(s.n_layers)]
+        self.kc, self.vc = [c[0] for c in caches], [c[1] for c in caches]
+        self.ks, self.vs = ([c[2] for c in caches], [c[3] for c in caches]) if kv_dtype == "fp8" else (None, None)
+        self.slot0 = torch.zeros(1, dtype=torch.int32, device=dev)      # the one-slot table of the e4m3 attention entry
         # A head's context is dealt over attn_split blocks.  One CU pulls ~50 GB/s, so past a few hundred cached positions
         # one block per head is bound by its own fetch; below that the merge hand-off (~2.5 us) costs more than the split
         # saves.  Measured on Llama-2-7B: contexts 64..192 -> 653 / 641 / 638 tokens/s at split 1 / 2 / 4; 100..700 ->
@@ -543,7 +579,7 @@ class DecodeEngine:
         forced = os.environ.get("QEFT_ATTN_SPLIT")
         self.attn_split_forced = int(forced) if forced else None
         self.attn_split = self.attn_split_forced or 1
-        nws = self.lib.qeft_attn_workspace_bytes(self.heads_l, 8)
+        nws = max(self.lib.qeft_attn_workspace_bytes(self.heads_l, 8), self.lib.qeft_attn_kv8_workspace_bytes(self.heads_l, 8, 1))
         self.attn_ws = torch.zeros(nws // 4, dtype=torch.float32, device=dev)
         self.host_pos = 0          # host mirror of self.pos (chooses the split; any split is correct at any position)
         self.graphs = {}
@@ -560,6 +596,8 @@ class DecodeEngine:
         self.tp3 = (tp and self.bits == 4 and k_ok and s.n_out in (0, 128) and g_ == 128 and self.hs % 16 == 0
                     and self.kvs % 16 == 0 and self.its % 16 == 0 and self.its >= 128
                     and os.environ.get("QEFT_ENGINE_V2") != "1")
+        if kv_dtype == "fp8" and not self.v3:
+            raise ValueError(self._kv8_needs("QEFT_ENGINE_V2=1, or shapes / weights the v3 GEMV does not take"))
         self.collective = "rccl" if tp else None
         self.collective_note = None
         self.oneshot = None
@@ -712,6 +750,15 @@ class DecodeEngine:
         else:
             import torch.distributed as dist
             dist.all_gather_into_tensor(out, inp, group=self.tp_group)
+
+    @staticmethod
+    def _kv8_needs(why):
+        return f'kv_dtype="fp8" runs on the single-GPU v3 engine only ({why})'
+
+    def store_kv(self, li, k, v, T):
+        """llama.prefill's hand-over: layer li's rotated keys and values [T, n_kv, 128] fp16 -> cache positions [0, T)."""
+        fp8 = self.kv_dtype == "fp8"
+        store_kv_rows(self.lib, k, v, self.kc[li], self.vc[li], self.ks[li] if fp8 else None, self.vs[li] if fp8 else None, T)
 
     def _split_for(self, pos):
         if self.attn_split_forced:
@@ -888,6 +935,14 @@ class DecodeEngine:
         """Layer li's one-token attention: rotary on q / k (device pointers; this rank's heads), K/V append at pos, attention
         over the cache, the output written to `out` at the indices `att_pos` (None: natural order)."""
         rope = self.rope_row.data_ptr()
+        if self.kv_dtype == "fp8":       # the slot-table entry with one row in one slot: slot 0, its position self.pos
+            _lib.check(self.lib.qeft_rope_attn_decode_kv8(q, k, v, self.heads_l * 128, rope, rope + 64 * 4, 128, 1,
+                                                          self.kc[li].data_ptr(), self.vc[li].data_ptr(), self.ks[li].data_ptr(),
+                                                          self.vs[li].data_ptr(), self.slot0.data_ptr(), self.pos.data_ptr(), None,
+                                                          att_pos.data_ptr() if att_pos is not None else None, out.data_ptr(),
+                                                          self.heads_l * 128, self.attn_ws.data_ptr(), self.attn_split, 1,
+                                                          self.heads_l, self.kv_heads_l, self.m.shape.max_seq, 1, st))
+            return
         _lib.check(self.lib.qeft_rope_attn_decode(q, k, v, rope, rope + 64 * 4, 1, self.kc[li].data_ptr(), self.vc[li].data_ptr(),
                                                   self.pos.data_ptr(), att_pos.data_ptr() if att_pos is not None else None,
                                                   out.data_ptr(), self.attn_ws.data_ptr(), self.attn_split, self.heads_l,
@@ -1123,7 +1178,8 @@ class DecodeEngine:
     # -- verify pass: m <= 8 tokens of this sequence in one launch sequence (assisted decoding, qeft_amd/assisted.py) ---------
     VERIFY_MAX = 8
 
-    def _verify_unsupported(self):
+    def _m_row_unsupported(self):
+        """Why this engine cannot run an m-row pass (what the verify pass and batched decoding both need), or None."""
         if self.tp or self.tp3:
             return "the verify pass runs on the single-GPU engine only (this engine is tensor-parallel)"
         if self.bits != 4:
@@ -1131,6 +1187,13 @@ class DecodeEngine:
         if not self.v3:
             return "the verify pass runs on the v3 engine only (QEFT_ENGINE_V2=1, or shapes the v3 GEMV does not take)"
         return None
+
+    def _verify_unsupported(self):
+        why = self._m_row_unsupported()
+        if why is None and self.kv_dtype != "fp16":
+            # the m-row same-sequence attention reads an fp16 cache (decode_verify.hip); over e4m3 it is a follow-up
+            return f'the verify pass runs on an fp16 KV cache only (this engine has kv_dtype="{self.kv_dtype}")'
+        return why
 
     def _verify_bufs(self):
         """Static buffers of the verify pass, [VERIFY_MAX] rows each (allocated on first use)."""

@@ -429,6 +429,20 @@ int qeft_rope_attn_decode_kv8(const void* q, const void* k, const void* v, int q
 int qeft_kv8_store_rows(const void* k_rows, const void* v_rows, int row_stride, void* k_codes, void* v_codes, void* k_scales,
                         void* v_scales, int n_kv_heads, int max_seq, int p0, int n_rows, qeft_stream_t stream);
 
+/* The verify pass over an FP8 KV cache (csrc/decode_verify_kv8.hip; DecodeEngine with kv_dtype="fp8", kv8_verify=True).
+ * qeft_rope_attn_decode_m_kv8: qeft_rope_attn_decode_m over the cache above (ONE sequence: no slot dimension, no slot table), same
+ *   arguments and rules: m rows at positions *pos .. *pos + m - 1, query i over keys [0, *pos + i]; *pos < 0 or *pos + m > max_seq
+ *   touches nothing; q / k / v / out / rotary rows, out_pos and n_split as there, with a zeroed workspace of
+ *   qeft_attn_m_kv8_workspace_bytes(n_heads, n_split, m) bytes whose counters re-arm themselves and which, sized for (8, 8),
+ *   serves every (m, n_split) in any order.  The launch quantises the m new K / V rows by THE RECIPE, appends their codes and
+ *   scales, and attends over every row AS THE CACHE HOLDS IT, the m new rows included.  Codes 16-byte aligned, scales 4-byte
+ *   aligned; head_dim 128, max_seq % 16 == 0, 16 <= max_seq <= 32768. */
+int qeft_attn_m_kv8_workspace_bytes(int n_heads, int n_split, int m);   /* 0 for n_split == 1 or bad arguments */
+int qeft_rope_attn_decode_m_kv8(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
+                                int tab_stride, int tab_rows, void* k_codes, void* v_codes, void* k_scales, void* v_scales,
+                                const int* pos, const int* out_pos, void* out, int out_stride, void* workspace, int n_split,
+                                int n_heads, int n_kv_heads, int max_seq, int m, qeft_stream_t stream);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py).  A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

@@ -83,6 +83,8 @@ SIGNATURES = {
     "qeft_attn_kv8_workspace_bytes": [_i, _i, _i],
     "qeft_rope_attn_decode_kv8": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
     "qeft_kv8_store_rows": [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "qeft_attn_m_kv8_workspace_bytes": [_i, _i, _i],
+    "qeft_rope_attn_decode_m_kv8": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
     "qeft_token_end_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "qeft_sample": [_p, _i, _i, _p, _p, _p, _p],
     "qeft_token_end_sample": [_p, _p, _p, _i, _p, _p],

@@ -75,6 +75,11 @@ hipError_t rope_attn_kv8_launch(const void* q, const void* k, const void* v, int
                                 int tab_stride, int tab_rows, void* kc, void* vc, void* ks, void* vs, const int* slot_tab,
                                 const int* pos_tab, const int* done, const int* out_pos, void* out, int out_stride, void* ws,
                                 int n_slots, int n_heads, int n_kv, int max_seq, int S, int m, hipStream_t st);
+// decode_verify_kv8.hip
+hipError_t rope_attn_m_kv8_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
+                                  int tab_stride, int tab_rows, void* kc, void* vc, void* ks, void* vs, const int* pos,
+                                  const int* out_pos, void* out, int out_stride, void* ws, int n_heads, int n_kv, int max_seq, int S,
+                                  int m, hipStream_t st);
 hipError_t kv8_store_rows_launch(const void* k, const void* v, int row_stride, void* kc, void* vc, void* ks, void* vs, int n_kv,
                                  int max_seq, int p0, int T, hipStream_t st);
 extern unsigned long long* g_attn_dbg;
@@ -1072,6 +1077,32 @@ int qeft_kv8_store_rows(const void* k_rows, const void* v_rows, int row_stride, 
     if (((uintptr_t)k_rows & 1) || ((uintptr_t)v_rows & 1) || ((uintptr_t)k_scales & 3) || ((uintptr_t)v_scales & 3)) return QEFT_ERR_ALIGN;
     return finish(qeft::kv8_store_rows_launch(k_rows, v_rows, row_stride, k_codes, v_codes, k_scales, v_scales, n_kv_heads, max_seq, p0,
                                               n_rows, (hipStream_t)stream));
+}
+
+// ---- the verify pass over an e4m3 KV cache (decode_verify_kv8.hip)
+int qeft_attn_m_kv8_workspace_bytes(int n_heads, int n_split, int m) {
+    if (n_heads < 1 || n_heads > 4096 || n_split < 1 || n_split > 8 || !verify_m_ok(m)) return 0;
+    return (int)qeft::attn_m_workspace_bytes(n_heads, n_split, m);      // one layout of counters and records with the fp16 kernel
+}
+
+int qeft_rope_attn_decode_m_kv8(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
+                                int tab_stride, int tab_rows, void* k_codes, void* v_codes, void* k_scales, void* v_scales,
+                                const int* pos, const int* out_pos, void* out, int out_stride, void* workspace, int n_split,
+                                int n_heads, int n_kv_heads, int max_seq, int m, qeft_stream_t stream) {
+    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0 || n_heads > 4096 || max_seq < 16 || max_seq % 16 != 0 ||
+        max_seq > 32768)
+        return QEFT_ERR_SHAPE;
+    if (tab_rows != m && tab_rows < max_seq) return QEFT_ERR_SHAPE;
+    if (tab_stride < 64 || qkv_stride < 1 || out_stride < 1 || (!out_pos && out_stride < n_heads * 128)) return QEFT_ERR_SHAPE;
+    if (n_split != 1 && n_split != 2 && n_split != 4 && n_split != 8) return QEFT_ERR_SHAPE;
+    if (!q || !k || !v || !cos_tab || !sin_tab || !k_codes || !v_codes || !k_scales || !v_scales || !pos || !out) return QEFT_ERR_NULL;
+    if (n_split > 1 && !workspace) return QEFT_ERR_NULL;
+    if (!aligned16(k_codes) || !aligned16(v_codes) || !aligned16(workspace) || ((uintptr_t)k_scales & 3) || ((uintptr_t)v_scales & 3))
+        return QEFT_ERR_ALIGN;
+    return finish(qeft::rope_attn_m_kv8_launch(q, k, v, qkv_stride, cos_tab, sin_tab, tab_stride, tab_rows, k_codes, v_codes, k_scales,
+                                               v_scales, pos, out_pos, out, out_stride, workspace, n_heads, n_kv_heads, max_seq,
+                                               n_split, m, (hipStream_t)stream));
 }
 
 // ---- sampled token end (decode_sample.hip)

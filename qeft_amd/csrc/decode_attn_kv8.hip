@@ -1,5 +1,5 @@
 // Decode attention over an e4m3 KV cache (kv_dtype="fp8" of DecodeEngine / BatchDecodeEngine).
-//   kv8_quant_row        the cache recipe of include/qeft_hip.h for one row of 128, by one wave
+//   kv8_quant_row        the cache recipe of include/qeft_hip.h for one row of 128, by one wave (decode_kv8.h)
 //   kv8_store_rows       T already rotated K rows and V rows -> codes + scales at positions p0 .. p0 + T - 1 (the prefill hand-over)
 //   rope_attn_kv8        rotary + quantise + append + attention, one query token per row, each row in its own slot
 // Cache of one slot and layer: K codes, V codes uint8 [n_kv][max_seq][128]; K scales, V scales fp32 [n_kv][max_seq]; a batch
@@ -7,26 +7,9 @@
 #include "qeft_common.h"
 #include "decode_attn.h"      // wave_max, dpp_mov, st_agent / ld_agent, kAttnRec
 #include "decode_rows.h"      // row_slot, attn_b_ctr_floats
+#include "decode_kv8.h"       // kv8_quant_row, Kv8Run, fx2
 
 namespace qeft {
-
-typedef float fx2 __attribute__((ext_vector_type(2)));
-
-// ---- one row of 128 fp16 values by one wave (all 64 lanes active): the lane holds elements `lane` (a) and `lane + 64` (b) as
-// fp32; returns their codes and the row's scale.  amax == 0: scale 0, codes 0.
-__device__ __forceinline__ void kv8_quant_row(float a, float b, uint8_t& ca, uint8_t& cb, float& scale) {
-    const float amax = wave_max(fmaxf(fabsf(a), fabsf(b)));
-    scale = 0.f;
-    ca = cb = 0;
-    if (amax > 0.f) {
-        const float inv = 448.0f / amax;              // correctly rounded divides (no fast-math in this build)
-        scale = amax / 448.0f;
-        const float x = fminf(fmaxf(a * inv, -448.0f), 448.0f), y = fminf(fmaxf(b * inv, -448.0f), 448.0f);
-        const int pk = __builtin_amdgcn_cvt_pk_fp8_f32(x, y, 0, false);      // v_cvt_pk_fp8_f32: OCP e4m3fn, round to nearest even
-        ca = (uint8_t)(pk & 0xff);
-        cb = (uint8_t)((pk >> 8) & 0xff);
-    }
-}
 
 // ---- prefill hand-over.  grid = (n_kv, T), block 128: wave 0 the K row of (kv head, t), wave 1 the V row.
 __global__ __launch_bounds__(128) void kv8_store_rows_kernel(const f16* __restrict__ k, const f16* __restrict__ v, int row_stride,
@@ -66,12 +49,6 @@ hipError_t kv8_store_rows_launch(const void* k, const void* v, int row_stride, v
 // This launch's own row is quantised here (wave 0: K after rotary and fp16 rounding, wave 1: V), kept in LDS as codes + scale and
 // takes the place of cache row `pos` in the run that holds it, so the token is seen exactly as the cache holds it and no block
 // reads another block's stores.
-struct Kv8Run {
-    u32x4 k[2];
-    u32x2 v[4];
-    float ks, vs;
-};
-
 template <int R>
 __global__ __launch_bounds__(256) void rope_attn_kv8_kernel(const int* __restrict__ slot_tab, const int* __restrict__ pos_tab,
                                                             const int* __restrict__ done, const int* __restrict__ out_pos,

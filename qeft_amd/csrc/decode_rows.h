@@ -3,6 +3,7 @@
 //   block_argmax_1024      the argmax of verify_greedy / token_end_b
 //   row_slot, attn_b_ctr_floats   the slot table and the workspace layout of the batched attention kernels (fp16 cache:
 //                          decode_batch.hip; e4m3 cache: decode_attn_kv8.hip)
+//   attn_m_ctr_floats      the workspace layout of the m-row same-sequence attention kernels
 // The two attention kernels (rope_attn_m / rope_attn_b) are the same algorithm too, but stay written out in their files: moved
 // into shared device functions their R = 32 instantiation compiles to other code (profiles/attn_rows_refactor.log).
 #pragma once
@@ -18,6 +19,10 @@ __device__ __forceinline__ int row_slot(const int* __restrict__ slot_tab, int ro
 
 // floats in front of the split records of a batched attention workspace: the arrival counters, one per (row, kv head, chunk)
 __host__ __device__ constexpr size_t attn_b_ctr_floats(int n_heads) { return ((size_t)8 * n_heads + 15) / 16 * 16; }
+
+// floats in front of the split records of an m-row same-sequence attention workspace (fp16 cache: decode_verify.hip; e4m3 cache:
+// decode_verify_kv8.hip): the arrival counters, one per (kv head, chunk), at an offset that does not depend on (m, S)
+__host__ __device__ constexpr size_t attn_m_ctr_floats(int n_heads) { return ((size_t)n_heads + 15) / 16 * 16; }
 
 // ---- token begin of one row (grid = (pieces of 2048 elements, rows), block 256): embedding of toks[row] -> h32 row, the first
 // norm's producer form, the piece's sum of squares; block 0 copies the rotary row of position row_pos() (clamped to the table).

@@ -9,7 +9,7 @@
 // are shared with the launches of batched decoding (decode_batch.hip): decode_rows.h.
 #include "qeft_common.h"
 #include "decode_attn.h"      // wave_max, st_agent / ld_agent, kAttnRec
-#include "decode_rows.h"      // token_begin_norm_row, block_argmax_1024
+#include "decode_rows.h"      // token_begin_norm_row, block_argmax_1024, attn_m_ctr_floats
 
 namespace qeft {
 
@@ -48,8 +48,7 @@ hipError_t token_begin_norm_m_launch(const void* embed, const void* toks, const 
 // out_pos[h * 128 + e] when out_pos is given.  Rotary rows: tab_rows == m: row i of cs / sn (tab_stride floats apart) is
 // position pos + i; otherwise the tables are indexed by position.
 // workspace: the arrival counters come FIRST, at an offset that does not depend on (m, S) -- passes of different m / split share
-// one workspace, and a counter must never land on another configuration's records
-__host__ __device__ constexpr size_t attn_m_ctr_floats(int n_heads) { return ((size_t)n_heads + 15) / 16 * 16; }
+// one workspace, and a counter must never land on another configuration's records (attn_m_ctr_floats, decode_rows.h)
 
 template <int R>
 __global__ __launch_bounds__(256) void rope_attn_m_kernel(const int* __restrict__ pos_ptr, const int* __restrict__ out_pos,

@@ -1,0 +1,376 @@
+// The verify pass over an e4m3 KV cache (DecodeEngine(kv_dtype="fp8", kv8_verify=True)):
+//   rope_attn_m_kv8      rotary + quantise + append of m rows + causal attention, m <= 8 tokens of ONE sequence at positions
+//                        pos .. pos + m - 1, query i over keys [0, pos + i]
+// The semantics are rope_attn_m_kernel's (decode_verify.hip): the grid (n_kv * n_chunk * S blocks, a block = one kv head, hc query
+// heads x m queries = `rows` query rows r = hl * m + i, split sp), the dealing of 16-position runs over the 4 S waves, the causal
+// bound, the rotary table addressing, out_pos, the block merge and the ticket-counter split merge with the counters in front
+// (attn_m_ctr_floats).  What a run is, and how a wave works through it, is rope_attn_kv8_kernel's (decode_attn_kv8.hip): 16 rows of
+// 128 bytes, score role with two 16-byte K loads per lane and the K scale on the finished score, P.V role by position class with
+// the V scale folded into the exp weight, codes to fp32 by v_cvt_pk_f32_fp8, two runs in flight per wave with a fixed load count.
+// Cache of one layer: K codes, V codes uint8 [n_kv][max_seq][128]; K scales, V scales fp32 [n_kv][max_seq] (no slot dimension).
+// This launch's own m rows are quantised here, one wave per row (K after rotary and fp16 rounding, V as given: 2 m <= 16 rows dealt
+// over the block's 4 waves), kept in LDS as codes [8][128] x 2 and scales [8] x 2, and take the place of cache rows pos .. pos + m - 1
+// in the (at most two) runs that hold them: a token is seen exactly as the cache holds it and no block reads another block's
+// stores.  Rows behind pos + m - 1 in those runs get the last new row as a finite stand-in; every query masks them.
+#include "qeft_common.h"
+#include "decode_attn.h"      // wave_max, dpp_mov, st_agent / ld_agent, kAttnRec
+#include "decode_rows.h"      // attn_m_ctr_floats
+#include "decode_kv8.h"       // kv8_quant_row, Kv8Run, fx2
+
+namespace qeft {
+
+template <int R>
+__global__ __launch_bounds__(256) void rope_attn_m_kv8_kernel(const int* __restrict__ pos_ptr, const int* __restrict__ out_pos,
+                                                              const f16* __restrict__ q, const f16* __restrict__ k,
+                                                              const f16* __restrict__ v, const float* __restrict__ cs,
+                                                              const float* __restrict__ sn, uint8_t* __restrict__ kc,
+                                                              uint8_t* __restrict__ vc, float* __restrict__ ksc,
+                                                              float* __restrict__ vsc, f16* __restrict__ out, float* __restrict__ ws,
+                                                              int qkv_stride, int out_stride, int tab_stride, int tab_rows,
+                                                              int max_seq, int n_heads, int n_kv, int S, int m, int hc) {
+    constexpr int HD = 128;
+    constexpr int NE = (R * HD + 255) / 256;         // (row, dim) pairs per thread
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+    f16* qs = (f16*)smem_raw;                        // [R][128] rotated, pre-scaled q
+    uint8_t* knew = (uint8_t*)(qs + R * HD);         // [8][128] codes of this launch's rotated k rows
+    uint8_t* vnew = knew + 8 * HD;                   // [8][128]
+    float* nks = (float*)(vnew + 8 * HD);            // [8] k scales of the new rows
+    float* nvs = nks + 8;                            // [8] v scales
+    float* pw = nvs + 8;                             // [4 waves][R][16] exp weights of the current run
+    float* pwv = pw + 4 * R * 16;                    // [4 waves][R][16] exp weight * v scale
+    float* wacc = pwv + 4 * R * 16;                  // [4][R][128] the waves' P.V partials
+    float* wM = wacc + 4 * R * HD;                   // [4][R]
+    float* wl = wM + 4 * R;                          // [4][R]
+    __shared__ int last_ticket;
+
+    const int grp = n_heads / n_kv, n_chunk = grp / hc;
+    const int bid = blockIdx.x, sp = bid % S, hkc = bid / S, chunk = hkc % n_chunk, hk = hkc / n_chunk;
+    const int h0 = hk * grp + chunk * hc;            // first query head of this block
+    const int rows = hc * m;
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int gw = sp * 4 + w, NWH = 4 * S;
+    const int pos = *pos_ptr;
+    if (pos < 0 || pos + m > max_seq) return;        // never index the cache out of range (grid-uniform)
+    const size_t sbase = (size_t)hk * max_seq;
+    uint8_t* const kch = kc + sbase * HD;
+    uint8_t* const vch = vc + sbase * HD;
+    float* const ksh = ksc + sbase;
+    float* const vsh = vsc + sbase;
+    const bool appender = sp == 0 && chunk == 0;
+    const int Lk = pos + m;
+
+    // ---- this wave's first two runs: nothing below depends on them until the loop
+    const int qd = lane & 3, pj = lane >> 2, dg = lane & 15, pc = lane >> 4;
+    const int nrun = (Lk + 15) >> 4;
+    auto load_run = [&](Kv8Run& b, int j) {        // rows < max_seq always (pos + m <= max_seq, max_seq % 16 == 0).  A run past
+        const int r0 = (j < nrun ? j : 0) * 16;      // the context re-reads run 0 (never used): the load count stays fixed
+        const uint8_t* kp = kch + (size_t)(r0 + pj) * HD + qd * 16;
+        b.k[0] = *(const u32x4*)kp;
+        b.k[1] = *(const u32x4*)(kp + 64);
+        const uint8_t* vp = vch + (size_t)(r0 + pc * 4) * HD + dg * 8;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) b.v[i] = *(const u32x2*)(vp + i * HD);
+        b.ks = ksh[r0 + pj];
+        b.vs = vsh[r0 + pj];
+    };
+    Kv8Run bufA, bufB;
+    load_run(bufA, gw);
+    load_run(bufB, gw + NWH);
+
+    // ---- rotary of the block's q rows; the kv head's m new k rows (rotary, fp16, quantise) and v rows; the appender writes the caches
+    auto rot = [&](int i, int ii, float a, float b, float& r0, float& r1) {
+        const size_t ro = tab_rows == m ? (size_t)i * tab_stride : (size_t)(pos + i) * tab_stride;
+        const float c = cs[ro + ii], s = sn[ro + ii];
+        r0 = a * c - b * s;
+        r1 = b * c + a * s;
+    };
+    for (int e = t; e < rows * 64; e += 256) {
+        const int r = e >> 6, ii = e & 63, hl = r / m, i = r - hl * m;
+        const f16* src = q + (size_t)i * qkv_stride + (size_t)(h0 + hl) * HD;
+        float r0, r1;
+        rot(i, ii, (float)src[ii], (float)src[ii + 64], r0, r1);
+        const float scale = 0.08838834764831845f;   // 1/sqrt(128)
+        qs[r * HD + ii] = (f16)(r0 * scale);
+        qs[r * HD + ii + 64] = (f16)(r1 * scale);
+    }
+    for (int e = t; e < R * 64; e += 256)            // rows past `rows`: zero (their scores are masked anyway)
+        if ((e >> 6) >= rows) {
+            qs[(e >> 6) * HD + (e & 63)] = (f16)0.f;
+            qs[(e >> 6) * HD + (e & 63) + 64] = (f16)0.f;
+        }
+    for (int job = w; job < 2 * m; job += 4) {       // job 2 i: K row i, job 2 i + 1: V row i (wave-uniform)
+        const int i = job >> 1;
+        const bool is_v = job & 1;
+        float a, b;
+        if (!is_v) {
+            const f16* src = k + (size_t)i * qkv_stride + (size_t)hk * HD;
+            float r0, r1;
+            rot(i, lane, (float)src[lane], (float)src[lane + 64], r0, r1);
+            a = (float)(f16)r0;                      // the fp16 row an fp16 cache would hold
+            b = (float)(f16)r1;
+        } else {
+            const f16* src = v + (size_t)i * qkv_stride + (size_t)hk * HD;
+            a = (float)src[lane];
+            b = (float)src[lane + 64];
+        }
+        uint8_t ca, cb;
+        float scale;
+        kv8_quant_row(a, b, ca, cb, scale);
+        uint8_t* const nw = (is_v ? vnew : knew) + i * HD;
+        nw[lane] = ca;
+        nw[lane + 64] = cb;
+        if (lane == 0) (is_v ? nvs : nks)[i] = scale;
+        if (appender) {
+            uint8_t* const dst = (is_v ? vch : kch) + (size_t)(pos + i) * HD;
+            dst[lane] = ca;
+            dst[lane + 64] = cb;
+            if (lane == 0) (is_v ? vsh : ksh)[pos + i] = scale;
+        }
+    }
+    __syncthreads();
+
+    float Mx[R], ls[R], acc[R][8];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        Mx[r] = -3.0e38f;
+        ls[r] = 0.f;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) acc[r][d] = 0.f;
+    }
+    float* const pww = pw + w * R * 16;
+    float* const pwvw = pwv + w * R * 16;
+    int qlim[R];                                     // query row r sees keys <= pos + r % m; padding rows see none
+#pragma unroll
+    for (int r = 0; r < R; ++r) qlim[r] = r < rows ? pos + r % m : -1;
+
+    // one run: `buf` holds run j and is refilled with run j + 2 NWH as soon as its registers are taken over
+    auto do_run = [&](Kv8Run& buf, int j) {
+        const int r0 = j * 16, p = r0 + pj;
+        u32x4 kk[2] = {buf.k[0], buf.k[1]};
+        u32x2 vv[4] = {buf.v[0], buf.v[1], buf.v[2], buf.v[3]};
+        float ksv = buf.ks, vsv = buf.vs;
+        if (r0 + 15 >= pos) {                        // a run that holds new rows: they come from LDS, and so do the rows behind
+            const bool fresh = p >= pos;             // them (finite stand-ins: their scores are masked, their weights 0)
+            const int ni = min(max(p - pos, 0), m - 1);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) kk[c] = fresh ? *(const u32x4*)(knew + ni * HD + qd * 16 + 64 * c) : kk[c];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int pv = r0 + pc * 4 + i;
+                vv[i] = pv >= pos ? *(const u32x2*)(vnew + min(pv - pos, m - 1) * HD + dg * 8) : vv[i];
+            }
+            ksv = fresh ? nks[ni] : ksv;
+            vsv = fresh ? nvs[ni] : vsv;
+        }
+        load_run(buf, j + 2 * NWH);
+        // K codes -> fp16 pairs (every e4m3 value is an fp16 value)
+        h2 kh[16];
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const fx2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)kk[c][e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)kk[c][e], true);
+                kh[c * 8 + e * 2] = __builtin_bit_cast(h2, __builtin_amdgcn_cvt_pkrtz(lo[0], lo[1]));
+                kh[c * 8 + e * 2 + 1] = __builtin_bit_cast(h2, __builtin_amdgcn_cvt_pkrtz(hi[0], hi[1]));
+            }
+        float scl[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float sdot = 0.f;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const h8* qr = (const h8*)(qs + r * HD + qd * 16 + 64 * c);
+#pragma unroll
+                for (int g = 0; g < 2; ++g) {
+                    const u32x4 qw = __builtin_bit_cast(u32x4, qr[g]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sdot = dot2(as_h2(qw[e]), kh[c * 8 + g * 4 + e], sdot);
+                }
+            }
+            sdot += dpp_mov<0xB1>(sdot);
+            sdot += dpp_mov<0x4E>(sdot);
+            sdot *= ksv;                             // the row's scale, once per score
+            const bool ok = p <= qlim[r];
+            const float s = ok ? sdot : -3.0e38f;
+            const float mn = fmaxf(Mx[r], wave_max(s));
+            const float ev = ok ? __expf(s - mn) : 0.f;
+            if (qd == 0) {
+                pww[r * 16 + pj] = ev;
+                pwvw[r * 16 + pj] = ev * vsv;        // the V row's scale, once per weight
+            }
+            scl[r] = __expf(Mx[r] - mn);
+            Mx[r] = mn;
+        }
+        __builtin_amdgcn_wave_barrier();              // pw of this wave: written and read by this wave only
+        float vf[4][8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const fx2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)vv[i][e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)vv[i][e], true);
+                vf[i][4 * e] = lo[0];
+                vf[i][4 * e + 1] = lo[1];
+                vf[i][4 * e + 2] = hi[0];
+                vf[i][4 * e + 3] = hi[1];
+            }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const f32x4 e4 = *(const f32x4*)(pww + r * 16 + pc * 4), w4 = *(const f32x4*)(pwvw + r * 16 + pc * 4);
+            ls[r] = ls[r] * scl[r] + ((e4[0] + e4[1]) + (e4[2] + e4[3]));
+#pragma unroll
+            for (int d = 0; d < 8; ++d) {
+                float a = acc[r][d] * scl[r];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a += w4[i] * vf[i][d];
+                acc[r][d] = a;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    for (int j = gw; j < nrun; j += 2 * NWH) {
+        do_run(bufA, j);
+        if (j + NWH < nrun) do_run(bufB, j + NWH);
+    }
+    // the 4 position classes of a wave meet (lanes l, l ^ 16, l ^ 32, l ^ 48 hold the same dims)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+#pragma unroll
+        for (int d = 0; d < 8; ++d) {
+            float a = acc[r][d];
+            a += __shfl_xor(a, 16);
+            a += __shfl_xor(a, 32);
+            acc[r][d] = a;
+        }
+        float l = ls[r];
+        l += __shfl_xor(l, 16);
+        l += __shfl_xor(l, 32);
+        if (pc == 0) {
+            float* dst = wacc + ((size_t)w * R + r) * HD + dg * 8;
+            *(f32x4*)dst = f32x4{acc[r][0], acc[r][1], acc[r][2], acc[r][3]};
+            *(f32x4*)(dst + 4) = f32x4{acc[r][4], acc[r][5], acc[r][6], acc[r][7]};
+        }
+        if (lane == 0) {
+            wM[w * R + r] = Mx[r];
+            wl[w * R + r] = l;
+        }
+    }
+    __syncthreads();
+    // ---- merge the block's 4 waves (a wave without positions has max -3e38: factor 0); thread -> (row, dim) pairs
+    const int nel = rows * HD;
+    float mrg[NE], mM[NE], mD[NE];
+#pragma unroll
+    for (int u = 0; u < NE; ++u) {
+        const int e = t + 256 * u, r = e >> 7, d = e & 127;
+        mrg[u] = 0.f;
+        mM[u] = -3.0e38f;
+        mD[u] = 0.f;
+        if (e < nel) {
+            const float M = fmaxf(fmaxf(wM[r], wM[R + r]), fmaxf(wM[2 * R + r], wM[3 * R + r]));
+            float a = 0.f, den = 0.f;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float f = __expf(wM[g * R + r] - M);
+                a += f * wacc[((size_t)g * R + r) * HD + d];
+                den += f * wl[g * R + r];
+            }
+            mrg[u] = a;
+            mM[u] = M;
+            mD[u] = den;
+        }
+    }
+    auto store_out = [&](int e, float val) {
+        const int r = e >> 7, d = e & 127, hl = r / m, i = r - hl * m, h = h0 + hl;
+        const int op = out_pos ? out_pos[h * HD + d] : h * HD + d;
+        out[(size_t)i * out_stride + op] = (f16)val;
+    };
+    if (S == 1) {
+#pragma unroll
+        for (int u = 0; u < NE; ++u)
+            if (t + 256 * u < nel) store_out(t + 256 * u, mrg[u] / mD[u]);
+        return;
+    }
+    // ---- publish this split's records (one per query row: acc[128], max, sum), take a ticket; the last arriver merges
+    float* const recs = ws + attn_m_ctr_floats(n_heads);
+#pragma unroll
+    for (int u = 0; u < NE; ++u) {
+        const int e = t + 256 * u, r = e >> 7, d = e & 127;
+        if (e < nel) {
+            const int hl = r / m, i = r - hl * m;
+            float* rec = recs + ((size_t)((h0 + hl) * m + i) * S + sp) * kAttnRec;
+            st_agent(rec + d, mrg[u]);
+            if (d == 0) {
+                st_agent(rec + HD, mM[u]);
+                st_agent(rec + HD + 1, mD[u]);
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    unsigned* ctr = (unsigned*)ws + hkc;
+    if (t == 0) {
+        const unsigned ticket = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last_ticket = (ticket == (unsigned)(S - 1));
+        if (ticket == (unsigned)(S - 1)) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!last_ticket) return;
+#pragma unroll
+    for (int u = 0; u < NE; ++u) {
+        const int e = t + 256 * u, r = e >> 7, d = e & 127;
+        if (e < nel) {
+            const int hl = r / m, i = r - hl * m;
+            const float* r0 = recs + ((size_t)((h0 + hl) * m + i) * S) * kAttnRec;
+            float Mh = -3.0e38f;
+            for (int s = 0; s < S; ++s) Mh = fmaxf(Mh, ld_agent(r0 + s * kAttnRec + HD));
+            float a2 = 0.f, d2 = 0.f;
+            for (int s = 0; s < S; ++s) {
+                const float f = __expf(ld_agent(r0 + s * kAttnRec + HD) - Mh);      // a split without positions: factor 0
+                a2 += f * ld_agent(r0 + s * kAttnRec + d);
+                d2 += f * ld_agent(r0 + s * kAttnRec + HD + 1);
+            }
+            store_out(e, a2 / d2);
+        }
+    }
+}
+
+// Query rows per block (heads of a chunk x m).  Measured on the 64/8 layout against a 16-row block of the same role (302 VGPRs, one
+// block per CU): 8 rows are 1.7 - 2.4 x faster at m = 4 and 8 at every context and split (DESIGN.md §4.11 has the lines), although
+// the chunks of a kv head each re-read its runs.
+constexpr int kAttnMKv8Rows = 8;
+// heads of a chunk: the largest divisor of the group with hc * m <= kAttnMKv8Rows
+static int attn_m_kv8_chunk(int grp, int m) {
+    int hc = 1;
+    for (int d = 1; d <= grp; ++d)
+        if (grp % d == 0 && d * m <= kAttnMKv8Rows) hc = d;
+    return hc;
+}
+
+static size_t attn_m_kv8_smem_bytes(int R) {
+    return (size_t)R * 128 * 2 + 2 * 8 * 128 + 2 * 8 * 4 + 2 * 4 * R * 16 * 4 + 4 * R * 128 * 4 + 2 * 4 * R * 4;
+}
+
+hipError_t rope_attn_m_kv8_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
+                                  int tab_stride, int tab_rows, void* kc, void* vc, void* ks, void* vs, const int* pos,
+                                  const int* out_pos, void* out, int out_stride, void* ws, int n_heads, int n_kv, int max_seq, int S,
+                                  int m, hipStream_t st) {
+    const int grp = n_heads / n_kv, hc = attn_m_kv8_chunk(grp, m), rows = hc * m;
+    const int R = rows <= 1 ? 1 : rows <= 2 ? 2 : rows <= 4 ? 4 : 8;          // rows <= 8: m <= 8 (the C entry checks it)
+    const size_t smem = attn_m_kv8_smem_bytes(R);
+    auto go = [&](auto kern) -> hipError_t {
+        if (smem > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(kern, dim3(n_kv * (grp / hc) * S), dim3(256), smem, st, pos, out_pos, (const f16*)q, (const f16*)k,
+                           (const f16*)v, (const float*)cs, (const float*)sn, (uint8_t*)kc, (uint8_t*)vc, (float*)ks, (float*)vs,
+                           (f16*)out, (float*)ws, qkv_stride, out_stride, tab_stride, tab_rows, max_seq, n_heads, n_kv, S, m, hc);
+        return hipGetLastError();
+    };
+    if (R == 1) return go(rope_attn_m_kv8_kernel<1>);
+    if (R == 2) return go(rope_attn_m_kv8_kernel<2>);
+    if (R == 4) return go(rope_attn_m_kv8_kernel<4>);
+    return go(rope_attn_m_kv8_kernel<8>);
+}
+
+}  // namespace qeft

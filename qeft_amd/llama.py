@@ -502,9 +502,11 @@ class DecodeEngine:
     shapes) keep the round-1 scheme: every linear row-sharded, 4 all-gathers per layer.
     """
 
-    def __init__(self, model: QuantLlama, use_graph=True, tp_group=None, collective="rccl", kv_dtype="fp16"):
+    def __init__(self, model: QuantLlama, use_graph=True, tp_group=None, collective="rccl", kv_dtype="fp16", kv8_verify=False):
         """kv_dtype: "fp16", or "fp8" -- the KV cache as e4m3 codes with one fp32 scale per (position, kv head) row (132 bytes
-        where fp16 has 256), on the single-GPU v3 engine; the verify pass does not run on it.
+        where fp16 has 256), on the single-GPU v3 engine.
+        kv8_verify: True lets the verify pass (verify, verify_sample, assisted_generate) run on an fp8 cache through the m-row
+        e4m3 attention; False (the default) refuses it there.  No effect on an fp16 cache.
         collective (tensor-parallel only): "rccl" = torch.distributed's all_reduce on the group (RCCL ring over xGMI; gloo in the
         one-GPU rehearsals), "oneshot" = the hand-written single-kernel all-reduce over IPC-mapped mailboxes (qeft_amd/oneshot.py,
         SURVEY.md section 8e: the decode payload is 16 KB, latency-bound); `self.collective` says which one runs -- a request for
@@ -515,6 +517,7 @@ class DecodeEngine:
         if kv_dtype not in KV_DTYPES:
             raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
         self.kv_dtype = kv_dtype
+        self.kv8_verify = bool(kv8_verify)
         self.m = model
         s = model.shape
         dev = model.lm_head.weight.device
@@ -1190,9 +1193,10 @@ class DecodeEngine:
 
     def _verify_unsupported(self):
         why = self._m_row_unsupported()
-        if why is None and self.kv_dtype != "fp16":
-            # the m-row same-sequence attention reads an fp16 cache (decode_verify.hip); over e4m3 it is a follow-up
-            return f'the verify pass runs on an fp16 KV cache only (this engine has kv_dtype="{self.kv_dtype}")'
+        if why is None and self.kv_dtype != "fp16" and not getattr(self, "kv8_verify", False):
+            # over e4m3 the m-row same-sequence attention (decode_verify_kv8.hip) is opt-in at construction
+            return (f'the verify pass runs on an fp16 KV cache only (this engine has kv_dtype="{self.kv_dtype}"; '
+                    f'build it with kv8_verify=True for the verify pass over an fp8 KV cache)')
         return why
 
     def _verify_bufs(self):
@@ -1201,7 +1205,8 @@ class DecodeEngine:
         if vb is not None:
             return vb
         s, dev, M = self.m.shape, self.dev, self.VERIFY_MAX
-        vb = m_row_buffers(self, M, self.lib.qeft_attn_m_workspace_bytes(s.n_heads, 8, M))
+        ws_bytes = self.lib.qeft_attn_m_kv8_workspace_bytes if self.kv_dtype == "fp8" else self.lib.qeft_attn_m_workspace_bytes
+        vb = m_row_buffers(self, M, ws_bytes(s.n_heads, 8, M))
         vb.toks = torch.zeros(M, dtype=torch.long, device=dev)
         vb.out = torch.zeros(M, dtype=torch.long, device=dev)
         vb.n_acc = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1224,6 +1229,14 @@ class DecodeEngine:
                                        vb.xn.data_ptr(), vb.ssq.data_ptr(), s.hidden, s.vocab, s.max_seq, m, st))
 
         def attn(li):
+            if self.kv_dtype == "fp8":
+                ck(lib.qeft_rope_attn_decode_m_kv8(qp, qp + s.hidden * 2, qp + (s.hidden + kvd) * 2, nq, rope, rope + 64 * 4, 128, m,
+                                                   self.kc[li].data_ptr(), self.vc[li].data_ptr(), self.ks[li].data_ptr(),
+                                                   self.vs[li].data_ptr(), self.pos.data_ptr(),
+                                                   self.att_pos[li].data_ptr() if self.att_pos[li] is not None else None,
+                                                   vb.att.data_ptr(), s.hidden, vb.ws.data_ptr(), split, s.n_heads, s.n_kv_heads,
+                                                   s.max_seq, m, st))
+                return
             ck(lib.qeft_rope_attn_decode_m(qp, qp + s.hidden * 2, qp + (s.hidden + kvd) * 2, nq, rope, rope + 64 * 4, 128, m,
                                            self.kc[li].data_ptr(), self.vc[li].data_ptr(), self.pos.data_ptr(),
                                            self.att_pos[li].data_ptr() if self.att_pos[li] is not None else None,

@@ -2,7 +2,10 @@
 against one step(), and greedy assisted decoding tokens/s with an ORACLE draft (the target's own greedy continuation: every
 draft accepted, the upper bound; k = 4 and 7 drafts = 5- and 8-row passes) and with a draft that is wrong every j-th token.  Prints one JSON line.
 
-    python tools/bench_verify.py [--pos 128] [--iters 50] [--tokens 256]
+    python tools/bench_verify.py [--pos 128] [--iters 50] [--tokens 256] [--kv-dtype fp16|fp8] [--max-seq 1024] [--start 0]
+
+--kv-dtype fp8 runs the engine on an e4m3 KV cache with kv8_verify=True; --start is the position the greedy and
+assisted runs begin at (the cache below it holds zeros, which cost what any content costs: the run is for timing, its tokens mean nothing), --max-seq the cache length.
 """
 import argparse
 import dataclasses
@@ -31,11 +34,11 @@ def _time(fn, iters, warm=5):
 class _Scripted:
     """A draft that proposes the given continuation, with every j-th proposed token made wrong (j = 0: never)."""
 
-    def __init__(self, ref, vocab, wrong_every=0):
-        self.ref, self.vocab, self.j, self.count = ref, vocab, wrong_every, 0
+    def __init__(self, ref, vocab, wrong_every=0, start=0):
+        self.ref, self.vocab, self.j, self.count, self.start = ref, vocab, wrong_every, 0, start
 
     def propose(self, ctx, k):
-        i = len(ctx) - 1                     # ref[i] is the token after ctx[-1]
+        i = len(ctx) - 1 - self.start        # ref[i] is the token after ctx[-1]
         out = []
         for t in self.ref[i:i + k]:
             self.count += 1
@@ -49,13 +52,17 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--tokens", type=int, default=256)
     ap.add_argument("--only-m", type=int, default=0, help="replay only the verify pass of this m (profiling)")
+    ap.add_argument("--kv-dtype", default="fp16", choices=["fp16", "fp8"])
+    ap.add_argument("--max-seq", type=int, default=1024)
+    ap.add_argument("--start", type=int, default=0, help="position the greedy and assisted runs begin at")
     args = ap.parse_args()
     from qeft_amd.assisted import assisted_generate
     from qeft_amd.llama import LLAMA2_7B, DecodeEngine, QuantLlama
-    shape = dataclasses.replace(LLAMA2_7B, max_seq=1024)
+    shape = dataclasses.replace(LLAMA2_7B, max_seq=args.max_seq)
     model = QuantLlama(shape, "cuda:0", seed=0, fast_init=True)
-    eng = DecodeEngine(model, use_graph=True)
-    rec = {"model": "llama-2-7b shapes (w4 g128 r128)", "pos": args.pos}
+    eng = DecodeEngine(model, use_graph=True, kv_dtype=args.kv_dtype, kv8_verify=args.kv_dtype == "fp8")
+    rec = {"model": "llama-2-7b shapes (w4 g128 r128)", "pos": args.pos, "kv_dtype": args.kv_dtype, "start": args.start}
+    context = [0] * args.start
     eng.greedy = False
     if args.only_m:
         for _ in range(3):
@@ -85,11 +92,11 @@ def main():
     # the right tokens are those the target produces under that draft.
     eng.greedy = True
     n = args.tokens
-    eng.reset()
+    eng.set_position(args.start)
     eng.tok.fill_(1)
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     eng.run(8)
-    eng.reset()
+    eng.set_position(args.start)
     eng.tok.fill_(1)
     torch.cuda.synchronize()
     a.record()
@@ -102,15 +109,15 @@ def main():
         for j in (0, 4, 2):
             ref = [0] * (n + 8)
             for _ in range(12):                              # fixed point: the draft's "right" tokens are the target's own
-                eng.reset()
-                out, acc = assisted_generate(eng, _Scripted(ref, shape.vocab, j), 1, n, k)
+                eng.set_position(args.start)
+                out, acc = assisted_generate(eng, _Scripted(ref, shape.vocab, j, args.start), 1, n, k, context=context)
                 if out == ref[:n]:
                     break
                 ref = out + [0] * 8
-            eng.reset()
+            eng.set_position(args.start)
             torch.cuda.synchronize()
             a.record()
-            out, acc = assisted_generate(eng, _Scripted(ref, shape.vocab, j), 1, n, k)
+            out, acc = assisted_generate(eng, _Scripted(ref, shape.vocab, j, args.start), 1, n, k, context=context)
             b.record()
             torch.cuda.synchronize()
             t = a.elapsed_time(b) / 1e3

@@ -443,6 +443,23 @@ int qeft_rope_attn_decode_m_kv8(const void* q, const void* k, const void* v, int
                                 const int* pos, const int* out_pos, void* out, int out_stride, void* workspace, int n_split,
                                 int n_heads, int n_kv_heads, int max_seq, int m, qeft_stream_t stream);
 
+/* Causal prompt attention over the KV cache (csrc/prefill_attn.hip; llama.prefill with attn="own", DecodeEngine.extend, chunked
+ * prompts).  t fp16 query rows, already rotated, at positions start .. start + t - 1: row i holds n_heads x 128 elements at
+ * q + i * q_stride and attends the cache rows 0 .. start + i inclusive.  k_cache / v_cache: fp16 [n_kv_heads][kv_rows][128], the
+ * decode engines' layout, holding positions [0, start + t) -- the caller stores the chunk's own rows BEFORE the launch; rows from
+ * start + t on are never used (whatever they hold, NaN included).  out: fp16 [t][n_heads * 128] at out_stride, heads in natural
+ * order; head h reads kv head h / (n_heads / n_kv_heads).  Scores are scaled by 128^-0.5 in fp32, the softmax is the online form
+ * in fp32 over key tiles of 64 at absolute multiples of 64, P is rounded to fp16 for the P V product (fp32 accumulation): row i's
+ * result depends on that row, start + i and the cache alone, bit for bit -- not on how a prompt was cut into chunks.  Strides
+ * in elements, multiples of 8 and >= n_heads * 128 (q may be a view of a fused q|k|v output); all four pointers 16-byte
+ * aligned; start and t are host integers (not graph-capturable state); no workspace.  QEFT_ERR_SHAPE for t < 1, start < 0,
+ * start + t > kv_rows, n_heads % n_kv_heads != 0 or a bad stride, before any pointer is looked at.
+ * qeft_attn_prefill_check_extents: CPU-only -- enumerates every global address such a launch would form and returns the largest
+ * number of bytes by which one passes the end of its operand, 0 when none does (-1 for arguments the entry refuses). */
+int qeft_attn_prefill(const void* q, int q_stride, const void* k_cache, const void* v_cache, int kv_rows, void* out, int out_stride,
+                      int start, int t, int n_heads, int n_kv_heads, qeft_stream_t stream);
+long long qeft_attn_prefill_check_extents(int q_stride, int kv_rows, int out_stride, int start, int t, int n_heads, int n_kv_heads);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py).  A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

@@ -85,6 +85,8 @@ SIGNATURES = {
     "qeft_kv8_store_rows": [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "qeft_attn_m_kv8_workspace_bytes": [_i, _i, _i],
     "qeft_rope_attn_decode_m_kv8": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
+    "qeft_attn_prefill": [_p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
+    "qeft_attn_prefill_check_extents": [_i, _i, _i, _i, _i, _i, _i],
     "qeft_token_end_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "qeft_sample": [_p, _i, _i, _p, _p, _p, _p],
     "qeft_token_end_sample": [_p, _p, _p, _i, _p, _p],
@@ -128,7 +130,7 @@ def lib():
             fn.restype = (ctypes.c_char_p if name in ("qeft_error_string", "qeft_last_variant") else
                           ctypes.c_longlong if name in ("qeft_gemm_w4_workspace_bytes", "qeft_gemm_w4_dx_workspace_bytes",
                                                        "qeft_gemv_v3_check_extents", "qeft_gemv_v3_check_extents_ckpt",
-                                                       "qeft_gemv_v3_check_extents_m",
+                                                       "qeft_gemv_v3_check_extents_m", "qeft_attn_prefill_check_extents",
                                                        "qeft_oneshot_mailbox_bytes") else _i)
         _lib = l
     return _lib

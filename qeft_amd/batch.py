@@ -114,9 +114,9 @@ class _SlotView:
             raise ValueError(f"position {t} outside the KV cache (max_seq = {self.max_seq})")
         self.position = int(t)
 
-    def store_kv(self, li, k, v, T):
+    def store_kv(self, li, k, v, T, start=0):
         llama.store_kv_rows(self.lib, k, v, self.kc[li], self.vc[li], self.ks[li] if self.ks is not None else None,
-                            self.vs[li] if self.vs is not None else None, T)
+                            self.vs[li] if self.vs is not None else None, T, start)
 
 
 class BatchDecodeEngine:
@@ -163,9 +163,10 @@ class BatchDecodeEngine:
 
     # -- slots ---------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def admit(self, prompt, max_new_tokens, eos_id=None, sampling=None):
+    def admit(self, prompt, max_new_tokens, eos_id=None, sampling=None, chunk=None):
         """Prefill `prompt` into a free slot (llama.prefill on that slot's caches) and return the slot.  Its first token is the
         argmax of the prompt's last logits, or with `sampling` (SamplingParams, temperature > 0) drawn from them at position T.
+        chunk=C: the prompt runs as pieces of at most C tokens on the prompt attention kernel (llama.prefill's chunk).
         Raises RuntimeError when no slot is free, ValueError when the prompt does not fit."""
         toks = torch.as_tensor(prompt, dtype=torch.long).flatten()
         T = int(toks.numel())
@@ -179,7 +180,7 @@ class BatchDecodeEngine:
         slot = self.table.take(T, limit, eos)
         try:
             view = _SlotView(self, slot)
-            logits = llama.prefill(self.model, toks.to(self.dev), engine=view)
+            logits = llama.prefill(self.model, toks.to(self.dev), engine=view, chunk=chunk)
             assert view.position == T
             first = sample(logits[-1], sampling, T)[0] if drawn else torch.argmax(logits[-1])
             self.tok_slot[slot] = first

@@ -8,6 +8,7 @@
 #include "../../include/qeft_hip.h"
 #include "qeft_common.h"
 #include "gemv_v3.h"
+#include "prefill_attn.h"
 
 namespace qeft {
 hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st);
@@ -83,6 +84,8 @@ hipError_t rope_attn_m_kv8_launch(const void* q, const void* k, const void* v, i
 hipError_t kv8_store_rows_launch(const void* k, const void* v, int row_stride, void* kc, void* vc, void* ks, void* vs, int n_kv,
                                  int max_seq, int p0, int T, hipStream_t st);
 extern unsigned long long* g_attn_dbg;
+hipError_t prefill_attn_launch(const void* q, const void* kc, const void* vc, void* out, const PaGeom& G, hipStream_t st);   // prefill_attn.hip
+long long prefill_attn_count_out_of_range(const PaGeom& G);
 hipError_t sample_launch(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens,  // decode_sample.hip
                          hipStream_t st);
 hipError_t token_end_sample_launch(const void* logits, void* tok, int* pos, const int* params, int vocab, hipStream_t st);
@@ -1103,6 +1106,31 @@ int qeft_rope_attn_decode_m_kv8(const void* q, const void* k, const void* v, int
     return finish(qeft::rope_attn_m_kv8_launch(q, k, v, qkv_stride, cos_tab, sin_tab, tab_stride, tab_rows, k_codes, v_codes, k_scales,
                                                v_scales, pos, out_pos, out, out_stride, workspace, n_heads, n_kv_heads, max_seq,
                                                n_split, m, (hipStream_t)stream));
+}
+
+// ---- prompt attention over the cache (prefill_attn.hip)
+static int prefill_geom(qeft::PaGeom& G, int q_stride, int kv_rows, int out_stride, int start, int t, int n_heads, int n_kv_heads) {
+    if (t < 1 || start < 0 || kv_rows < 1 || start > kv_rows || t > kv_rows - start) return QEFT_ERR_SHAPE;
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads > 4096 || n_heads % n_kv_heads != 0) return QEFT_ERR_SHAPE;
+    if (q_stride % 8 != 0 || q_stride < n_heads * 128 || out_stride % 8 != 0 || out_stride < n_heads * 128) return QEFT_ERR_SHAPE;
+    if (kv_rows > (1 << 24) || (long long)t * q_stride > (1ll << 40)) return QEFT_ERR_SHAPE;
+    G = qeft::PaGeom{q_stride, kv_rows, out_stride, start, t, n_heads, n_kv_heads};
+    return QEFT_OK;
+}
+
+int qeft_attn_prefill(const void* q, int q_stride, const void* k_cache, const void* v_cache, int kv_rows, void* out, int out_stride,
+                      int start, int t, int n_heads, int n_kv_heads, qeft_stream_t stream) {
+    qeft::PaGeom G{};
+    if (int e = prefill_geom(G, q_stride, kv_rows, out_stride, start, t, n_heads, n_kv_heads)) return e;
+    if (!q || !k_cache || !v_cache || !out) return QEFT_ERR_NULL;
+    if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) return QEFT_ERR_ALIGN;
+    return finish(qeft::prefill_attn_launch(q, k_cache, v_cache, out, G, (hipStream_t)stream));
+}
+
+long long qeft_attn_prefill_check_extents(int q_stride, int kv_rows, int out_stride, int start, int t, int n_heads, int n_kv_heads) {
+    qeft::PaGeom G{};
+    if (prefill_geom(G, q_stride, kv_rows, out_stride, start, t, n_heads, n_kv_heads) != QEFT_OK) return -1;
+    return qeft::prefill_attn_count_out_of_range(G);
 }
 
 // ---- sampled token end (decode_sample.hip)

@@ -1,0 +1,55 @@
+// Geometry and index arithmetic of the prompt attention (prefill_attn.hip), shared by the kernel and by the host-side address
+// enumeration behind qeft_attn_prefill_check_extents: every global address the kernel forms comes out of one of the pa_*_off
+// functions below, with its row already clamped into the operand by pa_q_row / pa_key_row.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace qeft {
+
+constexpr int PA_HD = 128;                  // head size
+constexpr int PA_WAVES = 4;                 // waves per block, 32 query rows each
+constexpr int PA_QT = 32 * PA_WAVES;        // query rows per block
+constexpr int PA_KT = 64;                   // keys per tile; tiles sit at absolute multiples of 64 from position 0
+constexpr int PA_THREADS = 64 * PA_WAVES;
+constexpr int PA_CHUNKS = PA_KT * PA_HD / 8;                 // 16-byte pieces of one K (or V) tile
+constexpr int PA_STAGE = PA_CHUNKS / PA_THREADS;             // pieces per thread
+
+struct PaGeom {
+    int q_stride, kv_rows, out_stride, start, t, n_heads, n_kv;
+};
+
+__host__ __device__ inline int pa_q_tiles(const PaGeom& G) { return (G.t + PA_QT - 1) / PA_QT; }
+// key tiles a Q tile walks: through the diagonal of its last real row
+__host__ __device__ inline int pa_key_tiles(const PaGeom& G, int qtile) {
+    const int last = qtile * PA_QT + PA_QT - 1 < G.t ? qtile * PA_QT + PA_QT - 1 : G.t - 1;
+    return (G.start + last) / PA_KT + 1;
+}
+// the launch order: the heaviest (last) Q tiles first, the heads of one kv group next to each other
+__host__ __device__ inline int pa_block_qtile(const PaGeom& G, int block) { return pa_q_tiles(G) - 1 - block / G.n_heads; }
+__host__ __device__ inline int pa_block_head(const PaGeom& G, int block) { return block % G.n_heads; }
+__host__ __device__ inline int pa_kv_head(const PaGeom& G, int head) { return head / (G.n_heads / G.n_kv); }
+
+// query row of lane row r of wave `wave`; rows past the chunk repeat its last row (computed, never stored)
+__host__ __device__ inline int pa_q_row(const PaGeom& G, int qtile, int wave, int r) {
+    const int row = qtile * PA_QT + wave * 32 + r;
+    return row < G.t ? row : G.t - 1;
+}
+// cache row of row `row` of key tile `tile`; rows past the context repeat its last row (K: masked; V: zeroed at staging)
+__host__ __device__ inline int pa_key_row(const PaGeom& G, int tile, int row) {
+    const int key = tile * PA_KT + row, len = G.start + G.t;
+    return key < len ? key : len - 1;
+}
+// element offsets; `chunk` counts 8 elements (16 bytes)
+__host__ __device__ inline long long pa_q_off(const PaGeom& G, int row, int head, int chunk) {
+    return (long long)row * G.q_stride + head * PA_HD + chunk * 8;
+}
+__host__ __device__ inline long long pa_kv_off(const PaGeom& G, int kvh, int key, int chunk) {
+    return ((long long)kvh * G.kv_rows + key) * PA_HD + chunk * 8;
+}
+__host__ __device__ inline long long pa_out_off(const PaGeom& G, int row, int head, int d) {
+    return (long long)row * G.out_stride + head * PA_HD + d;
+}
+// head dimension of accumulator register e of d-block db in lane half h (the 32x32 C/D map), first of a group of four
+__host__ __device__ inline int pa_acc_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+
+}  // namespace qeft

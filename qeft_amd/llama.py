@@ -346,20 +346,114 @@ def _prefill_operands(model):
     return ops
 
 
+_E4M3 = {}
+
+
+def kv8_decode_rows(codes, scales):
+    """e4m3 codes (uint8 [..., 128]) x their fp32 row scales ([...]) -> fp16: the code's value times the scale in fp32, rounded
+    once to fp16 (what the e4m3 attention kernels multiply by, rounded as the fp16 prompt attention needs it).  0x7f / 0xff are
+    NaN.  The 256 values come from the bit fields: sign | 4 exponent bits, bias 7 | 3 mantissa bits, exponent 0 subnormal."""
+    tab = _E4M3.get(codes.device)
+    if tab is None:
+        c = torch.arange(256, dtype=torch.int32)
+        e, mnt = (c >> 3) & 15, (c & 7).float()
+        mag = torch.where(e == 0, mnt * 2.0 ** -9, (1 + mnt / 8) * torch.exp2((e - 7).float()))
+        mag = torch.where((c & 0x7f) == 0x7f, torch.full_like(mag, float("nan")), mag)
+        tab = _E4M3[codes.device] = torch.where(c >= 128, -mag, mag).to(codes.device)
+    return (tab[codes.long()] * scales[..., None].float()).half()
+
+
+class _TransientKV:
+    """What the own prompt attention needs of an engine when there is none: fp16 K / V images [n_kv][rows][128] per layer for
+    the length of one prefill call.  A single pass needs one layer's image at a time and shares one pair of buffers; a chunked
+    prompt keeps every layer's rows for its later pieces."""
+    P = 1
+    ks = vs = None
+
+    def __init__(self, model, rows, per_layer):
+        s, dev = model.shape, model.model.embed_tokens.weight.device
+        self.lib = _lib.lib()
+        new = lambda: torch.empty(s.n_kv_heads, rows, 128, dtype=torch.float16, device=dev)      # noqa: E731
+        if per_layer:
+            self.kc, self.vc = [new() for _ in range(s.n_layers)], [new() for _ in range(s.n_layers)]
+        else:
+            self.kc, self.vc = [new()] * s.n_layers, [new()] * s.n_layers
+
+    def store_kv(self, li, k, v, T, start=0):
+        store_kv_rows(self.lib, k, v, self.kc[li], self.vc[li], None, None, T, start)
+
+    def set_position(self, t):
+        pass
+
+
+def _own_attention(kv, li, q, k, v, start, T, n_heads, n_kv):
+    """Layer li's causal attention of T rotated query rows at positions [start, start + T) on qeft_attn_prefill.  The chunk's
+    K / V rows go into `kv`'s cache first; an fp16 cache is read in place, an e4m3 cache through a transient fp16 image
+    [n_kv][start + T][128]: the past rows decoded (kv8_decode_rows), the chunk's own rows as they are."""
+    if not q.is_cuda:
+        raise RuntimeError("the prompt attention kernel needs GPU tensors (there is no CPU fallback)")
+    kv.store_kv(li, k, v, T, start)
+    if kv.ks is None:
+        kimg, vimg = kv.kc[li], kv.vc[li]
+    else:
+        kimg, vimg = (torch.cat([kv8_decode_rows(c[:, :start], sc[:, :start]), x.transpose(0, 1)], 1).contiguous()
+                      for c, sc, x in ((kv.kc[li], kv.ks[li], k), (kv.vc[li], kv.vs[li], v)))
+    assert kimg.is_contiguous() and vimg.is_contiguous() and kimg.shape == vimg.shape and kimg.shape[0] == n_kv
+    if not (q.stride(2) == 1 and q.stride(1) == 128 and q.stride(0) % 8 == 0):
+        q = q.contiguous()
+    out = torch.empty(T, n_heads * 128, dtype=torch.float16, device=q.device)
+    _lib.check(_lib.lib().qeft_attn_prefill(q.data_ptr(), q.stride(0), kimg.data_ptr(), vimg.data_ptr(), kimg.shape[1],
+                                            out.data_ptr(), out.stride(0), start, T, n_heads, n_kv,
+                                            torch.cuda.current_stream(q.device).cuda_stream))
+    return out
+
+
 @torch.no_grad()
-def prefill(model: "QuantLlama", tokens, engine=None):
+def prefill(model: "QuantLlama", tokens, engine=None, *, start=0, attn=None, chunk=None):
     """Batched forward over T prompt tokens through the packed QuantLinears: T >= 8 rows take the MFMA GEMM path
-    (fused outlier slice; BASELINE config 3), attention is torch's causal SDPA in fp16.  Returns fp16 logits
-    [T, vocab].  With `engine` (a DecodeEngine of the same model) the rotated keys and the values are written into its
-    KV caches and its position is set to T, so decoding continues from the prompt (main.py:340-371 feeds the prompt
-    token by token; this is the batched equivalent)."""
+    (fused outlier slice; BASELINE config 3).  Returns fp16 logits [T, vocab].  With `engine` (a DecodeEngine of the same model)
+    the rotated keys and the values are written into its KV caches at positions [start, start + T) and its position is set to
+    start + T, so decoding continues from the prompt (main.py:340-371 feeds the prompt token by token; this is the batched
+    equivalent).
+    attn: "sdpa" -- torch's causal SDPA in fp16 over the prompt alone (start == 0 only); "own" -- qeft_attn_prefill over the
+    cache (without an engine, over a transient image of the prompt's rows).  None: "sdpa" at start == 0, "own" at start > 0.
+    start > 0 continues a cached sequence (ftllama_modeling.py:87-125, q_len > 8 at start_pos > 0): it needs the engine whose
+    caches hold positions [0, start).  chunk=C runs the prompt as consecutive pieces of at most C tokens on the own kernel, each
+    starting where the previous one ended; the logits are the pieces' concatenated."""
+    s = model.shape
+    T, start = tokens.numel(), int(start)
+    if attn not in (None, "sdpa", "own"):
+        raise ValueError(f'attn must be "sdpa", "own" or None, got {attn!r}')
+    if chunk is not None:
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        if attn == "sdpa":
+            raise ValueError('a chunked prompt runs on the own attention kernel (attn="sdpa" attends the prompt alone)')
+        attn = "own"
+    if start < 0:
+        raise ValueError(f"start must be >= 0, got {start}")
+    if attn is None:
+        attn = "sdpa" if start == 0 else "own"
+    if attn == "sdpa" and start > 0:
+        raise ValueError('attn="sdpa" attends the prompt alone: a pass at start > 0 takes attn="own"')
+    if start > 0 and engine is None:
+        raise ValueError("start > 0 continues a cached sequence: pass the engine that holds positions [0, start)")
+    assert start + T <= s.max_seq and (engine is None or engine.P == 1), "prefill hands over to a single-GPU engine"
+    if chunk is None or T <= chunk:
+        return _prefill_pass(model, tokens, engine, start, attn)
+    kv = engine if engine is not None else _TransientKV(model, T, per_layer=True)
+    return torch.cat([_prefill_pass(model, tokens[a:a + chunk], kv, start + a, "own") for a in range(0, T, chunk)])
+
+
+def _prefill_pass(model, tokens, engine, start, attn):
+    """One pass of prefill(): T tokens at positions [start, start + T)."""
     s = model.shape
     T = tokens.numel()
-    assert T <= s.max_seq and (engine is None or engine.P == 1), "prefill hands over to a single-GPU engine"
     h = model.model.embed_tokens.weight[tokens]                       # [T, hidden] fp16
-    cos, sin = model.rope_cos[:T, None, :], model.rope_sin[:T, None, :]
+    cos, sin = model.rope_cos[start:start + T, None, :], model.rope_sin[start:start + T, None, :]
 
-    cos_t, sin_t = model.rope_cos[:T].contiguous(), model.rope_sin[:T].contiguous()
+    cos_t, sin_t = model.rope_cos[start:start + T].contiguous(), model.rope_sin[start:start + T].contiguous()
     lib = _lib.lib()
 
     def rope(x, heads=None):                                          # [T, H, 128] fp16 -> rotated fp16 (fp32 math), in place
@@ -370,6 +464,9 @@ def prefill(model: "QuantLlama", tokens, engine=None):
         a, b = x[..., :64].float(), x[..., 64:].float()
         return torch.cat([a * cos - b * sin, b * cos + a * sin], dim=-1).half()
 
+    kv = None
+    if attn == "own":
+        kv = engine if engine is not None else _TransientKV(model, T, per_layer=False)
     fused = _prefill_operands(model) if T >= 8 and h.is_cuda else None
     hq, hkv = s.n_heads * 128, s.n_kv_heads * 128
     delta = None                                                      # the previous layer's down_proj output, added by the next norm
@@ -391,15 +488,18 @@ def prefill(model: "QuantLlama", tokens, engine=None):
             q = rope(at.q_proj(x).view(T, s.n_heads, 128))
             k = rope(at.k_proj(x).view(T, s.n_kv_heads, 128))
             v = at.v_proj(x).view(T, s.n_kv_heads, 128)
-        if engine is not None:
-            engine.store_kv(li, k, v, T)
-        rep = s.n_heads // s.n_kv_heads
-        kk, vv = (k, v) if rep == 1 else (k.repeat_interleave(rep, 1), v.repeat_interleave(rep, 1))
-        # 4-D operands: torch routes an unbatched [H, T, 128] call to its math path (1.6 ms per layer at T = 2048 on this
-        # build) and a batched one to the fused kernel (0.14 ms) -- tools/sdpa_probe.py
-        a = torch.nn.functional.scaled_dot_product_attention(q.transpose(0, 1)[None], kk.transpose(0, 1)[None],
-                                                             vv.transpose(0, 1)[None], is_causal=True)[0]    # [H, T, 128]
-        a = a.transpose(0, 1).reshape(T, s.hidden).contiguous()
+        if kv is not None:
+            a = _own_attention(kv, li, q, k, v, start, T, s.n_heads, s.n_kv_heads)
+        else:
+            if engine is not None:
+                engine.store_kv(li, k, v, T)
+            rep = s.n_heads // s.n_kv_heads
+            kk, vv = (k, v) if rep == 1 else (k.repeat_interleave(rep, 1), v.repeat_interleave(rep, 1))
+            # 4-D operands: torch routes an unbatched [H, T, 128] call to its math path (1.6 ms per layer at T = 2048 on this
+            # build) and a batched one to the fused kernel (0.14 ms) -- tools/sdpa_probe.py
+            a = torch.nn.functional.scaled_dot_product_attention(q.transpose(0, 1)[None], kk.transpose(0, 1)[None],
+                                                                 vv.transpose(0, 1)[None], is_causal=True)[0]    # [H, T, 128]
+            a = a.transpose(0, 1).reshape(T, s.hidden).contiguous()
         h, x = _add_rmsnorm(h, at.o_proj(a), L.post_attention_layernorm.weight, s.rms_eps)     # o_proj gathers its own column order
         if "gu" in fo and qeft_cuda.gemm_gateup_supported(T, fo["gu"]):
             act = qeft_cuda.gemm_4bit_gateup(x, fo["gu"])             # gate|up as one GEMM, SiLU(gate) * up its epilogue
@@ -407,7 +507,7 @@ def prefill(model: "QuantLlama", tokens, engine=None):
             act = mlp.up_proj.forward_silu_mul(x, mlp.gate_proj(x))   # SiLU(gate) * up in the up_proj GEMM's epilogue
         delta = mlp.down_proj(act)
     if engine is not None:
-        engine.set_position(T)
+        engine.set_position(start + T)
     _, hn = _add_rmsnorm(h, delta, model.model.norm.weight, s.rms_eps)
     return torch.matmul(hn, model.lm_head.weight.t())
 
@@ -425,18 +525,19 @@ def kv_cache_arrays(kv_dtype, lead, n_kv, max_seq, dev):
     return tuple(torch.zeros(*lead, n_kv, max_seq, 128, dtype=torch.float16, device=dev) for _ in range(2))
 
 
-def store_kv_rows(lib, k, v, kc, vc, ks, vs, T):
+def store_kv_rows(lib, k, v, kc, vc, ks, vs, T, start=0):
     """The prefill hand-over into ONE sequence's cache of one layer: rotated keys k and values v, [T, n_kv, 128] fp16 (views of
-    the fused q|k|v output are taken as they are), to positions [0, T).  ks is None: the fp16 cache, a slice assignment; else
-    the e4m3 cache through qeft_kv8_store_rows."""
+    the fused q|k|v output are taken as they are), to positions [start, start + T).  ks is None: the fp16 cache, a slice
+    assignment; else the e4m3 cache through qeft_kv8_store_rows."""
     if ks is None:
-        kc[:, :T] = k.transpose(0, 1)
-        vc[:, :T] = v.transpose(0, 1)
+        kc[:, start:start + T] = k.transpose(0, 1)
+        vc[:, start:start + T] = v.transpose(0, 1)
         return
     if not (k.stride(2) == 1 and k.stride(1) == 128 and v.stride() == k.stride()):
         k, v = k.contiguous(), v.contiguous()
     _lib.check(lib.qeft_kv8_store_rows(k.data_ptr(), v.data_ptr(), k.stride(0), kc.data_ptr(), vc.data_ptr(), ks.data_ptr(),
-                                       vs.data_ptr(), kc.shape[0], kc.shape[1], 0, T, torch.cuda.current_stream(k.device).cuda_stream))
+                                       vs.data_ptr(), kc.shape[0], kc.shape[1], start, T,
+                                       torch.cuda.current_stream(k.device).cuda_stream))
 
 
 def _ptr_array(tensors):
@@ -758,10 +859,18 @@ class DecodeEngine:
     def _kv8_needs(why):
         return f'kv_dtype="fp8" runs on the single-GPU v3 engine only ({why})'
 
-    def store_kv(self, li, k, v, T):
-        """llama.prefill's hand-over: layer li's rotated keys and values [T, n_kv, 128] fp16 -> cache positions [0, T)."""
+    def store_kv(self, li, k, v, T, start=0):
+        """llama.prefill's hand-over: layer li's rotated keys and values [T, n_kv, 128] fp16 -> cache positions [start, start + T)."""
         fp8 = self.kv_dtype == "fp8"
-        store_kv_rows(self.lib, k, v, self.kc[li], self.vc[li], self.ks[li] if fp8 else None, self.vs[li] if fp8 else None, T)
+        store_kv_rows(self.lib, k, v, self.kc[li], self.vc[li], self.ks[li] if fp8 else None, self.vs[li] if fp8 else None, T,
+                      start)
+
+    def extend(self, tokens):
+        """Append `tokens` to the cached sequence in ONE batched pass (prefill at start = host_pos: the GEMM path and the prompt
+        attention over the cache) instead of verify passes of 8 or steps of 1.  Returns fp16 logits [T, vocab]; row i predicts
+        position host_pos + i + 1.  The position moves on by T."""
+        self._check_fresh()
+        return prefill(self.m, torch.as_tensor(tokens, dtype=torch.long).flatten().to(self.dev), engine=self, start=self.host_pos)
 
     def _split_for(self, pos):
         if self.attn_split_forced:

@@ -460,6 +460,24 @@ int qeft_attn_prefill(const void* q, int q_stride, const void* k_cache, const vo
                       int start, int t, int n_heads, int n_kv_heads, qeft_stream_t stream);
 long long qeft_attn_prefill_check_extents(int q_stride, int kv_rows, int out_stride, int start, int t, int n_heads, int n_kv_heads);
 
+/* The same attention with the past in an FP8 KV cache (csrc/prefill_attn_kv8.hip; llama.prefill / DecodeEngine.extend /
+ * BatchDecodeEngine.admit(chunk=) on kv_dtype="fp8").  q, out, start, t, the head layout and every rule as qeft_attn_prefill.
+ * Keys [0, start): ONE sequence's cache as laid out above, read in place -- k_codes / v_codes uint8 [n_kv_heads][kv_rows][128]
+ * e4m3fn, k_scales / v_scales fp32 [n_kv_heads][kv_rows]; a row's fp16 value is float(code) * scale in fp32, rounded once to
+ * fp16 (nearest even, subnormals kept).  Keys [start, start + t): the chunk's own rotated K rows and its V rows in fp16, k_new /
+ * v_new [t][>= n_kv_heads * 128], rows new_stride elements apart (views of the fused q|k|v output), attended UNQUANTISED.  The
+ * cache's rows at positions >= start are never read (the caller may store the chunk before or after the launch), and with
+ * start == 0 no cache value is read at all.  The result is bit-identical to qeft_attn_prefill over the fp16 image
+ * [decoded rows 0 .. start - 1 | the new rows].  new_stride % 8 == 0 and >= n_kv_heads * 128 (QEFT_ERR_SHAPE otherwise, with
+ * qeft_attn_prefill's shape rules, before any pointer is looked at); q, out, codes and new rows 16-byte aligned, scales 4-byte
+ * aligned; no workspace.
+ * qeft_attn_prefill_kv8_check_extents: CPU-only, as qeft_attn_prefill_check_extents, over all eight operands. */
+int qeft_attn_prefill_kv8(const void* q, int q_stride, const void* k_codes, const void* v_codes, const void* k_scales,
+                          const void* v_scales, int kv_rows, const void* k_new, const void* v_new, int new_stride, void* out,
+                          int out_stride, int start, int t, int n_heads, int n_kv_heads, qeft_stream_t stream);
+long long qeft_attn_prefill_kv8_check_extents(int q_stride, int kv_rows, int new_stride, int out_stride, int start, int t, int n_heads,
+                                              int n_kv_heads);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py).  A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

@@ -87,6 +87,8 @@ SIGNATURES = {
     "qeft_rope_attn_decode_m_kv8": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
     "qeft_attn_prefill": [_p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
     "qeft_attn_prefill_check_extents": [_i, _i, _i, _i, _i, _i, _i],
+    "qeft_attn_prefill_kv8": [_p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
+    "qeft_attn_prefill_kv8_check_extents": [_i, _i, _i, _i, _i, _i, _i, _i],
     "qeft_token_end_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "qeft_sample": [_p, _i, _i, _p, _p, _p, _p],
     "qeft_token_end_sample": [_p, _p, _p, _i, _p, _p],
@@ -131,6 +133,7 @@ def lib():
                           ctypes.c_longlong if name in ("qeft_gemm_w4_workspace_bytes", "qeft_gemm_w4_dx_workspace_bytes",
                                                        "qeft_gemv_v3_check_extents", "qeft_gemv_v3_check_extents_ckpt",
                                                        "qeft_gemv_v3_check_extents_m", "qeft_attn_prefill_check_extents",
+                                                       "qeft_attn_prefill_kv8_check_extents",
                                                        "qeft_oneshot_mailbox_bytes") else _i)
         _lib = l
     return _lib

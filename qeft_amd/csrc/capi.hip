@@ -86,6 +86,9 @@ hipError_t kv8_store_rows_launch(const void* k, const void* v, int row_stride, v
 extern unsigned long long* g_attn_dbg;
 hipError_t prefill_attn_launch(const void* q, const void* kc, const void* vc, void* out, const PaGeom& G, hipStream_t st);   // prefill_attn.hip
 long long prefill_attn_count_out_of_range(const PaGeom& G);
+hipError_t prefill_attn_kv8_launch(const void* q, const void* kq, const void* vq, const void* ksc, const void* vsc, const void* kn,
+                                   const void* vn, void* out, const Pa8Geom& G8, hipStream_t st);   // prefill_attn_kv8.hip
+long long prefill_attn_kv8_count_out_of_range(const Pa8Geom& G8);
 hipError_t sample_launch(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens,  // decode_sample.hip
                          hipStream_t st);
 hipError_t token_end_sample_launch(const void* logits, void* tok, int* pos, const int* params, int vocab, hipStream_t st);
@@ -1131,6 +1134,34 @@ long long qeft_attn_prefill_check_extents(int q_stride, int kv_rows, int out_str
     qeft::PaGeom G{};
     if (prefill_geom(G, q_stride, kv_rows, out_stride, start, t, n_heads, n_kv_heads) != QEFT_OK) return -1;
     return qeft::prefill_attn_count_out_of_range(G);
+}
+
+// ---- prompt attention with the past in an e4m3 cache (prefill_attn_kv8.hip)
+static int prefill_kv8_geom(qeft::Pa8Geom& G8, int q_stride, int kv_rows, int new_stride, int out_stride, int start, int t, int n_heads,
+                            int n_kv_heads) {
+    if (int e = prefill_geom(G8.g, q_stride, kv_rows, out_stride, start, t, n_heads, n_kv_heads)) return e;
+    if (new_stride % 8 != 0 || new_stride < n_kv_heads * 128 || (long long)t * new_stride > (1ll << 40)) return QEFT_ERR_SHAPE;
+    G8.new_stride = new_stride;
+    return QEFT_OK;
+}
+
+int qeft_attn_prefill_kv8(const void* q, int q_stride, const void* k_codes, const void* v_codes, const void* k_scales,
+                          const void* v_scales, int kv_rows, const void* k_new, const void* v_new, int new_stride, void* out,
+                          int out_stride, int start, int t, int n_heads, int n_kv_heads, qeft_stream_t stream) {
+    qeft::Pa8Geom G8{};
+    if (int e = prefill_kv8_geom(G8, q_stride, kv_rows, new_stride, out_stride, start, t, n_heads, n_kv_heads)) return e;
+    if (!q || !k_codes || !v_codes || !k_scales || !v_scales || !k_new || !v_new || !out) return QEFT_ERR_NULL;
+    if (!aligned16(q) || !aligned16(k_codes) || !aligned16(v_codes) || !aligned16(k_new) || !aligned16(v_new) || !aligned16(out) ||
+        ((uintptr_t)k_scales & 3) || ((uintptr_t)v_scales & 3))
+        return QEFT_ERR_ALIGN;
+    return finish(qeft::prefill_attn_kv8_launch(q, k_codes, v_codes, k_scales, v_scales, k_new, v_new, out, G8, (hipStream_t)stream));
+}
+
+long long qeft_attn_prefill_kv8_check_extents(int q_stride, int kv_rows, int new_stride, int out_stride, int start, int t, int n_heads,
+                                              int n_kv_heads) {
+    qeft::Pa8Geom G8{};
+    if (prefill_kv8_geom(G8, q_stride, kv_rows, new_stride, out_stride, start, t, n_heads, n_kv_heads) != QEFT_OK) return -1;
+    return qeft::prefill_attn_kv8_count_out_of_range(G8);
 }
 
 // ---- sampled token end (decode_sample.hip)

@@ -49,6 +49,34 @@ __host__ __device__ inline long long pa_kv_off(const PaGeom& G, int kvh, int key
 __host__ __device__ inline long long pa_out_off(const PaGeom& G, int row, int head, int d) {
     return (long long)row * G.out_stride + head * PA_HD + d;
 }
+
+// ---- the same attention with K / V of the past read from an e4m3 cache (prefill_attn_kv8.hip): keys [0, start) are rows of the
+// codes uint8 [n_kv][kv_rows][128] and scales fp32 [n_kv][kv_rows], keys [start, start + t) rows of the chunk's own fp16 K / V,
+// [t][>= n_kv * 128] at new_stride.  The source is chosen per key row; each row index is clamped into its own operand.
+struct Pa8Geom {
+    PaGeom g;
+    int new_stride;
+};
+__host__ __device__ inline bool pa8_from_cache(const PaGeom& G, int key) { return key < G.start; }
+__host__ __device__ inline int pa8_cache_row(const PaGeom& G, int key) {
+    const int row = key < G.start - 1 ? key : G.start - 1;
+    return row > 0 ? row : 0;
+}
+__host__ __device__ inline int pa8_new_row(const PaGeom& G, int key) {
+    const int row = key - G.start < G.t - 1 ? key - G.start : G.t - 1;
+    return row > 0 ? row : 0;
+}
+// byte offset of a chunk's codes (`chunk` as above: 8 elements; the kernel loads the aligned 16 bytes of chunk pair
+// pa8_code_pair(chunk)), element offset of the row's scale, element offset into the new rows
+__host__ __device__ inline int pa8_code_pair(int chunk) { return chunk & ~1; }
+__host__ __device__ inline long long pa8_code_off(const PaGeom& G, int kvh, int row, int chunk) {
+    return ((long long)kvh * G.kv_rows + row) * PA_HD + chunk * 8;
+}
+__host__ __device__ inline long long pa8_scale_off(const PaGeom& G, int kvh, int row) { return (long long)kvh * G.kv_rows + row; }
+__host__ __device__ inline long long pa8_new_off(const Pa8Geom& G8, int row, int kvh, int chunk) {
+    return (long long)row * G8.new_stride + kvh * PA_HD + chunk * 8;
+}
+
 // head dimension of accumulator register e of d-block db in lane half h (the 32x32 C/D map), first of a group of four
 __host__ __device__ inline int pa_acc_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 

@@ -387,24 +387,31 @@ class _TransientKV:
 
 
 def _own_attention(kv, li, q, k, v, start, T, n_heads, n_kv):
-    """Layer li's causal attention of T rotated query rows at positions [start, start + T) on qeft_attn_prefill.  The chunk's
-    K / V rows go into `kv`'s cache first; an fp16 cache is read in place, an e4m3 cache through a transient fp16 image
-    [n_kv][start + T][128]: the past rows decoded (kv8_decode_rows), the chunk's own rows as they are."""
+    """Layer li's causal attention of T rotated query rows at positions [start, start + T).  The chunk's K / V rows go into
+    `kv`'s cache first.  An fp16 cache is read in place by qeft_attn_prefill.  An e4m3 cache is read in place too, by
+    qeft_attn_prefill_kv8: the past rows [0, start) decoded on the way (kv8_decode_rows' values, bit for bit), the chunk's own
+    rows taken from k / v as they are, unquantised -- no fp16 image of the past, nothing allocated that grows with start."""
     if not q.is_cuda:
         raise RuntimeError("the prompt attention kernel needs GPU tensors (there is no CPU fallback)")
     kv.store_kv(li, k, v, T, start)
-    if kv.ks is None:
-        kimg, vimg = kv.kc[li], kv.vc[li]
-    else:
-        kimg, vimg = (torch.cat([kv8_decode_rows(c[:, :start], sc[:, :start]), x.transpose(0, 1)], 1).contiguous()
-                      for c, sc, x in ((kv.kc[li], kv.ks[li], k), (kv.vc[li], kv.vs[li], v)))
-    assert kimg.is_contiguous() and vimg.is_contiguous() and kimg.shape == vimg.shape and kimg.shape[0] == n_kv
     if not (q.stride(2) == 1 and q.stride(1) == 128 and q.stride(0) % 8 == 0):
         q = q.contiguous()
     out = torch.empty(T, n_heads * 128, dtype=torch.float16, device=q.device)
-    _lib.check(_lib.lib().qeft_attn_prefill(q.data_ptr(), q.stride(0), kimg.data_ptr(), vimg.data_ptr(), kimg.shape[1],
-                                            out.data_ptr(), out.stride(0), start, T, n_heads, n_kv,
-                                            torch.cuda.current_stream(q.device).cuda_stream))
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    if kv.ks is None:
+        kimg, vimg = kv.kc[li], kv.vc[li]
+        assert kimg.is_contiguous() and vimg.is_contiguous() and kimg.shape == vimg.shape and kimg.shape[0] == n_kv
+        _lib.check(_lib.lib().qeft_attn_prefill(q.data_ptr(), q.stride(0), kimg.data_ptr(), vimg.data_ptr(), kimg.shape[1],
+                                                out.data_ptr(), out.stride(0), start, T, n_heads, n_kv, stream))
+        return out
+    kc, vc, ks, vs = kv.kc[li], kv.vc[li], kv.ks[li], kv.vs[li]
+    assert all(x.is_contiguous() for x in (kc, vc, ks, vs)) and kc.shape == vc.shape == (n_kv, kc.shape[1], 128)
+    assert ks.shape == vs.shape == kc.shape[:2]
+    if not (k.stride(2) == 1 and k.stride(1) == 128 and k.stride(0) % 8 == 0 and v.stride() == k.stride()):
+        k, v = k.contiguous(), v.contiguous()
+    _lib.check(_lib.lib().qeft_attn_prefill_kv8(q.data_ptr(), q.stride(0), kc.data_ptr(), vc.data_ptr(), ks.data_ptr(), vs.data_ptr(),
+                                                kc.shape[1], k.data_ptr(), v.data_ptr(), k.stride(0), out.data_ptr(), out.stride(0),
+                                                start, T, n_heads, n_kv, stream))
     return out
 
 

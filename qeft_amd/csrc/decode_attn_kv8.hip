@@ -7,7 +7,7 @@
 #include "qeft_common.h"
 #include "decode_attn.h"      // wave_max, dpp_mov, st_agent / ld_agent, kAttnRec
 #include "decode_rows.h"      // row_slot, attn_b_ctr_floats
-#include "decode_kv8.h"       // kv8_quant_row, Kv8Run, fx2
+#include "decode_kv8.h"       // kv8_quant_row, Kv8Run, fx2, the host side of the launch
 
 namespace qeft {
 
@@ -37,7 +37,10 @@ hipError_t kv8_store_rows_launch(const void* k, const void* v, int row_stride, v
 
 // ---- rotary + quantise + append + attention.  The grid, the dealing of 16-position runs to the 4 S waves of a (row, kv head), the
 // GQA chunking, the online softmax, the split merge and the rules for skipped rows are rope_attn_b_kernel's (decode_batch.hip);
-// the block merge and the split merge below are its code.  What differs is what a run is: 16 rows of 128 BYTES.
+// the block merge and the split merge below are its code.  What differs is what a run is: 16 rows of 128 BYTES.  This kernel is
+// rope_attn_m_kv8_kernel (decode_verify_kv8.hip) at m = 1 with the slot table and `done` in front, one grid row per sequence and a
+// per-row workspace offset.  The two share the host side of the launch (decode_kv8.h); their device code is written out in both
+// files, so a fix belongs in both: shared, this kernel ran slower (decode_kv8.h's header, profiles/kv8_attn_core_refactor.log).
 //   score role  lane = (position pj = lane / 4, quarter qd = lane % 4): two 16-byte loads, dims qd * 16 + 64 c .. + 16 (the 4 lanes of
 //               a position read 64 contiguous bytes per instruction, a wave 1 KB), and the position's two scales;
 //   P.V role    lane = (position class pc = lane / 16, dim group dg = lane % 16): four 8-byte loads, dims dg * 8 .. + 8 of positions
@@ -361,18 +364,6 @@ __global__ __launch_bounds__(256) void rope_attn_kv8_kernel(const int* __restric
     }
 }
 
-// heads of a chunk: the largest divisor of the group that is <= 8 (as the fp16 kernel's)
-static int attn_kv8_chunk(int grp) {
-    int hc = 1;
-    for (int d = 1; d <= grp && d <= 8; ++d)
-        if (grp % d == 0) hc = d;
-    return hc;
-}
-
-static size_t attn_kv8_smem_bytes(int R) {
-    return (size_t)R * 128 * 2 + 2 * 128 + 4 * 4 + 2 * 4 * R * 16 * 4 + 4 * R * 128 * 4 + 2 * 4 * R * 4;
-}
-
 size_t attn_kv8_workspace_bytes(int n_heads, int S, int m) {
     return S > 1 ? (attn_b_ctr_floats(n_heads) + (size_t)m * n_heads * S * kAttnRec) * 4 : 0;
 }
@@ -381,20 +372,15 @@ hipError_t rope_attn_kv8_launch(const void* q, const void* k, const void* v, int
                                 int tab_stride, int tab_rows, void* kc, void* vc, void* ks, void* vs, const int* slot_tab,
                                 const int* pos_tab, const int* done, const int* out_pos, void* out, int out_stride, void* ws,
                                 int n_slots, int n_heads, int n_kv, int max_seq, int S, int m, hipStream_t st) {
-    const int grp = n_heads / n_kv, hc = attn_kv8_chunk(grp);
-    const int R = hc <= 1 ? 1 : hc <= 2 ? 2 : hc <= 4 ? 4 : 8;
-    const size_t smem = attn_kv8_smem_bytes(R);
-    auto go = [&](auto kern) -> hipError_t {
-        hipLaunchKernelGGL(kern, dim3(n_kv * (grp / hc) * S, m), dim3(256), smem, st, slot_tab, pos_tab, done, out_pos, (const f16*)q,
-                           (const f16*)k, (const f16*)v, (const float*)cs, (const float*)sn, (uint8_t*)kc, (uint8_t*)vc, (float*)ks,
-                           (float*)vs, (f16*)out, (float*)ws, qkv_stride, out_stride, tab_stride, tab_rows, max_seq, n_slots, n_heads,
-                           n_kv, S, hc);
+    const int grp = n_heads / n_kv, hc = kv8_attn_chunk(grp, 1);
+    return kv8_attn_dispatch(hc, [&](auto rc) {
+        constexpr int R = decltype(rc)::value;
+        hipLaunchKernelGGL(rope_attn_kv8_kernel<R>, dim3(n_kv * (grp / hc) * S, m), dim3(256), kv8_attn_smem_bytes<1>(R), st, slot_tab,
+                           pos_tab, done, out_pos, (const f16*)q, (const f16*)k, (const f16*)v, (const float*)cs, (const float*)sn,
+                           (uint8_t*)kc, (uint8_t*)vc, (float*)ks, (float*)vs, (f16*)out, (float*)ws, qkv_stride, out_stride,
+                           tab_stride, tab_rows, max_seq, n_slots, n_heads, n_kv, S, hc);
         return hipGetLastError();
-    };
-    if (R == 1) return go(rope_attn_kv8_kernel<1>);
-    if (R == 2) return go(rope_attn_kv8_kernel<2>);
-    if (R == 4) return go(rope_attn_kv8_kernel<4>);
-    return go(rope_attn_kv8_kernel<8>);
+    });
 }
 
 }  // namespace qeft

@@ -5,7 +5,9 @@
 //                          decode_batch.hip; e4m3 cache: decode_attn_kv8.hip)
 //   attn_m_ctr_floats      the workspace layout of the m-row same-sequence attention kernels
 // The two attention kernels (rope_attn_m / rope_attn_b) are the same algorithm too, but stay written out in their files: moved
-// into shared device functions their R = 32 instantiation compiles to other code (profiles/attn_rows_refactor.log).
+// into shared device functions their R = 32 instantiation compiles to other code (profiles/attn_rows_refactor.log).  The e4m3
+// pair (rope_attn_m_kv8 / rope_attn_kv8, R <= 8) stays written out as well and shares its host side only (decode_kv8.h): every
+// cut of shared device code made the one-row kernel slower (profiles/kv8_attn_core_refactor.log).
 #pragma once
 #include "qeft_common.h"
 

@@ -7,6 +7,8 @@
 // (attn_m_ctr_floats).  What a run is, and how a wave works through it, is rope_attn_kv8_kernel's (decode_attn_kv8.hip): 16 rows of
 // 128 bytes, score role with two 16-byte K loads per lane and the K scale on the finished score, P.V role by position class with
 // the V scale folded into the exp weight, codes to fp32 by v_cvt_pk_f32_fp8, two runs in flight per wave with a fixed load count.
+// The one-row kernel is this kernel at m = 1 in a slot of its own.  The two share the host side of the launch (decode_kv8.h); their
+// device code is written out in both files, so a fix belongs in both (decode_kv8.h's header has why).
 // Cache of one layer: K codes, V codes uint8 [n_kv][max_seq][128]; K scales, V scales fp32 [n_kv][max_seq] (no slot dimension).
 // This launch's own m rows are quantised here, one wave per row (K after rotary and fp16 rounding, V as given: 2 m <= 16 rows dealt
 // over the block's 4 waves), kept in LDS as codes [8][128] x 2 and scales [8] x 2, and take the place of cache rows pos .. pos + m - 1
@@ -15,7 +17,7 @@
 #include "qeft_common.h"
 #include "decode_attn.h"      // wave_max, dpp_mov, st_agent / ld_agent, kAttnRec
 #include "decode_rows.h"      // attn_m_ctr_floats
-#include "decode_kv8.h"       // kv8_quant_row, Kv8Run, fx2
+#include "decode_kv8.h"       // kv8_quant_row, Kv8Run, fx2, the host side of the launch
 
 namespace qeft {
 
@@ -334,43 +336,19 @@ __global__ __launch_bounds__(256) void rope_attn_m_kv8_kernel(const int* __restr
     }
 }
 
-// Query rows per block (heads of a chunk x m).  Measured on the 64/8 layout against a 16-row block of the same role (302 VGPRs, one
-// block per CU): 8 rows are 1.7 - 2.4 x faster at m = 4 and 8 at every context and split (DESIGN.md §4.11 has the lines), although
-// the chunks of a kv head each re-read its runs.
-constexpr int kAttnMKv8Rows = 8;
-// heads of a chunk: the largest divisor of the group with hc * m <= kAttnMKv8Rows
-static int attn_m_kv8_chunk(int grp, int m) {
-    int hc = 1;
-    for (int d = 1; d <= grp; ++d)
-        if (grp % d == 0 && d * m <= kAttnMKv8Rows) hc = d;
-    return hc;
-}
-
-static size_t attn_m_kv8_smem_bytes(int R) {
-    return (size_t)R * 128 * 2 + 2 * 8 * 128 + 2 * 8 * 4 + 2 * 4 * R * 16 * 4 + 4 * R * 128 * 4 + 2 * 4 * R * 4;
-}
-
 hipError_t rope_attn_m_kv8_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
                                   int tab_stride, int tab_rows, void* kc, void* vc, void* ks, void* vs, const int* pos,
                                   const int* out_pos, void* out, int out_stride, void* ws, int n_heads, int n_kv, int max_seq, int S,
                                   int m, hipStream_t st) {
-    const int grp = n_heads / n_kv, hc = attn_m_kv8_chunk(grp, m), rows = hc * m;
-    const int R = rows <= 1 ? 1 : rows <= 2 ? 2 : rows <= 4 ? 4 : 8;          // rows <= 8: m <= 8 (the C entry checks it)
-    const size_t smem = attn_m_kv8_smem_bytes(R);
-    auto go = [&](auto kern) -> hipError_t {
-        if (smem > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(n_kv * (grp / hc) * S), dim3(256), smem, st, pos, out_pos, (const f16*)q, (const f16*)k,
-                           (const f16*)v, (const float*)cs, (const float*)sn, (uint8_t*)kc, (uint8_t*)vc, (float*)ks, (float*)vs,
-                           (f16*)out, (float*)ws, qkv_stride, out_stride, tab_stride, tab_rows, max_seq, n_heads, n_kv, S, m, hc);
+    const int grp = n_heads / n_kv, hc = kv8_attn_chunk(grp, m);              // hc * m <= 8: m <= 8 (the C entry checks it)
+    return kv8_attn_dispatch(hc * m, [&](auto rc) {
+        constexpr int R = decltype(rc)::value;
+        hipLaunchKernelGGL(rope_attn_m_kv8_kernel<R>, dim3(n_kv * (grp / hc) * S), dim3(256), kv8_attn_smem_bytes<8>(R), st, pos, out_pos,
+                           (const f16*)q, (const f16*)k, (const f16*)v, (const float*)cs, (const float*)sn, (uint8_t*)kc, (uint8_t*)vc,
+                           (float*)ks, (float*)vs, (f16*)out, (float*)ws, qkv_stride, out_stride, tab_stride, tab_rows, max_seq,
+                           n_heads, n_kv, S, m, hc);
         return hipGetLastError();
-    };
-    if (R == 1) return go(rope_attn_m_kv8_kernel<1>);
-    if (R == 2) return go(rope_attn_m_kv8_kernel<2>);
-    if (R == 4) return go(rope_attn_m_kv8_kernel<4>);
-    return go(rope_attn_m_kv8_kernel<8>);
+    });
 }
 
 }  // namespace qeft

@@ -117,9 +117,10 @@ def test_rope_attention_decode_vs_torch_fp32(n_heads, n_kv, steps, split):
 
 
 @pytest.mark.parametrize("ns,k,r", [((4096, 4096, 4096), 4096, 128), ((11008, 11008), 4096, 128), ((256, 64, 64), 512, 0),
-                                    ((512, 256), 11008, 128)])
+                                    ((512, 256), 11008, 128), ((264, 72, 72), 512, 128)])
 def test_grouped_gemv_equals_separate_launches(ns, k, r):
-    """q/k/v (gate/up) in one launch == the per-linear GEMV, bit for bit (same per-row arithmetic)."""
+    """q/k/v (gate/up) in one launch == the per-linear GEMV, bit for bit (same per-row arithmetic).  The MFMA form where
+    gemv_w4.hip's mfma_ok holds for every part, the VALU form otherwise (the last case: N % 16 != 0)."""
     from qeft_amd import _lib, qeft_cuda
     g = 128
     layers = [layer_to_torch(O.make_layer(n, k, r, g, seed=10 + i), DEV) for i, n in enumerate(ns)]
@@ -135,6 +136,7 @@ def test_grouped_gemv_equals_separate_launches(ns, k, r):
         x.data_ptr(), None, 0.0, len(ns), arr([l["qweight"] for l in layers]), arr([l["scales"] for l in layers]),
         arr([l["scaled_zeros"] for l in layers]), arr([l["oweight_interleaved"] for l in layers]) if r else None, None, None,
         arr(ys), (ctypes.c_int * len(ns))(*ns), k, g, r, _st()))
+    assert _lib.last_variant() == ("gemv_valu_group" if ns == (264, 72, 72) else "gemv_mfma_group"), _lib.last_variant()
     for l, n, y in zip(layers, ns, ys):
         if r:
             ref = qeft_cuda.gemv_4bit_qeft(x, l["qweight"], l["scales"], l["scaled_zeros"], l["oweight_interleaved"],
@@ -207,10 +209,12 @@ def test_fused_rmsnorm_group_equals_unfused(ns, k):
     _lib.check(lib.qeft_rmsnorm(x.data_ptr(), None, gamma.data_ptr(), None, xn.data_ptr(), 1, k, 1e-5, _st()))
     _lib.check(lib.qeft_gemv_w4_group(xn.data_ptr(), None, 0.0, len(ns), *packs, None, None, _arr(y0), nn_, k, g, r,
                                       _st()))
+    assert _lib.last_variant() == "gemv_mfma_group"
     from qeft_amd import qeft_cuda
     szp = [qeft_cuda.pack_scales(l["scales"], l["scaled_zeros"], n, k, g) for l, n in zip(layers, ns)]
     _lib.check(lib.qeft_gemv_w4_group(x.data_ptr(), gamma.data_ptr(), 1e-5, len(ns), *packs, None, _arr(szp), _arr(y1),
                                       nn_, k, g, r, _st()))
+    assert _lib.last_variant() == "gemv_mfma_group"
     torch.cuda.synchronize()
     # the fused kernel stages x * gamma and applies 1/rms to the finished dot products: one fp16 rounding per
     # activation like the unfused norm, but not the same one -- equal within the path's tolerance, not bit for bit
@@ -245,6 +249,7 @@ def test_fused_silu_down_equals_unfused(n, k):
     _lib.check(lib.qeft_gemv_w4_silu(gate.data_ptr(), up.data_ptr(), l["qweight"].data_ptr(), l["scales"].data_ptr(),
                                      l["scaled_zeros"].data_ptr(), l["oweight_interleaved"].data_ptr(), None,
                                      res.data_ptr(), szp.data_ptr(), y1.data_ptr(), n, k, g, r, _st()))
+    assert _lib.last_variant() == "gemv_mfma_silu"
     torch.cuda.synchronize()
     assert torch.equal(y0, y1)
 

@@ -34,7 +34,7 @@ def _ref(bufs, x, g):
                                      (64, 512, 128, 128), (48, 256, 0, 128), (32, 384, 128, 384), (5120, 5120, 128, 128)])
 @pytest.mark.parametrize("m", [1, 3, 7, 16, 21])
 def test_gemv_w3_vs_oracle(n, k, r, g, m):
-    from qeft_amd import qeft_cuda
+    from qeft_amd import _lib, qeft_cuda
     if n * k > 2 ** 24 and m not in (1, 7):
         pytest.skip("full-size layers: batch 1 and 7 only (oracle time)")
     bufs = O.make_layer(n, k, r, g, seed=n + k, bits=3)
@@ -44,6 +44,7 @@ def test_gemv_w3_vs_oracle(n, k, r, g, m):
     for shadow in (szp, None):
         y = qeft_cuda.gemv_3bit(torch.from_numpy(x).to(DEV), t["qweight"], t["scales"], t["scaled_zeros"],
                                 t.get("oweight_interleaved"), None, None, m, n, k, g, shadow)
+        assert _lib.last_variant() == ("gemv_w3" if m == 1 else "gemv_w3_rows"), _lib.last_variant()
         torch.cuda.synchronize()
         yref = _ref(bufs, x, g)
         assert rel_err(y.cpu().numpy(), yref) < REL_TOL
@@ -99,6 +100,7 @@ def test_w3_group_norm_and_silu_variants(ns, k):
                                       _arr([l["scales"] for l in layers]), _arr([l["scaled_zeros"] for l in layers]),
                                       _arr([l["oweight_interleaved"] for l in layers]), None, _arr(szp), _arr(ys), nn_,
                                       k, g, r, _st()))
+    assert _lib.last_variant() == "gemv_w3_group"
     torch.cuda.synchronize()
     x64 = x.cpu().numpy().astype(np.float64)[0]
     xn = x64 / np.sqrt((x64 ** 2).mean() + 1e-5) * gamma.cpu().numpy().astype(np.float64)
@@ -117,6 +119,7 @@ def test_w3_group_norm_and_silu_variants(ns, k):
     _lib.check(lib.qeft_gemv_w3_silu(gate.data_ptr(), up.data_ptr(), l["qweight"].data_ptr(), l["scales"].data_ptr(),
                                      l["scaled_zeros"].data_ptr(), l["oweight_interleaved"].data_ptr(), None,
                                      res.data_ptr(), szp[0].data_ptr(), y1.data_ptr(), n, k, g, r, _st()))
+    assert _lib.last_variant() == "gemv_w3_silu"
     torch.cuda.synchronize()
     assert torch.equal(y0, y1)
 

@@ -6,9 +6,10 @@ never consumed, so no numeric check sees them; they fault only when the operand 
 The cases below run in a child process with PYTORCH_NO_CUDA_MEMORY_CACHING=1 (every tensor its own hipMalloc, so an
 operand ends at the end of its allocation instead of somewhere inside a 2 MiB pool segment), on the shapes where the
 clamps bite: one 16-row set, K below / at / just above one step and one staging pass, last blocks with fewer row sets
-than rs_cap, batch slices, ragged GEMM tiles, and (round 2) the 256-row GEMM / dX tiles with their loader waves, the
-round-2 decode launches on their smallest shapes, the fused token tail.  Every result is also checked against the oracle, so a clamp that
-"fixes" a fault by reading the wrong bytes fails too.  Runs last (file name) and once."""
+than rs_cap, batch slices, ragged GEMM tiles, the older GEMM / dX / d(oweight) tiers on their smallest shapes, and
+(round 2) the 256-row GEMM / dX tiles with their loader waves, the round-2 decode launches on their smallest shapes, the
+fused token tail.  Every result is also checked against the oracle, so a clamp that "fixes" a fault by reading the wrong
+bytes fails too.  Runs last (file name) and once."""
 import os
 import subprocess
 import sys
@@ -42,13 +43,16 @@ def gemv(n, k, r, g, m, gather=False):
     ref = O.quant_linear(x, b["qweight"], b["scales"], b["scaled_zeros"], b.get("oweight") if r else None, None, g, reorder_ids=ids)
     assert rel_err(y.cpu().numpy(), ref.astype(np.float64)) < 1e-3, ("gemv", n, k, r, g, m)
 
-def gemm(n, k, r, g, m):
+def gemm(n, k, r, g, m, want=None):
+    """want: the variants (forward, dX, d(oweight)) the launches must report"""
     b = O.make_layer(n, k, r, g, seed=n + k + m)
     t = layer_to_torch(b, DEV)
     x = O.make_activation(m, k, r, seed=m)
     dy = (np.random.default_rng(m).standard_normal((m, n)) * 0.1).astype(np.float16)
     y = qeft_cuda.gemm_4bit_qeft(torch.from_numpy(x).to(DEV), t["qweight"], t["scales"], t["scaled_zeros"], t.get("oweight") if r else None)
+    assert want is None or _lib.last_variant() == want[0], (_lib.last_variant(), want, n, k, r, g, m)
     dx = qeft_cuda.gemm_4bit_dx(torch.from_numpy(dy).to(DEV), t["qweight"], t["scales"], t["scaled_zeros"], t.get("oweight") if r else None)
+    assert want is None or _lib.last_variant() == want[1], (_lib.last_variant(), want, n, k, r, g, m)
     torch.cuda.synchronize()
     ref = O.quant_linear(x, b["qweight"], b["scales"], b["scaled_zeros"], b.get("oweight") if r else None, None, g)
     assert rel_err(y.cpu().numpy(), ref.astype(np.float64)) < 1e-3, ("gemm", n, k, r, g, m)
@@ -56,6 +60,7 @@ def gemm(n, k, r, g, m):
     assert rel_err(dx.cpu().numpy(), dx_ref.astype(np.float64)) < 2e-3, ("dx", n, k, r, g, m)
     if r:
         dow = qeft_cuda.grad_oweight(torch.from_numpy(dy).to(DEV), torch.from_numpy(x).to(DEV), r)
+        assert want is None or _lib.last_variant() == want[2], (_lib.last_variant(), want, n, k, r, g, m)
         torch.cuda.synchronize()
         assert rel_err(dow.cpu().numpy(), dow_ref) < 1e-3, ("dow", n, k, r, g, m)
 
@@ -73,7 +78,22 @@ gemv(64, 11008, 128, 128, 7)
 # GEMM / dX / d(oweight): ragged M and N tiles, the minimum K of the DMA ring, the small-M route, split-K
 for (n, k, r, g, m) in [(136, 192, 0, 64, 129), (8, 64, 0, 64, 1), (264, 256, 128, 128, 17), (128, 1024, 128, 128, 130),
                         (520, 2048, 64, 128, 257), (256, 4096, 128, 128, 200)]:
-    gemm(n, k, r, g, m)
+    # (the first is also the 128 x 128 DMA-ring kernel at exactly its three stages: the variant is asserted there)
+    gemm(n, k, r, g, m, ("gemm_v2_128x128", "dx64", None) if (n, k, m) == (136, 192, 129) else None)
+# the other tiers underneath the loader-wave kernels, each on its smallest shape with the variant asserted
+# (tests/test_gpu_gemm_tiers.py pins them to float64 on more shapes): gemm_v1 at one k-tile (half of it outliers), the 128 x 256
+# tile, the 128-wide dX tile, and the fp32 d(oweight) kernel on rows that are no multiple of 16 bytes
+for (n, k, r, g, m, want) in [(8, 64, 32, 32, 65, ("gemm_v1", "dx64", "grad_oweight_mfma")),
+                              (4096, 256, 0, 64, 2048, ("gemm_v2_128x256", "dx64+split", None)),
+                              (64, 4096, 0, 128, 2048, ("gemm_v3_128x128+splitk", "dx128", None))]:
+    gemm(n, k, r, g, m, want)
+for (m, n, k, r) in [(64, 128, 100, 8), (1, 8, 64, 3)]:
+    xx = O.make_activation(m, k, r, seed=m)
+    dd = (np.random.default_rng(m).standard_normal((m, n)) * 0.1).astype(np.float16)
+    dow = qeft_cuda.grad_oweight(torch.from_numpy(dd).to(DEV), torch.from_numpy(xx).to(DEV), r)
+    assert _lib.last_variant() == "grad_oweight_fma", (_lib.last_variant(), m, n, k, r)
+    torch.cuda.synchronize()
+    assert rel_err(dow.cpu().numpy(), dd.astype(np.float64).T @ xx[:, k - r:].astype(np.float64)) < 1e-3, ("dow fma", m, n, k, r)
 # ---- round 2: the 256-row GEMM / dX tiles (loader waves: DMA pieces, the register ring of packed weights, the outlier k-tile's
 # direct DMA), ragged M / N, every remainder class of the dX loader's ring
 import types

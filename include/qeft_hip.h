@@ -478,7 +478,34 @@ int qeft_attn_prefill_kv8(const void* q, int q_stride, const void* k_codes, cons
 long long qeft_attn_prefill_kv8_check_extents(int q_stride, int kv_rows, int new_stride, int out_stride, int start, int t, int n_heads,
                                               int n_kv_heads);
 
-/* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py).  A parameter record is int32 [8] in device memory:
+/* Fused lm_head + cross-entropy pieces (csrc/lm_head_nll.hip; qeft_amd/scoring.py: lm_head_nll, score, eval_nll; DESIGN.md
+ * section 4.13).  x: fp16 [t][hidden], the final-norm output rows, x_stride elements apart; weight: fp16 [vocab][hidden]
+ * contiguous, the checkpoint's lm_head.weight; targets: int32 [t], or NULL.  logit_ij = sum_k x_ik w_jk is accumulated in fp32 by
+ * MFMA and never rounded to fp16 or stored: no [t][vocab] array exists.  Per row i:
+ *   lse[i]       = log sum_j exp(logit_ij)   (fp32; max-shifted, so finite for any finite logits);
+ *   tgt_logit[i] = logit at targets[i]; a target outside [0, vocab) (-100, the reference's IGNORE_INDEX, among them) is ignored
+ *                  and gives 0.0; with NULL targets tgt_logit is not touched and may be NULL;
+ *   argmax[i]    = the lowest index among equal maxima, as qeft_token_end's (int32); argmax may be NULL.
+ * A row's three results depend on that row and the weight alone, bit for bit: not on t, on the row's index in the launch, on
+ * x_stride or on the grid.  The vocabulary is cut into column tiles at absolute multiples of 128; each (row, tile) leaves one
+ * partial {max, sum exp(l - max), first argmax} in `workspace` (12 bytes x t x ceil(vocab / 128), qeft_lm_head_nll_workspace_bytes)
+ * and a second launch folds a row's partials in ascending tile order; no atomics, no arrival order.  The workspace needs no
+ * initialisation and holds nothing between calls.
+ * t >= 1, hidden % 64 == 0, hidden >= 64, vocab >= 1, x_stride % 8 == 0, x_stride >= hidden, a workspace of at least
+ * qeft_lm_head_nll_workspace_bytes(t, vocab) bytes (t <= 2^20, vocab <= 2^24, hidden <= 2^16): QEFT_ERR_SHAPE otherwise, before any
+ * pointer is looked at; then QEFT_ERR_NULL (x, weight, lse, workspace; tgt_logit when targets is given), then QEFT_ERR_ALIGN
+ * (x, weight, workspace 16-byte aligned; targets and the outputs 4-byte aligned).  t is a host integer; no host synchronisation,
+ * capturable into a graph.  Rows >= t and columns >= vocab of the last tiles are read from the clamped row / column, never past
+ * an operand's end, and never stored.
+ * qeft_lm_head_nll_workspace_bytes: 0 for a t or vocab the entry refuses.
+ * qeft_lm_head_nll_check_extents: CPU-only -- enumerates every global address the two launches would form and returns the largest
+ * number of bytes by which one passes the end of its operand, 0 when none does (-1 for arguments the entry refuses). */
+long long qeft_lm_head_nll_workspace_bytes(int t, int vocab);
+int qeft_lm_head_nll(const void* x, int x_stride, const void* weight, const int* targets, float* lse, float* tgt_logit, int* argmax,
+                     void* workspace, long long workspace_bytes, int t, int hidden, int vocab, qeft_stream_t stream);
+long long qeft_lm_head_nll_check_extents(int x_stride, int t, int hidden, int vocab);
+
+/* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py). A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;
  *     otherwise weights w = exp((l - max l) / T) in fp32 (NaN: weight 0, never drawn; -0 == +0);

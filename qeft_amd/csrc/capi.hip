@@ -89,6 +89,10 @@ long long prefill_attn_count_out_of_range(const PaGeom& G);
 hipError_t prefill_attn_kv8_launch(const void* q, const void* kq, const void* vq, const void* ksc, const void* vsc, const void* kn,
                                    const void* vn, void* out, const Pa8Geom& G8, hipStream_t st);   // prefill_attn_kv8.hip
 long long prefill_attn_kv8_count_out_of_range(const Pa8Geom& G8);
+size_t lm_head_nll_workspace_bytes(int t, int vocab);                                                                 // lm_head_nll.hip
+hipError_t lm_head_nll_launch(const void* x, const void* w, const int* targets, float* lse, float* tgt_logit, int* argmax, void* ws,
+                              int x_stride, int t, int hidden, int vocab, hipStream_t st);
+long long lm_head_nll_count_out_of_range(int x_stride, int t, int hidden, int vocab);
 hipError_t sample_launch(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens,  // decode_sample.hip
                          hipStream_t st);
 hipError_t token_end_sample_launch(const void* logits, void* tok, int* pos, const int* params, int vocab, hipStream_t st);
@@ -1162,6 +1166,35 @@ long long qeft_attn_prefill_kv8_check_extents(int q_stride, int kv_rows, int new
     qeft::Pa8Geom G8{};
     if (prefill_kv8_geom(G8, q_stride, kv_rows, new_stride, out_stride, start, t, n_heads, n_kv_heads) != QEFT_OK) return -1;
     return qeft::prefill_attn_kv8_count_out_of_range(G8);
+}
+
+// ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)
+static bool lm_head_nll_shape_ok(int x_stride, int t, int hidden, int vocab) {
+    if (t < 1 || t > (1 << 20) || vocab < 1 || vocab > (1 << 24) || hidden < 64 || hidden % 64 != 0 || hidden > (1 << 16)) return false;
+    if (x_stride % 8 != 0 || x_stride < hidden || x_stride > (1 << 24)) return false;
+    return ((long long)(t + 63) / 64) * ((vocab + 127) / 128) < (1ll << 31);          // the grid of the 64-row tile
+}
+
+long long qeft_lm_head_nll_workspace_bytes(int t, int vocab) {
+    if (!lm_head_nll_shape_ok(64, t, 64, vocab)) return 0;
+    return (long long)qeft::lm_head_nll_workspace_bytes(t, vocab);
+}
+
+int qeft_lm_head_nll(const void* x, int x_stride, const void* weight, const int* targets, float* lse, float* tgt_logit, int* argmax,
+                     void* workspace, long long workspace_bytes, int t, int hidden, int vocab, qeft_stream_t stream) {
+    if (!lm_head_nll_shape_ok(x_stride, t, hidden, vocab)) return QEFT_ERR_SHAPE;
+    if (workspace_bytes < (long long)qeft::lm_head_nll_workspace_bytes(t, vocab)) return QEFT_ERR_SHAPE;
+    if (!x || !weight || !lse || !workspace || (targets && !tgt_logit)) return QEFT_ERR_NULL;
+    if (!aligned16(x) || !aligned16(weight) || !aligned16(workspace) || ((uintptr_t)targets & 3) || ((uintptr_t)lse & 3) ||
+        ((uintptr_t)tgt_logit & 3) || ((uintptr_t)argmax & 3))
+        return QEFT_ERR_ALIGN;
+    return finish(qeft::lm_head_nll_launch(x, weight, targets, lse, tgt_logit, argmax, workspace, x_stride, t, hidden, vocab,
+                                           (hipStream_t)stream));
+}
+
+long long qeft_lm_head_nll_check_extents(int x_stride, int t, int hidden, int vocab) {
+    if (!lm_head_nll_shape_ok(x_stride, t, hidden, vocab)) return -1;
+    return qeft::lm_head_nll_count_out_of_range(x_stride, t, hidden, vocab);
 }
 
 // ---- sampled token end (decode_sample.hip)

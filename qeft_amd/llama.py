@@ -10,7 +10,8 @@ C-ABI launches on static buffers so the whole step can be captured into one hipG
             -> [gate|up] grouped GEMV (post-attention RMSNorm fused) -> down_proj GEMV (silu*mul fused, +residual)
 
 `QuantLlama.forward_dense_reference` is a plain fp32 PyTorch implementation over the dense dequantised weights,
-used by the tests and by `eval_nll` as the parity target ("PPL vs reference" on synthetic weights).
+used by the tests as the parity target ("PPL vs reference" on synthetic weights; the perplexity protocol itself is
+`qeft_amd.scoring.eval_nll`).
 """
 import ctypes
 import os
@@ -174,7 +175,7 @@ class QuantLlama(nn.Module):
     def from_packed(cls, checkpoint_path, device="cuda:0", max_seq=512, rms_eps=1e-5, rope_theta=10000.0, name=None,
                     n_heads=None, n_kv_heads=None, unsafe_pickle=False):
         """A packed checkpoint in the reference's on-disk format (save_model, qeft/utils/modelutils.py:248-268) as a QuantLlama
-        the DecodeEngine / prefill / eval_nll run on -- the counterpart of load_owqmodel (modelutils.py:147-183) feeding the
+        the DecodeEngine / prefill / scoring.eval_nll run on -- the counterpart of load_owqmodel (modelutils.py:147-183) feeding the
         reference's decode benchmark (qeft/main.py:310-371, 510-553).  The state dict carries HF's LlamaForCausalLM keys
         (`model.embed_tokens.weight`, `model.layers.i.self_attn.q_proj.qweight` ..., `model.layers.i.input_layernorm.weight`,
         `model.norm.weight`, `lm_head.weight`); the shape is read off the tensors (head_dim 128: Llama-2 7B / 13B; HF hub
@@ -416,7 +417,7 @@ def _own_attention(kv, li, q, k, v, start, T, n_heads, n_kv):
 
 
 @torch.no_grad()
-def prefill(model: "QuantLlama", tokens, engine=None, *, start=0, attn=None, chunk=None):
+def prefill(model: "QuantLlama", tokens, engine=None, *, start=0, attn=None, chunk=None, _head=True):
     """Batched forward over T prompt tokens through the packed QuantLinears: T >= 8 rows take the MFMA GEMM path
     (fused outlier slice; BASELINE config 3).  Returns fp16 logits [T, vocab].  With `engine` (a DecodeEngine of the same model)
     the rotated keys and the values are written into its KV caches at positions [start, start + T) and its position is set to
@@ -426,7 +427,9 @@ def prefill(model: "QuantLlama", tokens, engine=None, *, start=0, attn=None, chu
     cache (without an engine, over a transient image of the prompt's rows).  None: "sdpa" at start == 0, "own" at start > 0.
     start > 0 continues a cached sequence (ftllama_modeling.py:87-125, q_len > 8 at start_pos > 0): it needs the engine whose
     caches hold positions [0, start).  chunk=C runs the prompt as consecutive pieces of at most C tokens on the own kernel, each
-    starting where the previous one ended; the logits are the pieces' concatenated."""
+    starting where the previous one ended; the logits are the pieces' concatenated.
+    (_head=False is scoring.score's hook: the same pass, caches and position, returning the final-norm rows [T, hidden] that
+    the lm_head would multiply, the pieces of a chunked prompt concatenated the same way.)"""
     s = model.shape
     T, start = tokens.numel(), int(start)
     if attn not in (None, "sdpa", "own"):
@@ -448,13 +451,14 @@ def prefill(model: "QuantLlama", tokens, engine=None, *, start=0, attn=None, chu
         raise ValueError("start > 0 continues a cached sequence: pass the engine that holds positions [0, start)")
     assert start + T <= s.max_seq and (engine is None or engine.P == 1), "prefill hands over to a single-GPU engine"
     if chunk is None or T <= chunk:
-        return _prefill_pass(model, tokens, engine, start, attn)
+        return _prefill_pass(model, tokens, engine, start, attn, _head)
     kv = engine if engine is not None else _TransientKV(model, T, per_layer=True)
-    return torch.cat([_prefill_pass(model, tokens[a:a + chunk], kv, start + a, "own") for a in range(0, T, chunk)])
+    return torch.cat([_prefill_pass(model, tokens[a:a + chunk], kv, start + a, "own", _head) for a in range(0, T, chunk)])
 
 
-def _prefill_pass(model, tokens, engine, start, attn):
-    """One pass of prefill(): T tokens at positions [start, start + T)."""
+def _prefill_pass(model, tokens, engine, start, attn, head=True):
+    """One pass of prefill(): T tokens at positions [start, start + T).  head=False: the final-norm rows hn (fp16 [T, hidden])
+    instead of their product with the lm_head (scoring.score feeds them to qeft_lm_head_nll)."""
     s = model.shape
     T = tokens.numel()
     h = model.model.embed_tokens.weight[tokens]                       # [T, hidden] fp16
@@ -516,6 +520,8 @@ def _prefill_pass(model, tokens, engine, start, attn):
     if engine is not None:
         engine.set_position(start + T)
     _, hn = _add_rmsnorm(h, delta, model.model.norm.weight, s.rms_eps)
+    if not head:
+        return hn
     return torch.matmul(hn, model.lm_head.weight.t())
 
 

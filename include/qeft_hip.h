@@ -505,6 +505,34 @@ int qeft_lm_head_nll(const void* x, int x_stride, const void* weight, const int*
                      void* workspace, long long workspace_bytes, int t, int hidden, int vocab, qeft_stream_t stream);
 long long qeft_lm_head_nll_check_extents(int x_stride, int t, int hidden, int vocab);
 
+/* Backward of the fused head with respect to x (csrc/lm_head_nll_grad.hip; qeft_amd/scoring.py: lm_head_nll_loss;
+ * qeft_amd/finetune.py: causal_lm_loss).  x, weight, targets as in qeft_lm_head_nll (targets required);
+ * lse: fp32 [t], qeft_lm_head_nll's own output; grad_nll: fp32 [t], the gradient arriving at nll_i = lse_i - tgt_logit_i;
+ * dx: [t][hidden], rows dx_stride elements apart, fp16, or fp32 when dx_fp32 != 0.  For a row with a target in [0, vocab)
+ *   dx[i][k] = grad_nll[i] * sum_j (p_ij - [j == targets[i]]) * weight[j][k],   p_ij = exp(logit_ij - lse[i]);
+ * a row with an ignored target gets +0.0 in every element whatever grad_nll[i] holds.  The lm_head is frozen in QEFT: there is
+ * no d(weight).  Rows are taken in chunks of R = qeft_lm_head_nll_grad_chunk_rows (1024); per chunk launch A recomputes the
+ * forward's fp32 logits (the same loop, bit for bit) and writes g = fp16(p - onehot), rounded once, as [rows][vocab rounded up
+ * to 128] into `workspace`; launch B forms g W with fp32 MFMA accumulators over the whole vocabulary in ascending order, reading
+ * weight where it lies (no transposed copy), multiplies by grad_nll in fp32 and writes fp32 or rounds once to fp16: the fp16
+ * output is the rounding of the fp32 output, bit for bit.  No atomics, no arrival order: a row of dx depends on that row of x,
+ * its lse, target and grad_nll and on the weight alone, bit for bit -- not on t, the row's index or chunk, a stride or the grid.
+ * The forward's shape rules, dx_stride % 8 == 0, dx_stride >= hidden and a workspace of at least
+ * qeft_lm_head_nll_grad_workspace_bytes(t, hidden, vocab) = 2 * min(t, R) * round_up(vocab, 128) bytes: QEFT_ERR_SHAPE otherwise,
+ * before any pointer is looked at; then QEFT_ERR_NULL (every pointer is required), then QEFT_ERR_ALIGN (x, weight, dx, workspace
+ * 16-byte aligned; targets, lse, grad_nll 4-byte aligned).  The workspace needs no initialisation and holds nothing between
+ * calls.  No host synchronisation, capturable into a graph.  Rows and columns past an operand's end are read from the clamped
+ * row / column and never stored.
+ * qeft_lm_head_nll_grad_workspace_bytes: 0 for arguments the entry refuses.
+ * qeft_lm_head_nll_grad_check_extents: CPU-only, as qeft_lm_head_nll_check_extents, in elements, over every launch of every
+ * chunk (-1 for arguments the entry refuses). */
+int qeft_lm_head_nll_grad_chunk_rows(int hidden, int vocab);
+long long qeft_lm_head_nll_grad_workspace_bytes(int t, int hidden, int vocab);
+int qeft_lm_head_nll_grad(const void* x, int x_stride, const void* weight, const int* targets, const float* lse,
+                          const float* grad_nll, void* dx, int dx_stride, int dx_fp32, void* workspace, long long workspace_bytes,
+                          int t, int hidden, int vocab, qeft_stream_t stream);
+long long qeft_lm_head_nll_grad_check_extents(int x_stride, int dx_stride, int t, int hidden, int vocab);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py). A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

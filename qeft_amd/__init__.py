@@ -1,13 +1,18 @@
-"""QEFT on AMD: packed QuantLinear, the decode engines, prefill and scoring over hand-written gfx950 kernels.
+"""QEFT on AMD: packed QuantLinear, the decode engines, prefill, scoring and the training loss over hand-written gfx950 kernels.
 
-The scoring entry points are exported here; they resolve on first use, so that `import qeft_amd` (and `qeft_amd.build`, which
-runs before the library exists) stays free of torch and of the HIP library.
+The scoring and fine-tuning entry points are exported here; they resolve on first use, so that `import qeft_amd` (and
+`qeft_amd.build`, which runs before the library exists) stays free of torch and of the HIP library.
 """
-__all__ = ["score", "eval_nll", "lm_head_nll"]
+_SCORING = ("score", "eval_nll", "lm_head_nll", "lm_head_nll_loss")
+_FINETUNE = ("causal_lm_loss", "shift_labels")           # qeft_amd.finetune also has begin(model) / end(model)
+__all__ = [*_SCORING, *_FINETUNE]
 
 
 def __getattr__(name):
-    if name in __all__:
+    if name in _SCORING:
         from . import scoring
         return getattr(scoring, name)
+    if name in _FINETUNE:
+        from . import finetune
+        return getattr(finetune, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -92,6 +92,10 @@ SIGNATURES = {
     "qeft_lm_head_nll_workspace_bytes": [_i, _i],
     "qeft_lm_head_nll": [_p, _i, _p, _p, _p, _p, _p, _p, ctypes.c_longlong, _i, _i, _i, _p],
     "qeft_lm_head_nll_check_extents": [_i, _i, _i, _i],
+    "qeft_lm_head_nll_grad_chunk_rows": [_i, _i],
+    "qeft_lm_head_nll_grad_workspace_bytes": [_i, _i, _i],
+    "qeft_lm_head_nll_grad": [_p, _i, _p, _p, _p, _p, _p, _i, _i, _p, ctypes.c_longlong, _i, _i, _i, _p],
+    "qeft_lm_head_nll_grad_check_extents": [_i, _i, _i, _i, _i],
     "qeft_token_end_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "qeft_sample": [_p, _i, _i, _p, _p, _p, _p],
     "qeft_token_end_sample": [_p, _p, _p, _i, _p, _p],
@@ -138,6 +142,8 @@ def lib():
                                                        "qeft_gemv_v3_check_extents_m", "qeft_attn_prefill_check_extents",
                                                        "qeft_attn_prefill_kv8_check_extents",
                                                        "qeft_lm_head_nll_workspace_bytes", "qeft_lm_head_nll_check_extents",
+                                                       "qeft_lm_head_nll_grad_workspace_bytes",
+                                                       "qeft_lm_head_nll_grad_check_extents",
                                                        "qeft_oneshot_mailbox_bytes") else _i)
         _lib = l
     return _lib

@@ -93,6 +93,11 @@ size_t lm_head_nll_workspace_bytes(int t, int vocab);                           
 hipError_t lm_head_nll_launch(const void* x, const void* w, const int* targets, float* lse, float* tgt_logit, int* argmax, void* ws,
                               int x_stride, int t, int hidden, int vocab, hipStream_t st);
 long long lm_head_nll_count_out_of_range(int x_stride, int t, int hidden, int vocab);
+int lm_head_nll_grad_chunk_rows();                                                                                    // lm_head_nll_grad.hip
+size_t lm_head_nll_grad_workspace_bytes(int t, int vocab);
+hipError_t lm_head_nll_grad_launch(const void* x, const void* w, const int* targets, const float* lse, const float* grad_nll, void* dx,
+                                   void* ws, int x_stride, int dx_stride, int dx_fp32, int t, int hidden, int vocab, hipStream_t st);
+long long lm_head_nll_grad_count_out_of_range(int x_stride, int dx_stride, int t, int hidden, int vocab);
 hipError_t sample_launch(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens,  // decode_sample.hip
                          hipStream_t st);
 hipError_t token_end_sample_launch(const void* logits, void* tok, int* pos, const int* params, int vocab, hipStream_t st);
@@ -1195,6 +1200,41 @@ int qeft_lm_head_nll(const void* x, int x_stride, const void* weight, const int*
 long long qeft_lm_head_nll_check_extents(int x_stride, int t, int hidden, int vocab) {
     if (!lm_head_nll_shape_ok(x_stride, t, hidden, vocab)) return -1;
     return qeft::lm_head_nll_count_out_of_range(x_stride, t, hidden, vocab);
+}
+
+// ---- backward of the fused lm_head + cross-entropy (lm_head_nll_grad.hip)
+static bool lm_head_nll_grad_shape_ok(int x_stride, int dx_stride, int t, int hidden, int vocab) {
+    if (!lm_head_nll_shape_ok(x_stride, t, hidden, vocab)) return false;
+    return dx_stride % 8 == 0 && dx_stride >= hidden && dx_stride <= (1 << 24);
+}
+
+int qeft_lm_head_nll_grad_chunk_rows(int hidden, int vocab) {
+    (void)hidden;
+    (void)vocab;
+    return qeft::lm_head_nll_grad_chunk_rows();
+}
+
+long long qeft_lm_head_nll_grad_workspace_bytes(int t, int hidden, int vocab) {
+    if (!lm_head_nll_grad_shape_ok(hidden, hidden, t, hidden, vocab)) return 0;
+    return (long long)qeft::lm_head_nll_grad_workspace_bytes(t, vocab);
+}
+
+int qeft_lm_head_nll_grad(const void* x, int x_stride, const void* weight, const int* targets, const float* lse,
+                          const float* grad_nll, void* dx, int dx_stride, int dx_fp32, void* workspace, long long workspace_bytes,
+                          int t, int hidden, int vocab, qeft_stream_t stream) {
+    if (!lm_head_nll_grad_shape_ok(x_stride, dx_stride, t, hidden, vocab)) return QEFT_ERR_SHAPE;
+    if (workspace_bytes < (long long)qeft::lm_head_nll_grad_workspace_bytes(t, vocab)) return QEFT_ERR_SHAPE;
+    if (!x || !weight || !targets || !lse || !grad_nll || !dx || !workspace) return QEFT_ERR_NULL;
+    if (!aligned16(x) || !aligned16(weight) || !aligned16(dx) || !aligned16(workspace) || ((uintptr_t)targets & 3) ||
+        ((uintptr_t)lse & 3) || ((uintptr_t)grad_nll & 3))
+        return QEFT_ERR_ALIGN;
+    return finish(qeft::lm_head_nll_grad_launch(x, weight, targets, lse, grad_nll, dx, workspace, x_stride, dx_stride, dx_fp32 != 0, t,
+                                                hidden, vocab, (hipStream_t)stream));
+}
+
+long long qeft_lm_head_nll_grad_check_extents(int x_stride, int dx_stride, int t, int hidden, int vocab) {
+    if (!lm_head_nll_grad_shape_ok(x_stride, dx_stride, t, hidden, vocab)) return -1;
+    return qeft::lm_head_nll_grad_count_out_of_range(x_stride, dx_stride, t, hidden, vocab);
 }
 
 // ---- sampled token end (decode_sample.hip)

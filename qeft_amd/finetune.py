@@ -1,0 +1,132 @@
+"""The training step the project is named after: a causal-LM loss over a packed model whose only trainable parameters are the
+fp16 outlier slices (`oweight`) of its QuantLinears.
+
+The reference's finetune.py freezes every parameter except `*oweight*` and trains them through HF's LlamaForCausalLM loss
+(cutoff_len 2048, labels of -100, gradient checkpointing).  Here:
+
+    params = begin(model)                       every QuantLinear in training mode; the fp32 oweight parameters
+    loss = causal_lm_loss(model, tokens, labels)
+    loss.backward()                             dX / d(oweight) kernels per linear, qeft_lm_head_nll_grad at the head
+    ... an optimiser of the caller's over params ...
+    end(model)                                  back to inference: prefill, score and a new DecodeEngine see the trained weights
+
+causal_lm_loss is a differentiable pass of its own (llama._prefill_pass, the inference route, is not touched): the linears and
+the head run the project's kernels; norms, rotary, attention and the activation are torch ops.  The activations are fp16, so a
+caller scales the loss against underflow themselves -- `(loss * s).backward()`, then divide the fp32 gradients by s; the head's
+backward takes the scale in fp32 and keeps its softmax - onehot unscaled, so no scale makes it overflow or underflow there.
+The optimiser loop and Trainer plumbing are out of scope.
+"""
+import torch
+from torch.utils.checkpoint import checkpoint as _checkpoint
+
+from . import scoring
+from .llama import layer_linears
+
+IGNORE_INDEX = scoring.IGNORE_INDEX
+
+
+def _linears(model):
+    for L in model.model.layers:
+        for _, ql in layer_linears(L):
+            yield ql
+
+
+def begin(model):
+    """Put every QuantLinear into training mode (set_for_wct(), set_kernel(training=True)) and return the trainable parameters:
+    the oweight slices, fp32 with requires_grad.  Everything else stays frozen."""
+    params = []
+    for ql in _linears(model):
+        ql.set_for_wct()
+        ql.set_kernel(training=True)
+        if ql.outlierfeatures > 0:
+            params.append(ql.oweight)
+    return params
+
+
+def end(model):
+    """Back to inference after training: the interleaved copies the decode GEMV reads are re-derived, the prefill operands are
+    dropped (rebuilt on the next prompt) and the model's oweight version is bumped as checkpoint.replace_oweight does, so a
+    DecodeEngine built before refuses to run and a new one streams the trained weights."""
+    for ql in _linears(model):
+        ql.refresh_interleaved()
+        ql.set_kernel(False)
+    model._prefill_ops = None
+    model._oweight_version = getattr(model, "_oweight_version", 0) + 1
+
+
+def shift_labels(tokens, labels=None):
+    """HF's rule for a causal LM: row i is scored against labels[i + 1], the last row of every sequence is ignored.  tokens /
+    labels [T] or [B, T]; labels default to the tokens.  Returns int32 of the same shape."""
+    labels = tokens if labels is None else labels
+    if labels.shape != tokens.shape:
+        raise ValueError(f"labels {tuple(labels.shape)} for tokens {tuple(tokens.shape)}")
+    out = torch.full(labels.shape, IGNORE_INDEX, dtype=torch.int32, device=labels.device)
+    out[..., :-1] = labels[..., 1:].to(torch.int32)
+    return out
+
+
+def _rmsnorm(x, gamma, eps):
+    xf = x.float()
+    return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * gamma.float()).half()
+
+
+def _rope(x, cos, sin):
+    """x [B, T, H, 128] fp16, cos / sin [T, 1, 64] fp32 -> rotated fp16 (fp32 math), the pairing of llama._prefill_pass."""
+    a, b = x[..., :64].float(), x[..., 64:].float()
+    return torch.cat([a * cos - b * sin, b * cos + a * sin], dim=-1).half()
+
+
+def _decoder_layer(h, L, s, B, T, cos, sin):
+    """h [B * T, hidden] fp16 -> the layer's output, fp16; every linear is the module's own forward (training mode: the MFMA
+    forward, dX and d(oweight) kernels; o_proj gathers its own column order)."""
+    at, mlp = L.self_attn, L.mlp
+    x = _rmsnorm(h, L.input_layernorm.weight, s.rms_eps)
+    q = _rope(at.q_proj(x).view(B, T, s.n_heads, 128), cos, sin)
+    k = _rope(at.k_proj(x).view(B, T, s.n_kv_heads, 128), cos, sin)
+    v = at.v_proj(x).view(B, T, s.n_kv_heads, 128)
+    rep = s.n_heads // s.n_kv_heads
+    if rep != 1:
+        k, v = k.repeat_interleave(rep, 2), v.repeat_interleave(rep, 2)
+    a = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True)
+    h = h + at.o_proj(a.transpose(1, 2).reshape(B * T, s.hidden))
+    x = _rmsnorm(h, L.post_attention_layernorm.weight, s.rms_eps)
+    act = (torch.nn.functional.silu(mlp.gate_proj(x).float()) * mlp.up_proj(x).float()).half()
+    return h + mlp.down_proj(act)
+
+
+def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused"):
+    """Mean NLL (fp32 scalar) of the shifted labels under `model`, differentiable with respect to the oweight parameters that
+    begin(model) returned.  tokens [T] or [B, T] (right-padded; label the padding -100), labels as shift_labels takes them; a
+    label outside [0, vocab) is ignored, and the mean runs over the others (0 when there is none).  Every sequence starts at
+    position 0.  checkpoint=True recomputes each decoder layer in the backward (torch.utils.checkpoint, use_reentrant=False), as
+    the reference's gradient checkpointing does.  head="fused": scoring.lm_head_nll_loss, no [T, vocab] tensor in either
+    direction; head="torch": hn @ W.t() -> fp32 -> cross_entropy, the route the fused head is measured against.
+    fp16 activations: scale the loss yourself, `(loss * s).backward()`."""
+    if head not in ("fused", "torch"):
+        raise ValueError(f"head must be 'fused' or 'torch', got {head!r}")
+    s = model.shape
+    dev = model.lm_head.weight.device
+    tokens = tokens.to(dev)
+    if tokens.dim() not in (1, 2):
+        raise ValueError(f"tokens must be [T] or [B, T], got {tuple(tokens.shape)}")
+    targets = shift_labels(tokens, None if labels is None else labels.to(dev)).reshape(-1)
+    tok2 = tokens.reshape(-1, tokens.shape[-1])
+    B, T = tok2.shape
+    if T > s.max_seq:
+        raise ValueError(f"{T} tokens exceed the model's max_seq {s.max_seq}")
+    cos, sin = model.rope_cos[:T, None, :], model.rope_sin[:T, None, :]
+    h = model.model.embed_tokens.weight[tok2.reshape(-1)]              # [B * T, hidden] fp16
+    for L in model.model.layers:
+        if checkpoint:
+            h = _checkpoint(_decoder_layer, h, L, s, B, T, cos, sin, use_reentrant=False)
+        else:
+            h = _decoder_layer(h, L, s, B, T, cos, sin)
+    hn = _rmsnorm(h, model.model.norm.weight, s.rms_eps)
+    W = model.lm_head.weight
+    ok = (targets >= 0) & (targets < s.vocab)
+    n = ok.sum().clamp_min(1).to(torch.float32)
+    if head == "fused":
+        return scoring.lm_head_nll_loss(hn, W, targets).sum() / n
+    logits = torch.matmul(hn, W.t()).float()
+    lab = torch.where(ok, targets, torch.full_like(targets, IGNORE_INDEX)).long()
+    return torch.nn.functional.cross_entropy(logits, lab, ignore_index=IGNORE_INDEX, reduction="sum") / n

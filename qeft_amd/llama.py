@@ -271,7 +271,7 @@ class QuantLlama(nn.Module):
             for n, ql in layer_linears(L):
                 qw = ql._qweight4().clone() if ql.bits == 3 else ql.qweight
                 d[n] = qeft_cuda.dequantize_weight_4bit_qeft(qw, ql.scales, ql.scaled_zeros,
-                                                             ql.oweight if ql.outlierfeatures else None).float()
+                                                             ql._outlier_weight_f16() if ql.outlierfeatures else None).float()
             out.append(d)
         return out
 

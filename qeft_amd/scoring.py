@@ -8,6 +8,8 @@ log-sum-exp, target logit and argmax: fp32 logits that never pass through fp16, 
     score(model, tokens)        per-token log-probabilities of a document (optionally on an engine's cache, in chunks)
     eval_nll(model, tokens)     the reference's perplexity protocol over windows of `seqlen` tokens
     lm_head_nll(hn, weight)     the kernel's thin wrapper
+    lm_head_nll_loss(hn, weight, targets)   the same head as a differentiable per-row NLL (section 4.14): the backward is
+                                qeft_lm_head_nll_grad, again without a [T, vocab] tensor; finetune.causal_lm_loss ends in it
 """
 import math
 from dataclasses import dataclass
@@ -20,6 +22,7 @@ IGNORE_INDEX = -100          # the reference's label for "no loss here" (any tar
 _QEFT_ERR_SHAPE = 2
 
 _workspace = {}              # device -> uint8 buffer, grown on demand; one stream at a time uses it (as the engines' buffers)
+_grad_workspace = {}         # the same for qeft_lm_head_nll_grad: at most chunk_rows rows of g, whatever T
 
 
 @dataclass
@@ -87,6 +90,93 @@ def lm_head_nll(hn, weight, targets=None):
         return _lm_head_nll_torch(hn, weight, targets)
     _lib.check(code)
     return lse, tgt, argmax
+
+
+def _nll_torch(hn, weight, targets):
+    """nll [T] in fp32 by differentiable torch ops, for a width the entries do not take.  It does build the [T, vocab] logits."""
+    logits = hn.float() @ weight.float().t()
+    vocab = logits.shape[1]
+    ok = (targets >= 0) & (targets < vocab)
+    got = logits.gather(1, targets.clamp(0, vocab - 1).long()[:, None])[:, 0]
+    nll = torch.logsumexp(logits, dim=1) - got
+    return torch.where(ok, nll, torch.zeros_like(nll))
+
+
+def _entry_view(hn, hidden):
+    """hn as the entries take it: unit column stride, rows a multiple of 8 elements apart, 16-byte aligned."""
+    if hn.stride(1) != 1 or hn.stride(0) % 8 != 0 or hn.stride(0) < hidden or hn.data_ptr() % 16 != 0:
+        hn = hn.contiguous()
+    return hn
+
+
+@torch.no_grad()
+def lm_head_nll_grad(hn, weight, targets, lse, grad_nll, fp32=False):
+    """d(sum_i grad_nll_i nll_i) / d hn through qeft_lm_head_nll_grad (include/qeft_hip.h): hn, weight, targets as lm_head_nll's,
+    lse its first result, grad_nll fp32 [T] -> fp16 [T, hidden] (fp32 with fp32=True); rows with an ignored target are +0.0.
+    The workspace is cached per device and holds at most chunk_rows rows of g."""
+    T, hidden = hn.shape
+    vocab = weight.shape[0]
+    dev = hn.device
+    lib = _lib.lib()
+    need = lib.qeft_lm_head_nll_grad_workspace_bytes(T, hidden, vocab)
+    if need == 0:
+        raise ValueError(f"qeft_lm_head_nll_grad does not take T={T}, hidden={hidden}, vocab={vocab}")
+    hn = _entry_view(hn, hidden)
+    weight = weight.contiguous()
+    targets = targets.to(device=dev, dtype=torch.int32).contiguous()
+    lse = lse.to(device=dev, dtype=torch.float32).contiguous()
+    grad_nll = grad_nll.to(device=dev, dtype=torch.float32).contiguous()
+    ws = _grad_workspace.get(dev)
+    if ws is None or ws.numel() < need:
+        _grad_workspace[dev] = None
+        ws = _grad_workspace[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    dx = torch.empty(T, hidden, dtype=torch.float32 if fp32 else torch.float16, device=dev)
+    _lib.check(lib.qeft_lm_head_nll_grad(hn.data_ptr(), hn.stride(0), weight.data_ptr(), targets.data_ptr(), lse.data_ptr(),
+                                         grad_nll.data_ptr(), dx.data_ptr(), hidden, int(fp32), ws.data_ptr(), ws.numel(), T, hidden,
+                                         vocab, torch.cuda.current_stream(dev).cuda_stream))
+    return dx
+
+
+class _LmHeadNllLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hn, weight, targets):
+        # rows are independent bit for bit (section 4.13), so the forward runs in pieces of the backward's chunk: neither
+        # workspace grows with T
+        R = _lib.lib().qeft_lm_head_nll_grad_chunk_rows(hn.shape[1], weight.shape[0])
+        parts = [lm_head_nll(hn[a:a + R], weight, targets[a:a + R])[:2] for a in range(0, hn.shape[0], R)]
+        lse = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts])
+        tgt = parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
+        ok = (targets >= 0) & (targets < weight.shape[0])
+        ctx.save_for_backward(hn, weight, lse, targets)
+        return torch.where(ok, lse - tgt, torch.zeros_like(lse))
+
+    @staticmethod
+    def backward(ctx, grad_nll):
+        hn, weight, lse, targets = ctx.saved_tensors
+        return lm_head_nll_grad(hn, weight, targets, lse, grad_nll), None, None
+
+
+def lm_head_nll_loss(hn, weight, targets):
+    """nll fp32 [T] = lse - tgt_logit of lm_head_nll (bit for bit; 0 on rows whose target is outside [0, vocab)), differentiable
+    with respect to hn: the backward is qeft_lm_head_nll_grad and returns fp16 [T, hidden].  Neither direction builds a
+    [T, vocab] tensor in torch; the backward's workspace holds at most 1024 rows of fp16 (softmax - onehot).  The lm_head is
+    frozen in QEFT: a weight that requires grad raises.  A width the entries refuse (hidden % 64 != 0) takes a differentiable
+    torch fp32 route, as lm_head_nll's forward does."""
+    if weight.requires_grad:
+        raise ValueError("lm_head_nll_loss has no gradient for the weight: QEFT never trains the lm_head (freeze it)")
+    if not (hn.is_cuda and weight.is_cuda):
+        raise RuntimeError("lm_head_nll_loss needs GPU tensors (there is no CPU path)")
+    if hn.dtype != torch.float16 or weight.dtype != torch.float16 or hn.dim() != 2 or weight.dim() != 2 \
+            or hn.shape[1] != weight.shape[1]:
+        raise ValueError(f"lm_head_nll_loss takes fp16 hn [T, hidden] and weight [vocab, hidden], got {tuple(hn.shape)} {hn.dtype}, "
+                         f"{tuple(weight.shape)} {weight.dtype}")
+    T, hidden = hn.shape
+    if targets.numel() != T:
+        raise ValueError(f"{targets.numel()} targets for {T} rows")
+    targets = targets.to(device=hn.device, dtype=torch.int32).reshape(T).contiguous()
+    if T == 0 or _lib.lib().qeft_lm_head_nll_grad_workspace_bytes(T, hidden, weight.shape[0]) == 0:
+        return _nll_torch(hn, weight, targets)
+    return _LmHeadNllLoss.apply(hn, weight, targets)
 
 
 @torch.no_grad()

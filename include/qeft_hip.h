@@ -478,6 +478,49 @@ int qeft_attn_prefill_kv8(const void* q, int q_stride, const void* k_codes, cons
 long long qeft_attn_prefill_kv8_check_extents(int q_stride, int kv_rows, int new_stride, int out_stride, int start, int t, int n_heads,
                                               int n_kv_heads);
 
+/* Causal attention of the training step (csrc/attn_train.hip; qeft_amd/attention.py: causal_attention; finetune.causal_lm_loss
+ * with attn="own").  n_seq sequences of t rows each, every one from position 0 and attending itself
+ * alone; sequence b is rows b * t .. b * t + t - 1 of every operand.  q, out, dout, dq: fp16 [n_seq * t][>= n_heads * 128], rows
+ * q_stride / out_stride / dout_stride / dq_stride elements apart; k, v (already rotated) and dk, dv: fp16
+ * [n_seq * t][>= n_kv_heads * 128] at kv_stride (k and v) and dkv_stride (dk and dv) -- q, k, v may be views of one fused q|k|v
+ * buffer, grouped-query layouts are read in place, head h reads kv head h / (n_heads / n_kv_heads); lse: fp32
+ * [n_seq * t][n_heads], contiguous.
+ * qeft_attn_train_fwd: `out` is, bit for bit, what qeft_attn_prefill gives at start = 0 over a cache holding the same K / V (the
+ * same body); lse[row][head] = m + log(l) of the row's online softmax over the scaled scores.
+ * qeft_attn_train_bwd: from q, k, v, the forward's out and lse, and dout, three launches -- delta[row][head] = sum_d dout * out in
+ * fp32 into `workspace` (qeft_attn_train_bwd_workspace_bytes = 4 * n_seq * t * n_heads, no initialisation, nothing kept); dK / dV,
+ * one workgroup per 128 keys of one (sequence, kv head), which sweeps the group's query heads and the query tiles in ascending
+ * order with its accumulators on chip; dQ, one workgroup per (sequence, head, 128 rows), which walks the key tiles in ascending
+ * order.  p = exp(s * 128^-0.5 - lse) in fp32, P rounded to fp16 for dV, dS = p * (dP - delta) in fp32 rounded once to fp16 (the
+ * same value in both launches), 128^-0.5 applied to dK and dQ in fp32 at the end.  No atomics and no workgroup waits on another:
+ * every output element is written exactly once (the outputs need no initialisation), and a sequence's out, lse, dq, dk, dv do
+ * not depend on n_seq, on its index or on any stride, bit for bit; out / lse / dq row i depend on rows <= i alone.
+ * QEFT_ERR_SHAPE, before any pointer is looked at: t < 1, n_seq < 1, n_seq * t > 2^20, n_heads % n_kv_heads != 0, a stride that is
+ * no multiple of 8 or narrower than its heads, a workspace shorter than qeft_attn_train_bwd_workspace_bytes; then QEFT_ERR_NULL
+ * (every pointer is required); then QEFT_ERR_ALIGN (16 bytes; 4 for lse).  n_seq and t are host integers; no host
+ * synchronisation, capturable into a graph.  Rows past a sequence's end are read from its clamped last row and never stored.
+ * qeft_attn_train_bwd_workspace_bytes: 0 for arguments the entries refuse.
+ * qeft_attn_train_bwd_part: ONE of the three launches alone under the same rules and arguments -- part 0 delta (writes the
+ * workspace), 1 dK / dV, 2 dQ (both read the workspace a part 0 call left there); QEFT_ERR_SHAPE for any other part.  For timing
+ * a launch on its own and for tests that name the kernel that ran; parts 0, 1, 2 in this order are qeft_attn_train_bwd.
+ * qeft_attn_train_check_extents / qeft_attn_train_bwd_check_extents: CPU-only -- enumerate every global address the forward /
+ * the three backward launches would form and return the largest number of bytes by which one passes the end of its operand or
+ * runs in front of it, 0 when none does (-1 for arguments the entries refuse). */
+int qeft_attn_train_fwd(const void* q, int q_stride, const void* k, const void* v, int kv_stride, void* out, int out_stride, float* lse,
+                        int n_seq, int t, int n_heads, int n_kv_heads, qeft_stream_t stream);
+long long qeft_attn_train_check_extents(int q_stride, int kv_stride, int out_stride, int n_seq, int t, int n_heads, int n_kv_heads);
+long long qeft_attn_train_bwd_workspace_bytes(int n_seq, int t, int n_heads, int n_kv_heads);
+int qeft_attn_train_bwd(const void* q, int q_stride, const void* k, const void* v, int kv_stride, const void* out, int out_stride,
+                        const void* dout, int dout_stride, const float* lse, void* dq, int dq_stride, void* dk, void* dv,
+                        int dkv_stride, void* workspace, long long workspace_bytes, int n_seq, int t, int n_heads, int n_kv_heads,
+                        qeft_stream_t stream);
+int qeft_attn_train_bwd_part(const void* q, int q_stride, const void* k, const void* v, int kv_stride, const void* out, int out_stride,
+                             const void* dout, int dout_stride, const float* lse, void* dq, int dq_stride, void* dk, void* dv,
+                             int dkv_stride, void* workspace, long long workspace_bytes, int n_seq, int t, int n_heads, int n_kv_heads,
+                             int part, qeft_stream_t stream);
+long long qeft_attn_train_bwd_check_extents(int q_stride, int kv_stride, int out_stride, int dout_stride, int dq_stride, int dkv_stride,
+                                            int n_seq, int t, int n_heads, int n_kv_heads);
+
 /* Fused lm_head + cross-entropy pieces (csrc/lm_head_nll.hip; qeft_amd/scoring.py: lm_head_nll, score, eval_nll; DESIGN.md
  * section 4.13).  x: fp16 [t][hidden], the final-norm output rows, x_stride elements apart; weight: fp16 [vocab][hidden]
  * contiguous, the checkpoint's lm_head.weight; targets: int32 [t], or NULL.  logit_ij = sum_k x_ik w_jk is accumulated in fp32 by

@@ -89,6 +89,12 @@ SIGNATURES = {
     "qeft_attn_prefill_check_extents": [_i, _i, _i, _i, _i, _i, _i],
     "qeft_attn_prefill_kv8": [_p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
     "qeft_attn_prefill_kv8_check_extents": [_i, _i, _i, _i, _i, _i, _i, _i],
+    "qeft_attn_train_fwd": [_p, _i, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p],
+    "qeft_attn_train_check_extents": [_i, _i, _i, _i, _i, _i, _i],
+    "qeft_attn_train_bwd_workspace_bytes": [_i, _i, _i, _i],
+    "qeft_attn_train_bwd": [_p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p, ctypes.c_longlong, _i, _i, _i, _i, _p],
+    "qeft_attn_train_bwd_part": [_p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p, ctypes.c_longlong, _i, _i, _i, _i, _i, _p],
+    "qeft_attn_train_bwd_check_extents": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i],
     "qeft_lm_head_nll_workspace_bytes": [_i, _i],
     "qeft_lm_head_nll": [_p, _i, _p, _p, _p, _p, _p, _p, ctypes.c_longlong, _i, _i, _i, _p],
     "qeft_lm_head_nll_check_extents": [_i, _i, _i, _i],
@@ -141,6 +147,8 @@ def lib():
                                                        "qeft_gemv_v3_check_extents", "qeft_gemv_v3_check_extents_ckpt",
                                                        "qeft_gemv_v3_check_extents_m", "qeft_attn_prefill_check_extents",
                                                        "qeft_attn_prefill_kv8_check_extents",
+                                                       "qeft_attn_train_check_extents", "qeft_attn_train_bwd_workspace_bytes",
+                                                       "qeft_attn_train_bwd_check_extents",
                                                        "qeft_lm_head_nll_workspace_bytes", "qeft_lm_head_nll_check_extents",
                                                        "qeft_lm_head_nll_grad_workspace_bytes",
                                                        "qeft_lm_head_nll_grad_check_extents",

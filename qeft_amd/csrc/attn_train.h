@@ -1,0 +1,75 @@
+// Geometry and index arithmetic of the training attention (attn_train.hip), shared by the kernels and by
+// the host-side address enumerations behind qeft_attn_train_check_extents and qeft_attn_train_bwd_check_extents: every global
+// address a launch forms comes out of one of the at_*_off functions below (the forward: of prefill_attn.h's, behind a
+// per-sequence base), with its row already clamped into the sequence.
+//
+// n_seq sequences of t rows each, every one from position 0; sequence b is rows b t .. b t + t - 1 of every operand:
+//   q, out, dout, dq  [n_seq t][>= n_heads 128]  fp16 at q_stride / out_stride / dout_stride / dq_stride
+//   k, v              [n_seq t][>= n_kv 128]     fp16 at kv_stride (both)            dk, dv the same at dkv_stride (both)
+//   lse, delta        [n_seq t][n_heads]         fp32, contiguous
+#pragma once
+#include "prefill_attn.h"
+
+namespace qeft {
+
+constexpr int AT_KB = 128;                  // keys per block of the dK / dV launch: 4 waves of 32 keys
+constexpr int AT_QT = 64;                   // query rows per tile of the dK / dV launch, at absolute multiples of 64
+constexpr int AT_THREADS = 256;
+constexpr int AT_DELTA_PAIRS = AT_THREADS / 16;     // (row, head) pairs per block of the delta launch, 16 lanes each
+
+struct AtGeom {
+    Pa8Geom f;                              // f.g: q_stride, kv_rows = t, out_stride, start = 0, t, n_heads, n_kv; f.new_stride = kv_stride
+    int dout_stride, dq_stride, dkv_stride, n_seq;
+};
+
+__host__ __device__ inline long long at_seq_base(const AtGeom& A, int seq, int stride) { return (long long)seq * A.f.g.t * stride; }
+__host__ __device__ inline int at_row(const AtGeom& A, int row) {            // a row clamped into its sequence
+    const int last = A.f.g.t - 1;
+    return row < last ? (row > 0 ? row : 0) : last;
+}
+// element offsets; `chunk` counts 8 elements (16 bytes); `row` is a row of sequence `seq`
+__host__ __device__ inline long long at_q_off(const AtGeom& A, int seq, int row, int head, int chunk) {
+    return at_seq_base(A, seq, A.f.g.q_stride) + (long long)row * A.f.g.q_stride + head * PA_HD + chunk * 8;
+}
+__host__ __device__ inline long long at_out_off(const AtGeom& A, int seq, int row, int head, int chunk) {
+    return at_seq_base(A, seq, A.f.g.out_stride) + (long long)row * A.f.g.out_stride + head * PA_HD + chunk * 8;
+}
+__host__ __device__ inline long long at_dout_off(const AtGeom& A, int seq, int row, int head, int chunk) {
+    return at_seq_base(A, seq, A.dout_stride) + (long long)row * A.dout_stride + head * PA_HD + chunk * 8;
+}
+__host__ __device__ inline long long at_kv_off(const AtGeom& A, int seq, int row, int kvh, int chunk) {
+    return at_seq_base(A, seq, A.f.new_stride) + (long long)row * A.f.new_stride + kvh * PA_HD + chunk * 8;
+}
+__host__ __device__ inline long long at_dq_off(const AtGeom& A, int seq, int row, int head, int d) {
+    return at_seq_base(A, seq, A.dq_stride) + (long long)row * A.dq_stride + head * PA_HD + d;
+}
+__host__ __device__ inline long long at_dkv_off(const AtGeom& A, int seq, int row, int kvh, int d) {
+    return at_seq_base(A, seq, A.dkv_stride) + (long long)row * A.dkv_stride + kvh * PA_HD + d;
+}
+__host__ __device__ inline long long at_lse_off(const AtGeom& A, int seq, int row, int head) {
+    return ((long long)seq * A.f.g.t + row) * A.f.g.n_heads + head;
+}
+
+// ---- forward and dQ launches: one block per (sequence, head, 128-row Q tile), prefill_attn.h's order inside a sequence
+__host__ __device__ inline int at_q_blocks_per_seq(const AtGeom& A) { return pa_q_tiles(A.f.g) * A.f.g.n_heads; }
+__host__ __device__ inline long long at_q_blocks(const AtGeom& A) { return (long long)A.n_seq * at_q_blocks_per_seq(A); }
+
+// ---- delta launch: pair = global row * n_heads + head, 16 lanes (one 16-byte chunk each) per pair
+__host__ __device__ inline long long at_delta_pairs(const AtGeom& A) { return (long long)A.n_seq * A.f.g.t * A.f.g.n_heads; }
+__host__ __device__ inline long long at_delta_blocks(const AtGeom& A) { return (at_delta_pairs(A) + AT_DELTA_PAIRS - 1) / AT_DELTA_PAIRS; }
+__host__ __device__ inline long long at_delta_pair(const AtGeom& A, long long block, int slot) {     // clamped: loaded, not stored
+    const long long pair = block * AT_DELTA_PAIRS + slot, last = at_delta_pairs(A) - 1;
+    return pair < last ? pair : last;
+}
+
+// ---- dK / dV launch: one block per (sequence, key block, kv head); key block 0 (the one with the most queries) first
+__host__ __device__ inline int at_kblocks(const AtGeom& A) { return (A.f.g.t + AT_KB - 1) / AT_KB; }
+__host__ __device__ inline long long at_dkv_blocks(const AtGeom& A) { return (long long)A.n_seq * at_kblocks(A) * A.f.g.n_kv; }
+__host__ __device__ inline int at_dkv_seq(const AtGeom& A, int block) { return block / (at_kblocks(A) * A.f.g.n_kv); }
+__host__ __device__ inline int at_dkv_kblock(const AtGeom& A, int block) { return block % (at_kblocks(A) * A.f.g.n_kv) / A.f.g.n_kv; }
+__host__ __device__ inline int at_dkv_kvh(const AtGeom& A, int block) { return block % A.f.g.n_kv; }
+// the query tiles a key block sweeps: from its own diagonal to the sequence's last row
+__host__ __device__ inline int at_dkv_first_tile(int kblock) { return kblock * (AT_KB / AT_QT); }
+__host__ __device__ inline int at_dkv_end_tile(const AtGeom& A) { return (A.f.g.t - 1) / AT_QT + 1; }
+
+}  // namespace qeft

@@ -9,6 +9,7 @@
 #include "qeft_common.h"
 #include "gemv_v3.h"
 #include "prefill_attn.h"
+#include "attn_train.h"
 
 namespace qeft {
 hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st);
@@ -89,6 +90,11 @@ long long prefill_attn_count_out_of_range(const PaGeom& G);
 hipError_t prefill_attn_kv8_launch(const void* q, const void* kq, const void* vq, const void* ksc, const void* vsc, const void* kn,
                                    const void* vn, void* out, const Pa8Geom& G8, hipStream_t st);   // prefill_attn_kv8.hip
 long long prefill_attn_kv8_count_out_of_range(const Pa8Geom& G8);
+hipError_t attn_train_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, const AtGeom& A, hipStream_t st);   // attn_train.hip
+hipError_t attn_train_bwd_launch(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse,
+                                 void* dq, void* dk, void* dv, float* delta, const AtGeom& A, int parts, hipStream_t st);
+long long attn_train_fwd_count_out_of_range(const AtGeom& A);
+long long attn_train_bwd_count_out_of_range(const AtGeom& A);
 size_t lm_head_nll_workspace_bytes(int t, int vocab);                                                                 // lm_head_nll.hip
 hipError_t lm_head_nll_launch(const void* x, const void* w, const int* targets, float* lse, float* tgt_logit, int* argmax, void* ws,
                               int x_stride, int t, int hidden, int vocab, hipStream_t st);
@@ -1171,6 +1177,101 @@ long long qeft_attn_prefill_kv8_check_extents(int q_stride, int kv_rows, int new
     qeft::Pa8Geom G8{};
     if (prefill_kv8_geom(G8, q_stride, kv_rows, new_stride, out_stride, start, t, n_heads, n_kv_heads) != QEFT_OK) return -1;
     return qeft::prefill_attn_kv8_count_out_of_range(G8);
+}
+
+// ---- training attention (attn_train.hip)
+static bool attn_train_stride_ok(int stride, int width) { return stride % 8 == 0 && stride >= width && stride <= (1 << 24); }
+
+static int attn_train_geom(qeft::AtGeom& A, int q_stride, int kv_stride, int out_stride, int n_seq, int t, int n_heads, int n_kv_heads) {
+    if (t < 1 || n_seq < 1 || (long long)n_seq * t > (1ll << 20)) return QEFT_ERR_SHAPE;
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads > 4096 || n_heads % n_kv_heads != 0) return QEFT_ERR_SHAPE;
+    if (!attn_train_stride_ok(q_stride, n_heads * 128) || !attn_train_stride_ok(out_stride, n_heads * 128) ||
+        !attn_train_stride_ok(kv_stride, n_kv_heads * 128))
+        return QEFT_ERR_SHAPE;
+    A = qeft::AtGeom{};
+    A.f.g = qeft::PaGeom{q_stride, t, out_stride, 0, t, n_heads, n_kv_heads};
+    A.f.new_stride = kv_stride;
+    A.dout_stride = A.dq_stride = n_heads * 128;
+    A.dkv_stride = n_kv_heads * 128;
+    A.n_seq = n_seq;
+    if (qeft::at_q_blocks(A) >= (1ll << 31) || qeft::at_delta_blocks(A) >= (1ll << 31)) return QEFT_ERR_SHAPE;      // the grids
+    return QEFT_OK;
+}
+
+static int attn_train_bwd_geom(qeft::AtGeom& A, int q_stride, int kv_stride, int out_stride, int dout_stride, int dq_stride,
+                               int dkv_stride, int n_seq, int t, int n_heads, int n_kv_heads) {
+    if (int e = attn_train_geom(A, q_stride, kv_stride, out_stride, n_seq, t, n_heads, n_kv_heads)) return e;
+    if (!attn_train_stride_ok(dout_stride, n_heads * 128) || !attn_train_stride_ok(dq_stride, n_heads * 128) ||
+        !attn_train_stride_ok(dkv_stride, n_kv_heads * 128))
+        return QEFT_ERR_SHAPE;
+    A.dout_stride = dout_stride;
+    A.dq_stride = dq_stride;
+    A.dkv_stride = dkv_stride;
+    return QEFT_OK;
+}
+
+int qeft_attn_train_fwd(const void* q, int q_stride, const void* k, const void* v, int kv_stride, void* out, int out_stride, float* lse,
+                        int n_seq, int t, int n_heads, int n_kv_heads, qeft_stream_t stream) {
+    qeft::AtGeom A{};
+    if (int e = attn_train_geom(A, q_stride, kv_stride, out_stride, n_seq, t, n_heads, n_kv_heads)) return e;
+    if (!q || !k || !v || !out || !lse) return QEFT_ERR_NULL;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || ((uintptr_t)lse & 3)) return QEFT_ERR_ALIGN;
+    return finish(qeft::attn_train_fwd_launch(q, k, v, out, lse, A, (hipStream_t)stream));
+}
+
+long long qeft_attn_train_check_extents(int q_stride, int kv_stride, int out_stride, int n_seq, int t, int n_heads, int n_kv_heads) {
+    qeft::AtGeom A{};
+    if (attn_train_geom(A, q_stride, kv_stride, out_stride, n_seq, t, n_heads, n_kv_heads) != QEFT_OK) return -1;
+    return qeft::attn_train_fwd_count_out_of_range(A);
+}
+
+long long qeft_attn_train_bwd_workspace_bytes(int n_seq, int t, int n_heads, int n_kv_heads) {
+    qeft::AtGeom A{};
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads > 4096) return 0;
+    if (attn_train_geom(A, n_heads * 128, n_kv_heads * 128, n_heads * 128, n_seq, t, n_heads, n_kv_heads) != QEFT_OK) return 0;
+    return 4ll * n_seq * t * n_heads;                                  // delta, fp32 [n_seq t][n_heads]
+}
+
+static int attn_train_bwd_entry(const void* q, int q_stride, const void* k, const void* v, int kv_stride, const void* out,
+                                int out_stride, const void* dout, int dout_stride, const float* lse, void* dq, int dq_stride, void* dk,
+                                void* dv, int dkv_stride, void* workspace, long long workspace_bytes, int n_seq, int t, int n_heads,
+                                int n_kv_heads, int parts, qeft_stream_t stream) {
+    qeft::AtGeom A{};
+    if (int e = attn_train_bwd_geom(A, q_stride, kv_stride, out_stride, dout_stride, dq_stride, dkv_stride, n_seq, t, n_heads,
+                                    n_kv_heads))
+        return e;
+    if (workspace_bytes < 4ll * n_seq * t * n_heads) return QEFT_ERR_SHAPE;
+    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !workspace) return QEFT_ERR_NULL;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(dout) || !aligned16(dq) || !aligned16(dk) ||
+        !aligned16(dv) || !aligned16(workspace) || ((uintptr_t)lse & 3))
+        return QEFT_ERR_ALIGN;
+    return finish(qeft::attn_train_bwd_launch(q, k, v, out, dout, lse, dq, dk, dv, (float*)workspace, A, parts, (hipStream_t)stream));
+}
+
+int qeft_attn_train_bwd(const void* q, int q_stride, const void* k, const void* v, int kv_stride, const void* out, int out_stride,
+                        const void* dout, int dout_stride, const float* lse, void* dq, int dq_stride, void* dk, void* dv,
+                        int dkv_stride, void* workspace, long long workspace_bytes, int n_seq, int t, int n_heads, int n_kv_heads,
+                        qeft_stream_t stream) {
+    return attn_train_bwd_entry(q, q_stride, k, v, kv_stride, out, out_stride, dout, dout_stride, lse, dq, dq_stride, dk, dv, dkv_stride,
+                                workspace, workspace_bytes, n_seq, t, n_heads, n_kv_heads, 7, stream);
+}
+
+int qeft_attn_train_bwd_part(const void* q, int q_stride, const void* k, const void* v, int kv_stride, const void* out, int out_stride,
+                             const void* dout, int dout_stride, const float* lse, void* dq, int dq_stride, void* dk, void* dv,
+                             int dkv_stride, void* workspace, long long workspace_bytes, int n_seq, int t, int n_heads, int n_kv_heads,
+                             int part, qeft_stream_t stream) {
+    if (part < 0 || part > 2) return QEFT_ERR_SHAPE;
+    return attn_train_bwd_entry(q, q_stride, k, v, kv_stride, out, out_stride, dout, dout_stride, lse, dq, dq_stride, dk, dv, dkv_stride,
+                                workspace, workspace_bytes, n_seq, t, n_heads, n_kv_heads, 1 << part, stream);
+}
+
+long long qeft_attn_train_bwd_check_extents(int q_stride, int kv_stride, int out_stride, int dout_stride, int dq_stride, int dkv_stride,
+                                            int n_seq, int t, int n_heads, int n_kv_heads) {
+    qeft::AtGeom A{};
+    if (attn_train_bwd_geom(A, q_stride, kv_stride, out_stride, dout_stride, dq_stride, dkv_stride, n_seq, t, n_heads, n_kv_heads) !=
+        QEFT_OK)
+        return -1;
+    return qeft::attn_train_bwd_count_out_of_range(A);
 }
 
 // ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)

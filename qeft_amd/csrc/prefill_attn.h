@@ -49,6 +49,8 @@ __host__ __device__ inline long long pa_kv_off(const PaGeom& G, int kvh, int key
 __host__ __device__ inline long long pa_out_off(const PaGeom& G, int row, int head, int d) {
     return (long long)row * G.out_stride + head * PA_HD + d;
 }
+// lse of the training forward: fp32 [t][n_heads], contiguous
+__host__ __device__ inline long long pa_lse_off(const PaGeom& G, int row, int head) { return (long long)row * G.n_heads + head; }
 
 // ---- the same attention with K / V of the past read from an e4m3 cache (prefill_attn_kv8.hip): keys [0, start) are rows of the
 // codes uint8 [n_kv][kv_rows][128] and scales fp32 [n_kv][kv_rows], keys [start, start + t) rows of the chunk's own fp16 K / V,

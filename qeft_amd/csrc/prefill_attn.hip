@@ -42,7 +42,7 @@ __global__ __launch_bounds__(PA_THREADS) void prefill_attn_kernel(const f16* __r
     __shared__ __attribute__((aligned(16))) unsigned char lds_k[PA_KT * PA_HD * 2];
     __shared__ __attribute__((aligned(16))) unsigned char lds_v[PA_KT * PA_HD * 2];
     PaStageF16 stage{kc, vc, G, pa_kv_head(G, pa_block_head(G, blockIdx.x)), (int)threadIdx.x, G.start + G.t};
-    pa_attend(q, out, G, stage, lds_k, lds_v);
+    pa_attend(q, out, G, stage, lds_k, lds_v, blockIdx.x);
 }
 
 hipError_t prefill_attn_launch(const void* q, const void* kc, const void* vc, void* out, const PaGeom& G, hipStream_t st) {

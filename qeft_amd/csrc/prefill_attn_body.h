@@ -35,11 +35,13 @@ __device__ __forceinline__ uint32_t pa_v_lds(int row, int ch) {
 // One block = one (head, 128-row Q tile), 4 waves of 32 query rows with Q in registers (the B operand of
 // v_mfma_f32_32x32x16_f16).  Tiles sit at absolute multiples of 64 from position 0, register-staged: stage.load(j + 1) is issued
 // before tile j's products and stage.store() runs after the next barrier.
-template <class Stage>
+// LSE (the training forward, attn_train.hip): the row's log-sum-exp m + log(l) also goes to lse[row][head], fp32 [t][n_heads];
+// `block` is the block's index within its sequence (blockIdx.x for the two cache kernels, which pass no lse).
+template <bool LSE = false, class Stage>
 __device__ __forceinline__ void pa_attend(const f16* __restrict__ q, f16* __restrict__ out, const PaGeom& G, Stage& stage,
-                                          unsigned char* lds_k, unsigned char* lds_v) {
+                                          unsigned char* lds_k, unsigned char* lds_v, int block, float* __restrict__ lse = nullptr) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int qtile = pa_block_qtile(G, blockIdx.x), head = pa_block_head(G, blockIdx.x);
+    const int qtile = pa_block_qtile(G, block), head = pa_block_head(G, block);
     const int n_tiles = pa_key_tiles(G, qtile);
 
     // Q fragments: k-step s takes d = 16 s + 8 h .. + 7 of this lane's row
@@ -146,6 +148,9 @@ __device__ __forceinline__ void pa_attend(const f16* __restrict__ q, f16* __rest
                 for (int j = 0; j < 4; ++j) v[j] = (f16)(o[db][4 * g + j] * inv);
                 *(h4*)(out + pa_out_off(G, row, head, 32 * db + pa_acc_row(4 * g, h))) = v;
             }
+        if constexpr (LSE) {
+            if (h == 0) lse[pa_lse_off(G, row, head)] = m + logf(l);   // both lane halves hold the row's m and l
+        }
     }
 }
 

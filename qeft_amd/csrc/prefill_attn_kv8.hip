@@ -88,7 +88,7 @@ __global__ __launch_bounds__(PA_THREADS) void prefill_attn_kv8_kernel(const f16*
     __shared__ __attribute__((aligned(16))) unsigned char lds_v[PA_KT * PA_HD * 2];
     PaStageKv8 stage{kq, vq, ksc, vsc, kn, vn, G8, pa_kv_head(G8.g, pa_block_head(G8.g, blockIdx.x)), (int)threadIdx.x,
                      G8.g.start + G8.g.t};
-    pa_attend(q, out, G8.g, stage, lds_k, lds_v);
+    pa_attend(q, out, G8.g, stage, lds_k, lds_v, blockIdx.x);
 }
 
 hipError_t prefill_attn_kv8_launch(const void* q, const void* kq, const void* vq, const void* ksc, const void* vsc, const void* kn,

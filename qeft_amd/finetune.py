@@ -11,7 +11,8 @@ The reference's finetune.py freezes every parameter except `*oweight*` and train
     end(model)                                  back to inference: prefill, score and a new DecodeEngine see the trained weights
 
 causal_lm_loss is a differentiable pass of its own (llama._prefill_pass, the inference route, is not touched): the linears and
-the head run the project's kernels; norms, rotary, attention and the activation are torch ops.  The activations are fp16, so a
+the head run the project's kernels; norms, rotary and the activation are torch ops, and so is attention unless attn="own" asks
+for the project's own (attention.causal_attention).  The activations are fp16, so a
 caller scales the loss against underflow themselves -- `(loss * s).backward()`, then divide the fp32 gradients by s; the head's
 backward takes the scale in fp32 and keeps its softmax - onehot unscaled, so no scale makes it overflow or underflow there.
 The optimiser loop and Trainer plumbing are out of scope.
@@ -19,7 +20,7 @@ The optimiser loop and Trainer plumbing are out of scope.
 import torch
 from torch.utils.checkpoint import checkpoint as _checkpoint
 
-from . import scoring
+from . import attention, scoring
 from .llama import layer_linears
 
 IGNORE_INDEX = scoring.IGNORE_INDEX
@@ -76,35 +77,48 @@ def _rope(x, cos, sin):
     return torch.cat([a * cos - b * sin, b * cos + a * sin], dim=-1).half()
 
 
-def _decoder_layer(h, L, s, B, T, cos, sin):
+def _decoder_layer(h, L, s, B, T, cos, sin, own_attn=False):
     """h [B * T, hidden] fp16 -> the layer's output, fp16; every linear is the module's own forward (training mode: the MFMA
-    forward, dX and d(oweight) kernels; o_proj gathers its own column order)."""
+    forward, dX and d(oweight) kernels; o_proj gathers its own column order).  own_attn: attention.causal_attention on the
+    un-repeated k / v instead of torch's SDPA."""
     at, mlp = L.self_attn, L.mlp
     x = _rmsnorm(h, L.input_layernorm.weight, s.rms_eps)
     q = _rope(at.q_proj(x).view(B, T, s.n_heads, 128), cos, sin)
     k = _rope(at.k_proj(x).view(B, T, s.n_kv_heads, 128), cos, sin)
     v = at.v_proj(x).view(B, T, s.n_kv_heads, 128)
-    rep = s.n_heads // s.n_kv_heads
-    if rep != 1:
-        k, v = k.repeat_interleave(rep, 2), v.repeat_interleave(rep, 2)
-    a = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True)
-    h = h + at.o_proj(a.transpose(1, 2).reshape(B * T, s.hidden))
+    if own_attn:
+        a = attention.causal_attention(q, k, v).reshape(B * T, s.hidden)
+    else:
+        rep = s.n_heads // s.n_kv_heads
+        if rep != 1:
+            k, v = k.repeat_interleave(rep, 2), v.repeat_interleave(rep, 2)
+        a = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True)
+        a = a.transpose(1, 2).reshape(B * T, s.hidden)
+    h = h + at.o_proj(a)
     x = _rmsnorm(h, L.post_attention_layernorm.weight, s.rms_eps)
     act = (torch.nn.functional.silu(mlp.gate_proj(x).float()) * mlp.up_proj(x).float()).half()
     return h + mlp.down_proj(act)
 
 
-def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused"):
+def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused", attn="sdpa"):
     """Mean NLL (fp32 scalar) of the shifted labels under `model`, differentiable with respect to the oweight parameters that
     begin(model) returned.  tokens [T] or [B, T] (right-padded; label the padding -100), labels as shift_labels takes them; a
     label outside [0, vocab) is ignored, and the mean runs over the others (0 when there is none).  Every sequence starts at
     position 0.  checkpoint=True recomputes each decoder layer in the backward (torch.utils.checkpoint, use_reentrant=False), as
     the reference's gradient checkpointing does.  head="fused": scoring.lm_head_nll_loss, no [T, vocab] tensor in either
     direction; head="torch": hn @ W.t() -> fp32 -> cross_entropy, the route the fused head is measured against.
+    attn="sdpa": torch's scaled_dot_product_attention over k / v repeated to the query heads; attn="own":
+    attention.causal_attention, the project's forward and backward kernels on the un-repeated k / v.
     fp16 activations: scale the loss yourself, `(loss * s).backward()`."""
     if head not in ("fused", "torch"):
         raise ValueError(f"head must be 'fused' or 'torch', got {head!r}")
+    if attn not in ("sdpa", "own"):
+        raise ValueError(f"attn must be 'sdpa' or 'own', got {attn!r}")
     s = model.shape
+    own = attn == "own"
+    if own and (s.n_heads % s.n_kv_heads != 0 or s.hidden != s.n_heads * 128):
+        raise ValueError(f"attn='own' takes heads of 128 and n_heads % n_kv_heads == 0, got hidden {s.hidden}, "
+                         f"{s.n_heads} / {s.n_kv_heads} heads")
     dev = model.lm_head.weight.device
     tokens = tokens.to(dev)
     if tokens.dim() not in (1, 2):
@@ -118,9 +132,9 @@ def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused")
     h = model.model.embed_tokens.weight[tok2.reshape(-1)]              # [B * T, hidden] fp16
     for L in model.model.layers:
         if checkpoint:
-            h = _checkpoint(_decoder_layer, h, L, s, B, T, cos, sin, use_reentrant=False)
+            h = _checkpoint(_decoder_layer, h, L, s, B, T, cos, sin, own, use_reentrant=False)
         else:
-            h = _decoder_layer(h, L, s, B, T, cos, sin)
+            h = _decoder_layer(h, L, s, B, T, cos, sin, own)
     hn = _rmsnorm(h, model.model.norm.weight, s.rms_eps)
     W = model.lm_head.weight
     ok = (targets >= 0) & (targets < s.vocab)

@@ -521,6 +521,43 @@ int qeft_attn_train_bwd_part(const void* q, int q_stride, const void* k, const v
 long long qeft_attn_train_bwd_check_extents(int q_stride, int kv_stride, int out_stride, int dout_stride, int dq_stride, int dkv_stride,
                                             int n_seq, int t, int n_heads, int n_kv_heads);
 
+/* The glue of the training step (csrc/train_glue.hip; qeft_amd/glue.py: add_rmsnorm, swiglu; finetune.causal_lm_loss
+ * with glue="fused"): forwards over a batch of rows and a backward for each.  Memory-bound row kernels:
+ * 16-byte accesses, fp32 math, every output rounded to fp16 exactly once, no atomics, no workspace.  A row's results depend on
+ * that row's operands alone, bit for bit -- not on the number of rows, the row's index, a stride or the grid.
+ * Common rules: hidden, n and every stride are multiples of 8, a stride is at least the row's width (and at most 2^24), the row
+ * count m is 1 .. 2^20.  QEFT_ERR_SHAPE for anything else, before any pointer is looked at; then QEFT_ERR_NULL; then
+ * QEFT_ERR_ALIGN (16 bytes).  No host synchronisation, capturable.
+ *
+ * qeft_add_rmsnorm_fwd: h, add, sum_out, y fp16 [m][hidden] dense, gamma fp16 [hidden].  s = fp16(h + add), written to sum_out
+ *   (add == NULL: s = h, and sum_out must be NULL too; one without the other is QEFT_ERR_NULL); y = fp16(s * rsqrt(mean s^2 +
+ *   eps) * gamma).  The bits of sum_out and y are qeft_rmsnorm's on the same operands.
+ * qeft_add_rmsnorm_bwd: gamma is frozen -- no d(gamma), no reduction across rows.  With r = rsqrt(mean s^2 + eps) recomputed
+ *   from s (no statistics are saved), xhat = s r and c = (1 / hidden) sum_k gamma_k dy_k xhat_k:
+ *   dsum_j = fp16(float(dres_j) + r (gamma_j dy_j - xhat_j c)), the gradient of h and of add alike.  dres is the gradient that
+ *   reaches s along the residual stream, dy the one of y; a NULL one is zero, both NULL is QEFT_ERR_SHAPE.  One launch: each row
+ *   is read once per pass (two passes) and stays in fp32 from the reductions to the store.
+ * qeft_swiglu_fwd: out[m][n] (dense) = fp16(silu(gate) * up), the bits of qeft_silu_mul; gate, up [m][>= n] at their strides.
+ * qeft_swiglu_bwd: with sigma = 1 / (1 + e^-g): dup = fp16(dact g sigma), dgate = fp16(dact u sigma (1 + g (1 - sigma))); sigma
+ *   and 1 - sigma come from one __expf(-|g|) and one hardware reciprocal without cancellation or overflow, so the results are
+ *   finite for every finite fp16 gate.  dact, dgate, dup [m][>= n] at their own strides.
+ * qeft_train_glue_check_extents: CPU-only -- enumerates every global address the launch of `op` would form and returns the
+ *   largest number of bytes by which one passes the end of its operand or runs in front of it, 0 when none does (-1 for
+ *   arguments the entry refuses or an unknown op).  rows = m, width = hidden / n; strides: SwiGLU forward gate_stride,
+ *   up_stride; SwiGLU backward gate_stride, up_stride, dact_stride, dgate_stride, dup_stride; the rest ignored. */
+#define QEFT_GLUE_ADD_RMSNORM_FWD 0
+#define QEFT_GLUE_ADD_RMSNORM_BWD 1
+#define QEFT_GLUE_SWIGLU_FWD 2
+#define QEFT_GLUE_SWIGLU_BWD 3
+int qeft_add_rmsnorm_fwd(const void* h, const void* add, const void* gamma, void* sum_out, void* y, int m, int hidden, float eps,
+                         qeft_stream_t stream);
+int qeft_add_rmsnorm_bwd(const void* s, const void* gamma, const void* dy, const void* dres, void* dsum, int m, int hidden, float eps,
+                         qeft_stream_t stream);
+int qeft_swiglu_fwd(const void* gate, const void* up, void* out, int m, int n, int gate_stride, int up_stride, qeft_stream_t stream);
+int qeft_swiglu_bwd(const void* gate, const void* up, const void* dact, void* dgate, void* dup, int m, int n, int gate_stride,
+                    int up_stride, int dact_stride, int dgate_stride, int dup_stride, qeft_stream_t stream);
+long long qeft_train_glue_check_extents(int op, int rows, int width, int stride0, int stride1, int stride2, int stride3, int stride4);
+
 /* Fused lm_head + cross-entropy pieces (csrc/lm_head_nll.hip; qeft_amd/scoring.py: lm_head_nll, score, eval_nll; DESIGN.md
  * section 4.13).  x: fp16 [t][hidden], the final-norm output rows, x_stride elements apart; weight: fp16 [vocab][hidden]
  * contiguous, the checkpoint's lm_head.weight; targets: int32 [t], or NULL.  logit_ij = sum_k x_ik w_jk is accumulated in fp32 by

@@ -6,7 +6,8 @@ The scoring and fine-tuning entry points are exported here; they resolve on firs
 _SCORING = ("score", "eval_nll", "lm_head_nll", "lm_head_nll_loss")
 _FINETUNE = ("causal_lm_loss", "shift_labels")           # qeft_amd.finetune also has begin(model) / end(model)
 _ATTENTION = ("causal_attention",)
-__all__ = [*_SCORING, *_FINETUNE, *_ATTENTION]
+_GLUE = ("add_rmsnorm", "swiglu")
+__all__ = [*_SCORING, *_FINETUNE, *_ATTENTION, *_GLUE]
 
 
 def __getattr__(name):
@@ -19,4 +20,7 @@ def __getattr__(name):
     if name in _ATTENTION:
         from . import attention
         return getattr(attention, name)
+    if name in _GLUE:
+        from . import glue
+        return getattr(glue, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

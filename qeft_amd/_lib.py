@@ -95,6 +95,11 @@ SIGNATURES = {
     "qeft_attn_train_bwd": [_p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p, ctypes.c_longlong, _i, _i, _i, _i, _p],
     "qeft_attn_train_bwd_part": [_p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p, ctypes.c_longlong, _i, _i, _i, _i, _i, _p],
     "qeft_attn_train_bwd_check_extents": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i],
+    "qeft_add_rmsnorm_fwd": [_p, _p, _p, _p, _p, _i, _i, ctypes.c_float, _p],
+    "qeft_add_rmsnorm_bwd": [_p, _p, _p, _p, _p, _i, _i, ctypes.c_float, _p],
+    "qeft_swiglu_fwd": [_p, _p, _p, _i, _i, _i, _i, _p],
+    "qeft_swiglu_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
+    "qeft_train_glue_check_extents": [_i, _i, _i, _i, _i, _i, _i, _i],
     "qeft_lm_head_nll_workspace_bytes": [_i, _i],
     "qeft_lm_head_nll": [_p, _i, _p, _p, _p, _p, _p, _p, ctypes.c_longlong, _i, _i, _i, _p],
     "qeft_lm_head_nll_check_extents": [_i, _i, _i, _i],
@@ -149,6 +154,7 @@ def lib():
                                                        "qeft_attn_prefill_kv8_check_extents",
                                                        "qeft_attn_train_check_extents", "qeft_attn_train_bwd_workspace_bytes",
                                                        "qeft_attn_train_bwd_check_extents",
+                                                       "qeft_train_glue_check_extents",
                                                        "qeft_lm_head_nll_workspace_bytes", "qeft_lm_head_nll_check_extents",
                                                        "qeft_lm_head_nll_grad_workspace_bytes",
                                                        "qeft_lm_head_nll_grad_check_extents",

@@ -10,6 +10,7 @@
 #include "gemv_v3.h"
 #include "prefill_attn.h"
 #include "attn_train.h"
+#include "train_glue.h"
 
 namespace qeft {
 hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st);
@@ -95,6 +96,15 @@ hipError_t attn_train_bwd_launch(const void* q, const void* k, const void* v, co
                                  void* dq, void* dk, void* dv, float* delta, const AtGeom& A, int parts, hipStream_t st);
 long long attn_train_fwd_count_out_of_range(const AtGeom& A);
 long long attn_train_bwd_count_out_of_range(const AtGeom& A);
+hipError_t add_rmsnorm_fwd_launch(const void* h, const void* add, const void* gamma, void* sum_out, void* y, const TgNorm& G, float eps,
+                                  hipStream_t st);                                                                       // train_glue.hip
+hipError_t add_rmsnorm_bwd_launch(const void* s, const void* gamma, const void* dy, const void* dres, void* dsum, const TgNorm& G,
+                                  float eps, hipStream_t st);
+hipError_t swiglu_fwd_launch(const void* gate, const void* up, void* out, const TgSwiglu& G, hipStream_t st);
+hipError_t swiglu_bwd_launch(const void* gate, const void* up, const void* dact, void* dgate, void* dup, const TgSwiglu& G,
+                             hipStream_t st);
+long long train_glue_norm_count_out_of_range(const TgNorm& G);
+long long train_glue_swiglu_count_out_of_range(const TgSwiglu& G, bool backward);
 size_t lm_head_nll_workspace_bytes(int t, int vocab);                                                                 // lm_head_nll.hip
 hipError_t lm_head_nll_launch(const void* x, const void* w, const int* targets, float* lse, float* tgt_logit, int* argmax, void* ws,
                               int x_stride, int t, int hidden, int vocab, hipStream_t st);
@@ -1272,6 +1282,84 @@ long long qeft_attn_train_bwd_check_extents(int q_stride, int kv_stride, int out
         QEFT_OK)
         return -1;
     return qeft::attn_train_bwd_count_out_of_range(A);
+}
+
+// ---- training glue (train_glue.hip)
+static bool tg_stride_ok(int stride, int width) { return stride % 8 == 0 && stride >= width && stride <= (1 << 24); }
+
+static int tg_norm_geom(qeft::TgNorm& G, int m, int hidden) {
+    if (m < 1 || m > (1 << 20) || hidden < 8 || hidden % 8 != 0 || hidden > (1 << 24)) return QEFT_ERR_SHAPE;
+    G = qeft::TgNorm{m, hidden};
+    return QEFT_OK;
+}
+
+static int tg_swiglu_geom(qeft::TgSwiglu& G, int m, int n, int gate_stride, int up_stride, int dact_stride, int dgate_stride,
+                          int dup_stride) {
+    if (m < 1 || m > (1 << 20) || n < 8 || n % 8 != 0 || n > (1 << 24)) return QEFT_ERR_SHAPE;
+    if (!tg_stride_ok(gate_stride, n) || !tg_stride_ok(up_stride, n) || !tg_stride_ok(dact_stride, n) || !tg_stride_ok(dgate_stride, n) ||
+        !tg_stride_ok(dup_stride, n))
+        return QEFT_ERR_SHAPE;
+    G = qeft::TgSwiglu{m, n, gate_stride, up_stride, dact_stride, dgate_stride, dup_stride};
+    if (qeft::tg_swiglu_blocks(G) >= (1ll << 31)) return QEFT_ERR_SHAPE;                 // the grid
+    return QEFT_OK;
+}
+
+int qeft_add_rmsnorm_fwd(const void* h, const void* add, const void* gamma, void* sum_out, void* y, int m, int hidden, float eps,
+                         qeft_stream_t stream) {
+    qeft::TgNorm G{};
+    if (int e = tg_norm_geom(G, m, hidden)) return e;
+    if (!h || !gamma || !y || (add != nullptr) != (sum_out != nullptr)) return QEFT_ERR_NULL;
+    if (!aligned16(h) || !aligned16(add) || !aligned16(gamma) || !aligned16(sum_out) || !aligned16(y)) return QEFT_ERR_ALIGN;
+    return finish(qeft::add_rmsnorm_fwd_launch(h, add, gamma, sum_out, y, G, eps, (hipStream_t)stream));
+}
+
+int qeft_add_rmsnorm_bwd(const void* s, const void* gamma, const void* dy, const void* dres, void* dsum, int m, int hidden, float eps,
+                         qeft_stream_t stream) {
+    qeft::TgNorm G{};
+    if (int e = tg_norm_geom(G, m, hidden)) return e;
+    if (!dy && !dres) return QEFT_ERR_SHAPE;                     // no gradient at all: nothing to compute
+    if (!s || !gamma || !dsum) return QEFT_ERR_NULL;
+    if (!aligned16(s) || !aligned16(gamma) || !aligned16(dy) || !aligned16(dres) || !aligned16(dsum)) return QEFT_ERR_ALIGN;
+    return finish(qeft::add_rmsnorm_bwd_launch(s, gamma, dy, dres, dsum, G, eps, (hipStream_t)stream));
+}
+
+int qeft_swiglu_fwd(const void* gate, const void* up, void* out, int m, int n, int gate_stride, int up_stride, qeft_stream_t stream) {
+    qeft::TgSwiglu G{};
+    if (int e = tg_swiglu_geom(G, m, n, gate_stride, up_stride, n, n, n)) return e;
+    if (!gate || !up || !out) return QEFT_ERR_NULL;
+    if (!aligned16(gate) || !aligned16(up) || !aligned16(out)) return QEFT_ERR_ALIGN;
+    return finish(qeft::swiglu_fwd_launch(gate, up, out, G, (hipStream_t)stream));
+}
+
+int qeft_swiglu_bwd(const void* gate, const void* up, const void* dact, void* dgate, void* dup, int m, int n, int gate_stride,
+                    int up_stride, int dact_stride, int dgate_stride, int dup_stride, qeft_stream_t stream) {
+    qeft::TgSwiglu G{};
+    if (int e = tg_swiglu_geom(G, m, n, gate_stride, up_stride, dact_stride, dgate_stride, dup_stride)) return e;
+    if (!gate || !up || !dact || !dgate || !dup) return QEFT_ERR_NULL;
+    if (!aligned16(gate) || !aligned16(up) || !aligned16(dact) || !aligned16(dgate) || !aligned16(dup)) return QEFT_ERR_ALIGN;
+    return finish(qeft::swiglu_bwd_launch(gate, up, dact, dgate, dup, G, (hipStream_t)stream));
+}
+
+long long qeft_train_glue_check_extents(int op, int rows, int width, int stride0, int stride1, int stride2, int stride3, int stride4) {
+    switch (op) {
+        case QEFT_GLUE_ADD_RMSNORM_FWD:
+        case QEFT_GLUE_ADD_RMSNORM_BWD: {
+            qeft::TgNorm G{};
+            if (tg_norm_geom(G, rows, width) != QEFT_OK) return -1;
+            return qeft::train_glue_norm_count_out_of_range(G);
+        }
+        case QEFT_GLUE_SWIGLU_FWD: {
+            qeft::TgSwiglu G{};
+            if (tg_swiglu_geom(G, rows, width, stride0, stride1, width, width, width) != QEFT_OK) return -1;
+            return qeft::train_glue_swiglu_count_out_of_range(G, false);
+        }
+        case QEFT_GLUE_SWIGLU_BWD: {
+            qeft::TgSwiglu G{};
+            if (tg_swiglu_geom(G, rows, width, stride0, stride1, stride2, stride3, stride4) != QEFT_OK) return -1;
+            return qeft::train_glue_swiglu_count_out_of_range(G, true);
+        }
+        default: return -1;
+    }
 }
 
 // ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)

@@ -11,8 +11,10 @@ The reference's finetune.py freezes every parameter except `*oweight*` and train
     end(model)                                  back to inference: prefill, score and a new DecodeEngine see the trained weights
 
 causal_lm_loss is a differentiable pass of its own (llama._prefill_pass, the inference route, is not touched): the linears and
-the head run the project's kernels; norms, rotary and the activation are torch ops, and so is attention unless attn="own" asks
-for the project's own (attention.causal_attention).  The activations are fp16, so a
+the head run the project's kernels; norms, rotary, the activation and the residual adds are torch ops unless glue="fused" asks
+for the project's row kernels and their backward kernels (qeft_amd.glue; the rotary stays torch's), and
+so is attention unless attn="own" asks for the project's own (attention.causal_attention).  The
+activations are fp16, so a
 caller scales the loss against underflow themselves -- `(loss * s).backward()`, then divide the fp32 gradients by s; the head's
 backward takes the scale in fp32 and keeps its softmax - onehot unscaled, so no scale makes it overflow or underflow there.
 The optimiser loop and Trainer plumbing are out of scope.
@@ -20,7 +22,7 @@ The optimiser loop and Trainer plumbing are out of scope.
 import torch
 from torch.utils.checkpoint import checkpoint as _checkpoint
 
-from . import attention, scoring
+from . import attention, glue as _glue, scoring
 from .llama import layer_linears
 
 IGNORE_INDEX = scoring.IGNORE_INDEX
@@ -77,6 +79,17 @@ def _rope(x, cos, sin):
     return torch.cat([a * cos - b * sin, b * cos + a * sin], dim=-1).half()
 
 
+def _attend(q, k, v, s, B, T, own_attn):
+    """q [B, T, H, 128], k / v [B, T, Hkv, 128] (rotated) -> [B * T, hidden] on either attention route."""
+    if own_attn:
+        return attention.causal_attention(q, k, v).reshape(B * T, s.hidden)
+    rep = s.n_heads // s.n_kv_heads
+    if rep != 1:
+        k, v = k.repeat_interleave(rep, 2), v.repeat_interleave(rep, 2)
+    a = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True)
+    return a.transpose(1, 2).reshape(B * T, s.hidden)
+
+
 def _decoder_layer(h, L, s, B, T, cos, sin, own_attn=False):
     """h [B * T, hidden] fp16 -> the layer's output, fp16; every linear is the module's own forward (training mode: the MFMA
     forward, dX and d(oweight) kernels; o_proj gathers its own column order).  own_attn: attention.causal_attention on the
@@ -86,21 +99,28 @@ def _decoder_layer(h, L, s, B, T, cos, sin, own_attn=False):
     q = _rope(at.q_proj(x).view(B, T, s.n_heads, 128), cos, sin)
     k = _rope(at.k_proj(x).view(B, T, s.n_kv_heads, 128), cos, sin)
     v = at.v_proj(x).view(B, T, s.n_kv_heads, 128)
-    if own_attn:
-        a = attention.causal_attention(q, k, v).reshape(B * T, s.hidden)
-    else:
-        rep = s.n_heads // s.n_kv_heads
-        if rep != 1:
-            k, v = k.repeat_interleave(rep, 2), v.repeat_interleave(rep, 2)
-        a = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True)
-        a = a.transpose(1, 2).reshape(B * T, s.hidden)
-    h = h + at.o_proj(a)
+    h = h + at.o_proj(_attend(q, k, v, s, B, T, own_attn))
     x = _rmsnorm(h, L.post_attention_layernorm.weight, s.rms_eps)
     act = (torch.nn.functional.silu(mlp.gate_proj(x).float()) * mlp.up_proj(x).float()).half()
     return h + mlp.down_proj(act)
 
 
-def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused", attn="sdpa"):
+def _decoder_layer_fused(h, delta, L, s, B, T, cos, sin, own_attn=False):
+    """The layer of glue="fused" (DESIGN.md section 4.16).  The residual stream arrives as (h, delta) -- the stream before the last
+    MLP and that MLP's output, delta None in layer 0 -- and leaves the same way, so that every residual add happens inside the
+    norm that follows it (glue.add_rmsnorm) and every sum of residual-stream gradients inside that norm's backward; SiLU * up is
+    glue.swiglu.  The rotary stays the torch expression of the default route."""
+    at, mlp = L.self_attn, L.mlp
+    s1, x = _glue.add_rmsnorm(h, delta, L.input_layernorm.weight, s.rms_eps)
+    q = _rope(at.q_proj(x).view(B, T, s.n_heads, 128), cos, sin)
+    k = _rope(at.k_proj(x).view(B, T, s.n_kv_heads, 128), cos, sin)
+    v = at.v_proj(x).view(B, T, s.n_kv_heads, 128)
+    s2, x = _glue.add_rmsnorm(s1, at.o_proj(_attend(q, k, v, s, B, T, own_attn)), L.post_attention_layernorm.weight, s.rms_eps)
+    act = _glue.swiglu(mlp.gate_proj(x), mlp.up_proj(x))
+    return s2, mlp.down_proj(act)
+
+
+def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused", attn="sdpa", glue="torch"):
     """Mean NLL (fp32 scalar) of the shifted labels under `model`, differentiable with respect to the oweight parameters that
     begin(model) returned.  tokens [T] or [B, T] (right-padded; label the padding -100), labels as shift_labels takes them; a
     label outside [0, vocab) is ignored, and the mean runs over the others (0 when there is none).  Every sequence starts at
@@ -109,11 +129,16 @@ def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused",
     direction; head="torch": hn @ W.t() -> fp32 -> cross_entropy, the route the fused head is measured against.
     attn="sdpa": torch's scaled_dot_product_attention over k / v repeated to the query heads; attn="own":
     attention.causal_attention, the project's forward and backward kernels on the un-repeated k / v.
+    glue="torch": norms, rotary, SiLU * up and the residual adds are torch ops; glue="fused": norms and SiLU * up on the project's
+    row kernels and their backward kernels (qeft_amd.glue), with every residual add inside the norm that
+    follows it; the rotary stays torch's.
     fp16 activations: scale the loss yourself, `(loss * s).backward()`."""
     if head not in ("fused", "torch"):
         raise ValueError(f"head must be 'fused' or 'torch', got {head!r}")
     if attn not in ("sdpa", "own"):
         raise ValueError(f"attn must be 'sdpa' or 'own', got {attn!r}")
+    if glue not in ("torch", "fused"):
+        raise ValueError(f"glue must be 'torch' or 'fused', got {glue!r}")
     s = model.shape
     own = attn == "own"
     if own and (s.n_heads % s.n_kv_heads != 0 or s.hidden != s.n_heads * 128):
@@ -130,12 +155,21 @@ def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused",
         raise ValueError(f"{T} tokens exceed the model's max_seq {s.max_seq}")
     cos, sin = model.rope_cos[:T, None, :], model.rope_sin[:T, None, :]
     h = model.model.embed_tokens.weight[tok2.reshape(-1)]              # [B * T, hidden] fp16
-    for L in model.model.layers:
-        if checkpoint:
-            h = _checkpoint(_decoder_layer, h, L, s, B, T, cos, sin, own, use_reentrant=False)
-        else:
-            h = _decoder_layer(h, L, s, B, T, cos, sin, own)
-    hn = _rmsnorm(h, model.model.norm.weight, s.rms_eps)
+    if glue == "fused":
+        delta = None
+        for L in model.model.layers:
+            if checkpoint:
+                h, delta = _checkpoint(_decoder_layer_fused, h, delta, L, s, B, T, cos, sin, own, use_reentrant=False)
+            else:
+                h, delta = _decoder_layer_fused(h, delta, L, s, B, T, cos, sin, own)
+        hn = _glue.add_rmsnorm(h, delta, model.model.norm.weight, s.rms_eps)[1]
+    else:
+        for L in model.model.layers:
+            if checkpoint:
+                h = _checkpoint(_decoder_layer, h, L, s, B, T, cos, sin, own, use_reentrant=False)
+            else:
+                h = _decoder_layer(h, L, s, B, T, cos, sin, own)
+        hn = _rmsnorm(h, model.model.norm.weight, s.rms_eps)
     W = model.lm_head.weight
     ok = (targets >= 0) & (targets < s.vocab)
     n = ok.sum().clamp_min(1).to(torch.float32)

@@ -33,15 +33,19 @@ __host__ __device__ constexpr size_t attn_ctr_floats(int n_heads) { return ((siz
 
 // Single-token attention for one sequence.  grid = n_heads * S, block = 256 (4 waves), head_dim = 128.
 //   q,k,v  : this token's projections [n_heads*128], [n_kv*128], [n_kv*128] (fp16)
-//   cos/sin: [tab_rows][64] fp32 rotary table; tab_rows == 1: the row of THIS position, selected by the caller
+//   cos/sin: fp32 rotary values; ROW: [64], the row of THIS position, selected by the caller (the engine's form);
+//            !ROW: the whole table [>= max_seq][64], row *pos_ptr is used.  The launcher picks the instantiation (tab_rows == 1)
 //   kc, vc : caches [n_kv][max_seq][128] fp16;  *pos_ptr = index of this token (0-based)
 //   out    : [n_heads*128] fp16, element i stored at out_pos[i] when out_pos is given
 //   ws     : S > 1 only: [attn_ctr_floats(n_heads)] uint32 arrival counters (zero before first use), then [n_heads*S][kAttnRec] floats
 // 32 blocks pulling a whole head's K and V each are bound by what ONE CU can load (~100 KB took ~4 us), so a head is
 // split over S blocks and the kernel is organised around latency:
-//   * everything that does not depend on `pos` is requested first -- q/k/v, out_pos and, unconditionally, the K
-//     quarter-rows and V pieces of the first PRE runs of each wave (rows past the context are fetched and ignored);
-//     only the rotary entry waits for `pos`;
+//   * requests go out in the order in which their consumers run, because a wave's vector loads retire in order through one
+//     counter: q/k/v and the rotary values first (ROW: before `pos` is back), the output map, then -- `pos` gives the context
+//     length -- the K quarter-rows and V pieces of the first PRE runs of each wave (a run past the context re-reads row 0, so
+//     the count is fixed).  The rotary waits for what is older than that prefetch (vmcnt(PRE * (4 + 4 / DH))), run i's scores
+//     for the K loads up to run i's, P.V for the V loads; rotary, scores and P.V of the prefetched runs are straight-line
+//     code (values and addresses selected, nothing branched on), so that no wait covers a load its consumer does not read;
 //   * positions are dealt in runs of 16 to the 4*S waves of a head (run r belongs to wave r % (4*S)); each wave
 //     computes its scores, its own maximum, exp and P.V partials with wave-level operations only (flash-decoding
 //     split), the block merges its 4 waves once through LDS;
@@ -66,7 +70,7 @@ __device__ __forceinline__ size_t kcache_off(int p, int chunk, int max_seq) {
 // `bid` = the block's index among the attention blocks, `smem_raw` = its dynamic LDS, and -- S == 1 only -- `pub` != NULL sends
 // every output element to pub[opos] by an agent-scope (write-through) store instead of a plain store to out[opos]: readers on
 // other XCDs of the SAME launch can then be released by a flag (lab only; the product passes NULL).
-template <int PRE, int DH = 1, bool KFT = false, bool DBG = false, bool ALIBI = false>
+template <int PRE, int DH = 1, bool KFT = false, bool DBG = false, bool ALIBI = false, bool ROW = true>
 __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const int bid, const int* __restrict__ pos_ptr,
                                                       const int* __restrict__ out_pos, const f16* __restrict__ q,
                                                       const f16* __restrict__ k, const f16* __restrict__ v,
@@ -77,7 +81,7 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
                                                       f16* __restrict__ pub = nullptr) {
     constexpr int HD = 128;
     const int n_heads = (int)(heads_kv_s_tab & 0xfffu), n_kv = (int)((heads_kv_s_tab >> 12) & 0xfffu);
-    const int S = (int)((heads_kv_s_tab >> 24) & 0xfu), tab_rows = (int)(heads_kv_s_tab >> 28);     // 1: cs / sn are this position's row; 0: the whole table
+    const int S = (int)((heads_kv_s_tab >> 24) & 0xfu);
     unsigned long long* const dbg = DBG ? dbg_ptr : nullptr;
     unsigned long long stamp[10];
     auto mark = [&](int i) {
@@ -111,29 +115,40 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
     // added to the scaled score (decoder_masked_multihead_attention_template.hpp:1335-1345, no padding tokens)
     const float slope = ALIBI ? alibi[h] : 0.f;
 
-    // ---- loads that do not depend on pos.  All of them are unconditional (addresses selected, never branched on)
-    // and nothing is converted here: a conversion or a divergent branch makes the compiler wait for the load on the
+    // ---- loads that do not depend on pos.  The per-thread ones are unconditional (addresses selected, never branched
+    // on) and nothing is converted here: a conversion or a divergent branch makes the compiler wait for the load on the
     // spot, which serialises one memory round trip per load group at the top of the kernel.
     const int ti = dhi * HDB + (t & (HDB - 1));                        // output element of this thread (within the head)
-    const int* opp = out_pos ? out_pos + h * HD + ti : pos_ptr;        // dummy in-range address when there is no map
-    const int opos_raw = *opp;
     const f16* src = (t < 64) ? q + h * HD + t : (t < 128) ? k + hk * HD + (t - 64) : v + hk * HD + (t - 128);
     const f16 raw_a = src[0];
     const f16 raw_b = src[(t < 128) ? 64 : 0];
-    float rc = 0.f, rsn = 0.f;
-    if (tab_rows == 1) {                      // the caller already selected this position's rotary row: no wait for pos
+    // The rotary values are requested by every thread, without a branch and AHEAD of the K/V prefetch in both forms: the
+    // counter of outstanding vector loads retires in order, so the rotary's wait for them then leaves the whole prefetch
+    // in flight.  (Loaded behind the prefetch in one form only, they made the compiler drain it -- vmcnt(0) -- in both.)
+    float rc, rsn;
+    if constexpr (ROW) {                      // the caller already selected this position's rotary row: no wait for pos
         rc = cs[t & 63];
         rsn = sn[t & 63];
     }
+    // The output map is the one load taken under a (kernel-uniform, scalar) branch, and it stands HERE on purpose: loads
+    // whose values are used only behind the `pos` check below are otherwise sunk behind that check -- issued one scalar
+    // round trip late -- and a load is not sunk past a join of two paths.
+    int opos_raw = 0;
+    if (out_pos) opos_raw = out_pos[h * HD + ti];
     // `pos` is a scalar load: it arrives while the vector loads above are in flight, and nothing above waits for it
     mark(1);
     const int pos = *pos_ptr, L = pos + 1;
     if (pos < 0 || pos >= max_seq) return;   // never index the cache / rotary table out of range (grid-uniform)
     if (dbg) { asm volatile("" :: "s"(pos)); }
+    if constexpr (!ROW) {                     // the whole table: row pos; `pos` is awaited for the prefetch (L) anyway
+        rc = cs[(size_t)pos * 64 + (t & 63)];
+        rsn = sn[(size_t)pos * 64 + (t & 63)];
+    }
     mark(2);
     // ---- K/V of the first PRE runs of this wave.  One CU pulls ~50 GB/s, so only rows inside the context are
     // fetched; the load COUNT stays fixed (runs past the context re-read row 0, an L1 hit), which keeps the compiler's
-    // vmcnt bookkeeping exact and lets the rotary / scores start while later rows are still in flight.
+    // vmcnt bookkeeping exact: the rotary waits for q/k/v and the table values only, run i's scores for the K loads up to
+    // run i's, and P.V for the V loads -- all of it straight-line code, so no wait covers a load its consumer does not read.
     // score role: position pj of the run, dims qd*8 + 32*j .. +8 (j = 0..3): the 4 lanes of a position read 64
     // contiguous bytes per load instruction
     const int qd = lane & 3, pj = lane >> 2;
@@ -157,32 +172,36 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
         for (int j = 0; j < PPC; ++j) vpre[i][j] = row[j * (HD / 8)];
     }
     const int opos = out_pos ? opos_raw : h * HD + ti;
+    // ---- rotary and staging, one straight line for the four waves: every thread rotates (the v threads' result is not used)
+    // and writes two LDS halves whose VALUE and ADDRESS are selected by its role.  A value used under a role branch only
+    // is sunk into that branch by the compiler, load and all -- behind the prefetch, where waiting for it drains the prefetch.
     const float ra = (float)raw_a, rb = (float)raw_b;
-    if (t < 128) {
-        const int i = t & 63;
-        const float c = (tab_rows == 1) ? rc : cs[(size_t)pos * 64 + i];
-        const float sv = (tab_rows == 1) ? rsn : sn[(size_t)pos * 64 + i];
-        const float r0 = ra * c - rb * sv, r1 = rb * c + ra * sv;
-        if (t < 64) {
-            const float scale = 0.08838834764831845f;  // 1/sqrt(128)
-            qs[i] = (f16)(r0 * scale);
-            qs[i + 64] = (f16)(r1 * scale);
-        } else {
-            const f16 k0 = (f16)r0, k1 = (f16)r1;
-            knew[i] = k0;
-            knew[i + 64] = k1;
-            if (appender) {
-                kch[kcache_off<KFT>(pos, i >> 3, max_seq) + (i & 7)] = k0;
-                kch[kcache_off<KFT>(pos, (i >> 3) + 8, max_seq) + (i & 7)] = k1;
-            }
-        }
-    } else {
-        const int i = t - 128;
-        const f16 vv = (f16)ra;
-        vnew[i] = vv;
-        if (appender) vch[(size_t)pos * HD + i] = vv;
+    const int i = t & 63;
+    const float c = rc, sv = rsn;
+    float r0 = ra * c - rb * sv, r1 = rb * c + ra * sv;
+    // the rotated pair exists in fp32 once, for q and k alike: k is the fp16 rounding OF that fp32 value (without this the
+    // compiler folds the rounding into a second, fused evaluation for k, which rounds once and differs in the last bit)
+    asm("" : "+v"(r0), "+v"(r1));
+    const float scale = 0.08838834764831845f;  // 1/sqrt(128)
+    const f16 q0 = (f16)(r0 * scale), q1 = (f16)(r1 * scale);
+    const f16 k0 = (f16)r0, k1 = (f16)r1;
+    const f16 vv = (f16)ra;
+    {
+        // qs + i | knew + i | vnew + (t - 128), as one offset into knew | vnew | qs (contiguous, above): plain integer selects
+        f16* const d0 = knew + t + ((t < 64) ? 2 * HD : (t < 128) ? -64 : 0);
+        d0[0] = (t < 64) ? q0 : (t < 128) ? k0 : vv;
+        d0[(t < 128) ? 64 : 0] = (t < 64) ? q1 : (t < 128) ? k1 : vv;      // the v threads write their one element twice
     }
-    // workgroup barrier for LDS only: __syncthreads() would also drain the K/V prefetch that is still in flight
+    if (appender) {                           // block-uniform; stores only, of values the LDS writes above already needed
+        if (t >= 128) {
+            vch[(size_t)pos * HD + (t - 128)] = vv;
+        } else if (t >= 64) {
+            kch[kcache_off<KFT>(pos, i >> 3, max_seq) + (i & 7)] = k0;
+            kch[kcache_off<KFT>(pos, (i >> 3) + 8, max_seq) + (i & 7)] = k1;
+        }
+    }
+    // workgroup barrier for LDS only: __syncthreads() would also drain the K/V prefetch that is still in flight (the append
+    // stores above count in vmcnt as well; they are the youngest entries and nothing below waits for them)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     mark(3);
 
@@ -190,37 +209,40 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
     h2 qreg[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) qreg[j] = *(const h2*)(qs + (j >> 2) * 32 + qd * 8 + 2 * (j & 3));
+    // The new token's own score comes from LDS (its cache row may not have landed, and the tests poison it): every lane
+    // runs that chain once per wave, and the lanes of position `pos` take it by a select.  Nothing in a run is branched on,
+    // so the PRE prefetched runs are one basic block with one vmcnt wait per K load (this hipcc keeps the runs' dot2 chains in
+    // program order and interleaves only the own-score chain with run 0's); a run past the context (the wave-uniform !live)
+    // computes on row 0 and sends its masked scores to the 16 spare floats behind prob[max_seq].
+    float snew = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) snew = dot2(qreg[j], *(const h2*)(knew + (j >> 2) * 32 + qd * 8 + 2 * (j & 3)), snew);
     float lmax = -3.0e38f;
-    auto score_run = [&](int i, const h8* kr) {
+    auto score_run = [&](int i, const h8* kr, bool live) {
         const int p = (i * NW + gw) * 16 + pj;
         float sdot = 0.f;
         // v_dot2_f32_f16: two products per instruction, fp32 accumulation, no conversions
-        if (p == pos) {
 #pragma unroll
-            for (int j = 0; j < 16; ++j) sdot = dot2(qreg[j], *(const h2*)(knew + (j >> 2) * 32 + qd * 8 + 2 * (j & 3)), sdot);
-        } else {
+        for (int j = 0; j < 4; ++j) {
+            const u32x4 kw = __builtin_bit_cast(u32x4, kr[j]);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const u32x4 kw = __builtin_bit_cast(u32x4, kr[j]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sdot = dot2(qreg[j * 4 + e], as_h2(kw[e]), sdot);
-            }
+            for (int e = 0; e < 4; ++e) sdot = dot2(qreg[j * 4 + e], as_h2(kw[e]), sdot);
         }
+        sdot = (p == pos) ? snew : sdot;
         sdot += dpp_mov<0xB1>(sdot);
         sdot += dpp_mov<0x4E>(sdot);
         if constexpr (ALIBI) sdot += slope * (float)(p - pos);
-        if (p >= L) sdot = -3.0e38f;         // fetched but outside the context (possibly uninitialised cache rows)
-        if (qd == 0) prob[p] = sdot;
+        sdot = (p >= L) ? -3.0e38f : sdot;   // fetched but outside the context (possibly uninitialised cache rows)
+        if (qd == 0) prob[live ? p : max_seq + pj] = sdot;
         lmax = fmaxf(lmax, sdot);
     };
 #pragma unroll
-    for (int i = 0; i < PRE; ++i)
-        if ((i * NW + gw) * 16 < L) score_run(i, kpre[i]);
+    for (int i = 0; i < PRE; ++i) score_run(i, kpre[i], (i * NW + gw) * 16 < L);
     for (int i = PRE; (i * NW + gw) * 16 < L; ++i) {
         h8 kr[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) kr[j] = *(const h8*)(kch + kcache_off<KFT>((i * NW + gw) * 16 + pj, qd + 4 * j, max_seq));
-        score_run(i, kr);
+        score_run(i, kr, true);
     }
     const float mw = wave_max(lmax);
     mark(4);
@@ -231,33 +253,35 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = 0.f;
     float lsum = 0.f;
-    auto pv_run = [&](int i, const h8* vr) {
+    // Selects again, no branches: a position outside the context gets the weight 0 by a select (never 0 x cache, which may
+    // hold NaN there) and, like the token's own position, the token's v from LDS as its finite operand; adding 0 x that
+    // leaves every sum as it was, bit for bit.
+    const h8 vn = *(const h8*)(vnew + dim0);
+    auto pv_run = [&](int i, const h8* vr, bool live) {
         const int p0 = (i * NW + gw) * 16 + pc * PPC;
+        const int s0 = live ? p0 : max_seq + pc * PPC;
         float sraw[PPC];
 #pragma unroll
-        for (int j = 0; j < PPC; ++j) sraw[j] = prob[p0 + j];
+        for (int j = 0; j < PPC; ++j) sraw[j] = prob[s0 + j];
 #pragma unroll
         for (int j = 0; j < PPC; ++j) {
             const int p = p0 + j;
-            if (p < L) {
-                const float e = __expf(sraw[j] - mw);
-                h8 vv = vr[j];
-                if (p == pos) vv = *(const h8*)(vnew + dim0);
-                lsum += e;
+            const float ex = __expf(sraw[j] - mw);
+            const float e = (p < L) ? ex : 0.f;
+            const h8 vv = (p < pos) ? vr[j] : vn;
+            lsum += e;
 #pragma unroll
-                for (int d = 0; d < 8; ++d) o[d] += e * (float)vv[d];
-            }
+            for (int d = 0; d < 8; ++d) o[d] += e * (float)vv[d];
         }
     };
 #pragma unroll
-    for (int i = 0; i < PRE; ++i)
-        if ((i * NW + gw) * 16 < L) pv_run(i, vpre[i]);
+    for (int i = 0; i < PRE; ++i) pv_run(i, vpre[i], (i * NW + gw) * 16 < L);
     for (int i = PRE; (i * NW + gw) * 16 < L; ++i) {
         h8 vr[PPC];
 #pragma unroll
         for (int j = 0; j < PPC; ++j)
             vr[j] = *(const h8*)(vch + (size_t)((i * NW + gw) * 16 + pc * PPC + j) * HD + dim0);
-        pv_run(i, vr);
+        pv_run(i, vr, true);
     }
     {
         float* dst = part + (w * NPC + pc) * HDB + dg * 8;
@@ -341,7 +365,7 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
     }
 }
 
-template <int PRE, int DH = 1, bool KFT = false, bool DBG = false, bool ALIBI = false>
+template <int PRE, int DH = 1, bool KFT = false, bool DBG = false, bool ALIBI = false, bool ROW = true>
 __global__ __launch_bounds__(256) void rope_attn_decode_kernel(const int* __restrict__ pos_ptr, const int* __restrict__ out_pos,
                                                                const f16* __restrict__ q, const f16* __restrict__ k,
                                                                const f16* __restrict__ v, const float* __restrict__ cs,
@@ -350,7 +374,7 @@ __global__ __launch_bounds__(256) void rope_attn_decode_kernel(const int* __rest
                                                                float* __restrict__ ws, int max_seq, unsigned long long* dbg_ptr,
                                                                const float* __restrict__ alibi) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
-    rope_attn_decode_body<PRE, DH, KFT, DBG, ALIBI>(smem_raw, (int)blockIdx.x, pos_ptr, out_pos, q, k, v, cs, heads_kv_s_tab, sn, kc, vc, out, ws,
+    rope_attn_decode_body<PRE, DH, KFT, DBG, ALIBI, ROW>(smem_raw, (int)blockIdx.x, pos_ptr, out_pos, q, k, v, cs, heads_kv_s_tab, sn, kc, vc, out, ws,
                                                     max_seq, dbg_ptr, alibi);
 }
 

@@ -360,6 +360,11 @@ hipError_t silu_mul_launch(const void* gate, const void* up, void* out, int n, h
 }
 
 unsigned long long* g_attn_dbg = nullptr;   // lab only: per-wave phase stamps
+// Prefetched runs per wave of the one-block-per-head (S == 1) launches: 4 x 4 waves x 16 = the first 256 positions.  A/B of the
+// depth: build with -DQEFT_ATTN_PRE1=2 / 6 (qeft_amd.build extra_flags) and time the two libraries with QEFT_HIP_LIB.
+#ifndef QEFT_ATTN_PRE1
+#define QEFT_ATTN_PRE1 4
+#endif
 size_t attn_workspace_bytes(int n_heads, int S) { return S > 1 ? (attn_ctr_floats(n_heads) + (size_t)n_heads * S * kAttnRec) * 4 : 0; }
 
 hipError_t rope_attn_decode_launch(const void* q, const void* k, const void* v, const void* cs, const void* sn, void* kc,
@@ -375,7 +380,7 @@ hipError_t rope_attn_decode_launch(const void* q, const void* k, const void* v, 
             if (e != hipSuccess) return e;
         }
         if (n_heads > 4095 || n_kv > 4095 || S > 15) return hipErrorInvalidValue;
-        const uint32_t packed = (uint32_t)n_heads | ((uint32_t)n_kv << 12) | ((uint32_t)S << 24) | ((tab_rows == 1 ? 1u : 0u) << 28);
+        const uint32_t packed = (uint32_t)n_heads | ((uint32_t)n_kv << 12) | ((uint32_t)S << 24);
         hipLaunchKernelGGL(kern, dim3(n_heads * S * dh), dim3(256), smem, st, pos, out_pos, (const f16*)q, (const f16*)k,
                            (const f16*)v, (const float*)cs, packed, (const float*)sn, (f16*)kc, (f16*)vc, (f16*)out, (float*)ws,
                            max_seq, g_attn_dbg, alibi_slopes);
@@ -383,31 +388,37 @@ hipError_t rope_attn_decode_launch(const void* q, const void* k, const void* v, 
     };
     // measured on the 7B decode step (contexts 64..192): 682 / 689 / 688 tokens/s with 1 / 2 / 4 blocks per head
     static const int dh_env = getenv("QEFT_ATTN_DH") ? atoi(getenv("QEFT_ATTN_DH")) : 2;   // A/B switch: 1, 2 or 4 (4: 797 vs 799 tokens/s)
+    // with the K/V prefetch left in flight across the rotary (decode_attn.h): 841 / 851 / 846-850 with 1 / 2 / 4
+    // The rotary-table form is a template parameter (ROW: the caller selected this position's row): either form then has
+    // its table loads in one place ahead of the K/V prefetch (decode_attn.h).
+    const bool row = tab_rows == 1;
+#define QEFT_ATTN_FORM(...) (row ? launch(rope_attn_decode_kernel<__VA_ARGS__, true>) : launch(rope_attn_decode_kernel<__VA_ARGS__, false>))
     if (k_ft_layout) {     // the reference's single_query_attention boundary: one block per head
         if (S != 1) return hipErrorInvalidValue;
-        if (alibi_slopes) return launch(rope_attn_decode_kernel<4, 1, true, false, true>);
-        return launch(rope_attn_decode_kernel<4, 1, true>);
+        if (alibi_slopes) return QEFT_ATTN_FORM(4, 1, true, false, true);
+        return QEFT_ATTN_FORM(4, 1, true, false, false);
     }
     if (g_attn_dbg) {      // lab: the stamped variants
         if (S == 1 && dh_env == 2) {
             dh = 2;
-            return launch(rope_attn_decode_kernel<4, 2, false, true>);
+            return QEFT_ATTN_FORM(4, 2, false, true, false);
         }
-        if (S == 1) return launch(rope_attn_decode_kernel<4, 1, false, true>);
-        if (S == 2) return launch(rope_attn_decode_kernel<2, 1, false, true>);
-        return launch(rope_attn_decode_kernel<1, 1, false, true>);
+        if (S == 1) return QEFT_ATTN_FORM(4, 1, false, true, false);
+        if (S == 2) return QEFT_ATTN_FORM(2, 1, false, true, false);
+        return QEFT_ATTN_FORM(1, 1, false, true, false);
     }
     if (S == 1 && dh_env == 4) {
         dh = 4;
-        return launch(rope_attn_decode_kernel<4, 4>);
+        return QEFT_ATTN_FORM(QEFT_ATTN_PRE1, 4, false, false, false);
     }
     if (S == 1 && dh_env == 2) {
         dh = 2;
-        return launch(rope_attn_decode_kernel<4, 2>);
+        return QEFT_ATTN_FORM(QEFT_ATTN_PRE1, 2, false, false, false);
     }
-    if (S == 1) return launch(rope_attn_decode_kernel<4>);
-    if (S == 2) return launch(rope_attn_decode_kernel<2>);
-    return launch(rope_attn_decode_kernel<1>);
+    if (S == 1) return QEFT_ATTN_FORM(QEFT_ATTN_PRE1, 1, false, false, false);
+    if (S == 2) return QEFT_ATTN_FORM(2, 1, false, false, false);
+    return QEFT_ATTN_FORM(1, 1, false, false, false);
+#undef QEFT_ATTN_FORM
 }
 
 // ---- single-query attention for head sizes other than 128 (round 4; the `qeft_cuda.single_query_attention` boundary only).

@@ -371,10 +371,11 @@ hipError_t attn_oproj_launch(const void* q, const void* k, const void* v, const 
                              const int* pos, const int* out_pos, int n_heads, int n_kv, int max_seq, const void* qweight, const void* sz_packed,
                              const void* oweight, void* h32, const void* gamma_out, void* ynorm, float* ssq_out, int hidden, int k_in,
                              void* xatt, void* state, hipStream_t st) {
+    if (tab_rows != 1) return hipErrorInvalidValue;     // the lab runs the body's ROW form (the engine's: the caller selected the rotary row)
     AoArgs a{};
     a.pos = pos; a.out_pos = out_pos; a.q = (const f16*)q; a.k = (const f16*)k; a.v = (const f16*)v;
     a.cs = (const float*)cs; a.sn = (const float*)sn;
-    a.heads_kv_s_tab = (uint32_t)n_heads | ((uint32_t)n_kv << 12) | (1u << 24) | ((tab_rows == 1 ? 1u : 0u) << 28);
+    a.heads_kv_s_tab = (uint32_t)n_heads | ((uint32_t)n_kv << 12) | (1u << 24);
     a.kc = (f16*)kc; a.vc = (f16*)vc; a.max_seq = max_seq; a.n_attn_blocks = n_heads * 2;
     a.qw = (const uint8_t*)qweight; a.szp = (const uint8_t*)sz_packed; a.ow = (const uint8_t*)oweight;
     a.h32 = (float*)h32; a.gamma_out = (const f16*)gamma_out; a.ynorm = (f16*)ynorm; a.ssq_out = ssq_out;

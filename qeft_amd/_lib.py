@@ -4,6 +4,7 @@ There is no CPU fallback: if the library is missing, or an entry point fails, th
 """
 import ctypes
 import os
+import re
 
 # torch must be in the process BEFORE the library is loaded: torch ships its own libamdhip64 and the library links
 # the system one under the same soname.  Whichever loads first serves both; if it is the system copy, torch's
@@ -15,118 +16,52 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # QEFT_HIP_LIB: load another build of the same ABI (A/B timing of two builds on one GPU box); never a fallback
 LIB_PATH = os.environ.get("QEFT_HIP_LIB") or os.path.join(_HERE, "lib", "libqeft_hip.so")
 
-_p, _i = ctypes.c_void_p, ctypes.c_int
-
-# name -> argtypes, exactly as declared in include/qeft_hip.h
-SIGNATURES = {
-    "qeft_abi_version": [],
-    "qeft_error_string": [_i],
-    "qeft_last_hip_error": [],
-    "qeft_last_variant": [],
-    "qeft_gemv_w4": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_gemv_w4_qeft": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_gemv_w4_fused": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_pack_scales": [_p, _p, _p, _i, _i, _i, _p],
-    "qeft_gemm_w4": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_gemm_w4_workspace_bytes": [_i, _i, _i, _i],
-    "qeft_gemm_w4_silu_mul": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_gemm_w4_gateup_supported": [_i, _i, _i, _i, _i],
-    "qeft_gemm_w4_gateup": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_gemm_w4_ws": [_p, _p, _p, _p, _p, _p, _p, _p, ctypes.c_longlong, _i, _i, _i, _i, _i, _p],
-    "qeft_gemm_w4_dx": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_gemm_w4_dx_workspace_bytes": [_i, _i, _i],
-    "qeft_gemm_w4_dx_ws": [_p, _p, _p, _p, _p, _p, _p, ctypes.c_longlong, _i, _i, _i, _i, _i, _p],
-    "qeft_grad_oweight": [_p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_dequant_w4": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_pack_oweight": [_p, _p, _i, _i, _p],
-    "qeft_gemv_w4_group": [_p, _p, ctypes.c_float, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "qeft_gemv_w4_silu": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_rmsnorm": [_p, _p, _p, _p, _p, _i, _i, ctypes.c_float, _p],
-    "qeft_silu_mul": [_p, _p, _p, _i, _p],
-    "qeft_gemv_w3": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_gemv_w3_group": [_p, _p, ctypes.c_float, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "qeft_gemv_w3_silu": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_expand_w3": [_p, _p, _i, _i, _i, _p],
-    "qeft_gemm_w3_supported": [_i, _i, _i, _i, _i],
-    "qeft_gemm_w3": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_gemm_w3_dx_supported": [_i, _i, _i, _i, _i],
-    "qeft_gemm_w3_dx": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_attn_workspace_bytes": [_i, _i],
-    "qeft_token_begin": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "qeft_token_end": [_p, _p, _p, _i, _i, _p],
-    "qeft_decode_linear_blocks": [_i],
-    "qeft_decode_linear": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, ctypes.c_float, _p, _p, _p, _p],
-    "qeft_decode_linear_w3": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, ctypes.c_float, _p, _p, _p, _p],
-    "qeft_gemv_v3_check_extents": [_i, _i, _i, _i, _i, _i],
-    "qeft_gemv_v3_check_extents_ckpt": [_i, _i, _i, _i, _i, _i, _i],
-    "qeft_decode_linear_hnorm": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, ctypes.c_float, _p],
-    "qeft_token_begin_norm_blocks": [_i],
-    "qeft_token_begin_norm": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "qeft_rmsnorm_f32": [_p, _p, _p, _i, _i, ctypes.c_float, _p],
-    "qeft_lm_head_f16": [_p, _p, _p, _p, _i, _i, ctypes.c_float, _p],
-    "qeft_rope_rows": [_p, _p, _p, _i, _i, _i, _p],
-    "qeft_residual_norm": [_p, _p, _p, _p, _p, _p, _i, _p],
-    "qeft_single_query_attention": [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p],
-    "qeft_single_query_attention_alibi": [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p],
-    "qeft_single_query_attention_generic": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
-    "qeft_rope_attn_decode": [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_decode_linear_m": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, ctypes.c_float, _p, _p, _p, _i, _p],
-    "qeft_gemv_v3_check_extents_m": [_i, _i, _i, _i, _i, _i, _i, _i],
-    "qeft_token_begin_norm_m": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_attn_m_workspace_bytes": [_i, _i, _i],
-    "qeft_rope_attn_decode_m": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_lm_head_f16_m": [_p, _p, _p, _p, _i, _i, ctypes.c_float, _i, _p],
-    "qeft_verify_greedy": [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p],
-    "qeft_token_begin_norm_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_attn_batch_workspace_bytes": [_i, _i, _i],
-    "qeft_rope_attn_decode_batch": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
-    "qeft_attn_kv8_workspace_bytes": [_i, _i, _i],
-    "qeft_rope_attn_decode_kv8": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
-    "qeft_kv8_store_rows": [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_attn_m_kv8_workspace_bytes": [_i, _i, _i],
-    "qeft_rope_attn_decode_m_kv8": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_attn_prefill": [_p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_attn_prefill_check_extents": [_i, _i, _i, _i, _i, _i, _i],
-    "qeft_attn_prefill_kv8": [_p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
-    "qeft_attn_prefill_kv8_check_extents": [_i, _i, _i, _i, _i, _i, _i, _i],
-    "qeft_attn_train_fwd": [_p, _i, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p],
-    "qeft_attn_train_check_extents": [_i, _i, _i, _i, _i, _i, _i],
-    "qeft_attn_train_bwd_workspace_bytes": [_i, _i, _i, _i],
-    "qeft_attn_train_bwd": [_p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p, ctypes.c_longlong, _i, _i, _i, _i, _p],
-    "qeft_attn_train_bwd_part": [_p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p, ctypes.c_longlong, _i, _i, _i, _i, _i, _p],
-    "qeft_attn_train_bwd_check_extents": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i],
-    "qeft_add_rmsnorm_fwd": [_p, _p, _p, _p, _p, _i, _i, ctypes.c_float, _p],
-    "qeft_add_rmsnorm_bwd": [_p, _p, _p, _p, _p, _i, _i, ctypes.c_float, _p],
-    "qeft_swiglu_fwd": [_p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_swiglu_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "qeft_train_glue_check_extents": [_i, _i, _i, _i, _i, _i, _i, _i],
-    "qeft_lm_head_nll_workspace_bytes": [_i, _i],
-    "qeft_lm_head_nll": [_p, _i, _p, _p, _p, _p, _p, _p, ctypes.c_longlong, _i, _i, _i, _p],
-    "qeft_lm_head_nll_check_extents": [_i, _i, _i, _i],
-    "qeft_lm_head_nll_grad_chunk_rows": [_i, _i],
-    "qeft_lm_head_nll_grad_workspace_bytes": [_i, _i, _i],
-    "qeft_lm_head_nll_grad": [_p, _i, _p, _p, _p, _p, _p, _i, _i, _p, ctypes.c_longlong, _i, _i, _i, _p],
-    "qeft_lm_head_nll_grad_check_extents": [_i, _i, _i, _i, _i],
-    "qeft_token_end_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_sample": [_p, _i, _i, _p, _p, _p, _p],
-    "qeft_token_end_sample": [_p, _p, _p, _i, _p, _p],
-    "qeft_token_end_sample_batch": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "qeft_verify_sample": [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p],
-    "qeft_oneshot_mailbox_bytes": [_i, _i],
-    "qeft_oneshot_max_world": [],
-    "qeft_oneshot_mailbox_alloc": [_i, _i, ctypes.POINTER(ctypes.c_void_p)],
-    "qeft_oneshot_mailbox_free": [_p],
-    "qeft_oneshot_ipc_export": [_p, _p],
-    "qeft_oneshot_ipc_open": [_p, ctypes.POINTER(ctypes.c_void_p)],
-    "qeft_oneshot_ipc_close": [_p],
-    "qeft_oneshot_allreduce_f32": [_p, _i, ctypes.POINTER(ctypes.c_void_p), _i, _i, _p, _p, _p],
-}
-
-_lib = None
+HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "qeft_hip.h"))
 
 
 class QeftHipError(RuntimeError):
     pass
+
+
+_ARG = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong, "qeft_stream_t": ctypes.c_void_p}
+_RET = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "const char*": ctypes.c_char_p}
+
+
+def parse_header(text):
+    """[(name, restype, argtypes)] of every `ret qeft_name(params);` in the header text, in order of declaration.
+    A pointer of any kind is c_void_p; a type that neither table knows raises -- a guess here would truncate a device address."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)                    # some sit inside parameter lists
+    text = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    protos = []
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(qeft_\w+)\s*\(([^()]*)\)\s*;", text):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RET:
+            raise QeftHipError(f"{name}: return type '{ret}' has no ctypes mapping")
+        argtypes = []
+        for param in (params.split(",") if params.strip() != "void" else []):
+            words = param.split()                                        # the last one is the parameter's name
+            ctype = ctypes.c_void_p if "*" in param else _ARG.get(" ".join(words[:-1]))
+            if ctype is None:
+                raise QeftHipError(f"{name}: parameter '{' '.join(words)}' has no ctypes mapping")
+            argtypes.append(ctype)
+        protos.append((name, _RET[ret], argtypes))
+    return protos
+
+
+def _read_header():
+    try:
+        with open(HEADER) as f:
+            return f.read()
+    except OSError as e:
+        raise QeftHipError(f"{HEADER} not readable ({e}): the ctypes binding is derived from it") from None
+
+
+# name -> argtypes / restype, as include/qeft_hip.h declares them
+_PROTOS = parse_header(_read_header())
+SIGNATURES = {name: argtypes for name, _, argtypes in _PROTOS}
+RESTYPES = {name: restype for name, restype, _ in _PROTOS}
+
+_lib = None
 
 
 def lib():
@@ -141,24 +76,13 @@ def lib():
         for name, argtypes in SIGNATURES.items():
             fn = getattr(l, name, None)
             if fn is None:
-                # only an explicitly selected A/B build (QEFT_HIP_LIB) may be older than this table; the in-tree library must
-                # export every entry (tests/test_cabi.py checks it against include/qeft_hip.h as well)
+                # only an explicitly selected A/B build (QEFT_HIP_LIB) may be older than the header; the in-tree library must
+                # export every entry
                 if os.environ.get("QEFT_HIP_LIB"):
                     continue
                 raise QeftHipError(f"{LIB_PATH} does not export {name}: rebuild it (python -m qeft_amd.build)")
             fn.argtypes = argtypes
-            fn.restype = (ctypes.c_char_p if name in ("qeft_error_string", "qeft_last_variant") else
-                          ctypes.c_longlong if name in ("qeft_gemm_w4_workspace_bytes", "qeft_gemm_w4_dx_workspace_bytes",
-                                                       "qeft_gemv_v3_check_extents", "qeft_gemv_v3_check_extents_ckpt",
-                                                       "qeft_gemv_v3_check_extents_m", "qeft_attn_prefill_check_extents",
-                                                       "qeft_attn_prefill_kv8_check_extents",
-                                                       "qeft_attn_train_check_extents", "qeft_attn_train_bwd_workspace_bytes",
-                                                       "qeft_attn_train_bwd_check_extents",
-                                                       "qeft_train_glue_check_extents",
-                                                       "qeft_lm_head_nll_workspace_bytes", "qeft_lm_head_nll_check_extents",
-                                                       "qeft_lm_head_nll_grad_workspace_bytes",
-                                                       "qeft_lm_head_nll_grad_check_extents",
-                                                       "qeft_oneshot_mailbox_bytes") else _i)
+            fn.restype = RESTYPES[name]
         _lib = l
     return _lib
 

@@ -14,7 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libqeft_hip.so")
 SOURCES = ["capi.hip", "gemv_w4.hip", "gemv_v3.hip", "gemv_v3_plain.hip", "gemv_v3_multi.hip", "gemv_w3.hip", "gemm_w4.hip", "gemm_ws.hip", "aux_w4.hip", "decode_aux.hip", "decode_verify.hip", "decode_batch.hip", "decode_attn_kv8.hip", "decode_verify_kv8.hip", "decode_sample.hip", "prefill_attn.hip", "prefill_attn_kv8.hip", "attn_train.hip", "train_glue.hip", "lm_head_nll.hip", "lm_head_nll_grad.hip", "oneshot.hip"]
-HEADERS = ["qeft_common.h", "gemv_w4_kernel.h", "gemv_w4_mfma.h", "gemv_v3.h", "gemv_v3_dispatch.h", "decode_attn.h", "decode_rows.h", "decode_kv8.h", "prefill_attn.h", "prefill_attn_body.h", "attn_train.h", "train_glue.h", "lm_head_nll_body.h", os.path.join("..", "..", "include", "qeft_hip.h")]
+# every header a source may include: an edit to any of them rebuilds (SOURCES stays explicit: a stray .hip must not enter the library)
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "qeft_hip.h")]
 ARCH = "gfx950"
 
 

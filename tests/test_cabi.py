@@ -32,6 +32,89 @@ def test_header_symbols_all_exported(lib):
     assert set(syms) == set(_lib.SIGNATURES), "ctypes table and header disagree"
 
 
+def test_binding_parser_agrees_with_an_independent_extraction():
+    """qeft_amd/_lib.py derives the ctypes tables from the header.  The names it finds are those of declared_symbols() (another
+    regex, which knows nothing of types), and it yields one prototype per name: none parsed twice, none dropped."""
+    from qeft_amd import _lib
+    protos = _lib.parse_header(open(os.path.join(ROOT, "include", "qeft_hip.h")).read())
+    names = [name for name, _, _ in protos]
+    assert sorted(names) == declared_symbols()          # declared_symbols() is a sorted set: equal lists = no duplicate either
+    assert len(protos) == len(declared_symbols()) >= 101
+    assert _lib.SIGNATURES == {name: argtypes for name, _, argtypes in protos}
+    assert _lib.RESTYPES == {name: restype for name, restype, _ in protos}
+
+
+def test_binding_of_one_entry_per_type_class(lib):
+    """Expected types written out from the header by hand, one entry per kind of thing the parser has to get right; the loaded
+    functions carry them."""
+    from qeft_amd import _lib
+    p, i, f, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
+    want = {
+        "qeft_abi_version": (i, []),                                              # (void)
+        "qeft_error_string": (ctypes.c_char_p, [i]),                              # returns const char*
+        "qeft_lm_head_nll_workspace_bytes": (ll, [i, i]),                         # returns long long
+        "qeft_gemm_w4_ws": (i, [p] * 8 + [ll] + [i] * 5 + [p]),                   # a long long parameter
+        "qeft_gemv_w4_group": (i, [p, p, f, i] + [p] * 8 + [i] * 3 + [p]),        # float, const void* const*, void* const*
+        "qeft_oneshot_ipc_export": (i, [p, p]),                                   # a comment inside the parameter list
+        "qeft_rope_attn_decode_kv8": (i, [p, p, p, i, p, p, i, i] + [p] * 9 + [i, p] + [i] * 6 + [p]),      # 26 parameters
+        "qeft_attn_train_bwd_part": (i, [p, i, p, p, i, p, i, p, i, p, p, i, p, p, i, p, ll] + [i] * 5 + [p]),
+    }
+    assert len(want["qeft_rope_attn_decode_kv8"][1]) == 26 and len(want["qeft_attn_train_bwd_part"][1]) == 23
+    for name, (restype, argtypes) in want.items():
+        assert _lib.RESTYPES[name] is restype, name
+        assert _lib.SIGNATURES[name] == argtypes, name
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
+def test_binding_parser_refuses_what_it_does_not_know():
+    """An unknown type raises and names the entry and the type: an int assumed where the header has something else would hand a
+    kernel a truncated address or count.  The parser takes text, so the real header is not touched."""
+    from qeft_amd import _lib
+    p, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    good = """
+        #define QEFT_X 1  /* a macro that looks like a call: qeft_not_an_entry(1) */
+        typedef void* qeft_stream_t;
+        long long qeft_split(const void* x,   /* the input, */
+                             int rows,        // then a count (and a stray paren
+                             void* const* out /* 64 bytes; host */, long long bytes, float eps,
+                             qeft_stream_t stream);
+        const char * qeft_name(void);
+    """
+    assert _lib.parse_header(good) == [("qeft_split", ll, [p, i, p, ll, ctypes.c_float, p]), ("qeft_name", ctypes.c_char_p, [])]
+    for bad, word in (("int qeft_bad(const void* x, double scale);", "double"),
+                      ("int qeft_bad(const void* x, size_t n);", "size_t"),
+                      ("int qeft_bad(struct qeft_opts opts, int n);", "struct qeft_opts"),
+                      ("int qeft_bad(unsigned n);", "unsigned"),
+                      ("double qeft_bad(int n);", "double"),
+                      ("void* qeft_bad(int n);", "void*"),
+                      ("size_t qeft_bad(void);", "size_t")):
+        with pytest.raises(_lib.QeftHipError, match=r"qeft_bad.*" + re.escape(word)):
+            _lib.parse_header(bad)
+
+
+def test_missing_header_fails_loudly(monkeypatch):
+    from qeft_amd import _lib
+    monkeypatch.setattr(_lib, "HEADER", "/nonexistent/qeft_hip.h")
+    with pytest.raises(_lib.QeftHipError, match="/nonexistent/qeft_hip.h"):
+        _lib._read_header()
+
+
+def test_every_included_header_is_a_build_dependency():
+    """needs_build() looks at build.HEADERS alone: a header some source includes but the list lacks could be edited without a
+    rebuild, and the suite would run the old library."""
+    from qeft_amd import build
+    deps = {os.path.normpath(os.path.join(build.CSRC, h)) for h in build.HEADERS}
+    assert os.path.join(ROOT, "include", "qeft_hip.h") in deps
+    files = [f for f in sorted(os.listdir(build.CSRC)) if f.endswith((".hip", ".h"))]
+    assert set(build.SOURCES) <= set(files)
+    for f in files:
+        for inc in re.findall(r'^\s*#\s*include\s*"([^"]+)"', open(os.path.join(build.CSRC, f)).read(), flags=re.M):
+            path = os.path.normpath(os.path.join(build.CSRC, inc))
+            assert os.path.isfile(path), f"{f} includes {inc}, which does not exist"
+            assert path in deps, f"{f} includes {inc}, which is not in build.HEADERS"
+
+
 def test_abi_version_and_error_strings(lib):
     assert lib.qeft_abi_version() == 1
     assert lib.qeft_error_string(1).decode() == "Unsupported batch size for gemv kernel."

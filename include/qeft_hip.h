@@ -140,6 +140,24 @@ int qeft_gemm_w4_dx_ws(const void* dy, const void* qweight, const void* scales, 
 int qeft_grad_oweight(const void* dy, const void* x, void* d_oweight_f32, int m, int n, int k, int n_out,
                       qeft_stream_t stream);
 
+/* What the launchers behind qeft_gemm_w4* / qeft_gemm_w3 (forward), qeft_gemm_w4_dx* / qeft_gemm_w3_dx and qeft_grad_oweight
+ * would do for a shape: host arithmetic only, no GPU needed.  The forward entries route few rows (m <= 64) to the GEMV and
+ * weight-stationary tiers before their launcher is asked; these plans are the launcher's alone.
+ * out[QEFT_GEMM_PLAN_INTS] = { tier id, grid x, y, z, threads per block, dynamic LDS bytes, split factor S, 1 if the reduce
+ * launch follows, 1 if silu(gate) * y is fused into the epilogue, 1 if the shape is supported }; qeft_gemm_tier_name(tier id) is
+ * the name qeft_last_variant reports for the tier ("" for an id that is none).  n_out: the outlier width in effect (0 without
+ * oweight); bits 4 or 3; gate 0 none, 1 a gate tensor (qeft_gemm_w4_silu_mul), 2 the paired halves (qeft_gemm_w4_gateup);
+ * workspace_bytes 0: none.  overrides: NULL for the process's environment, else 8 ints in place of it -- QEFT_GEMM_V3, _V3M, _V3S
+ * (-1 unset), QEFT_GEMM_NWV, QEFT_DX_V3 (-1 unset), QEFT_DOW_BN, QEFT_GEMM_ABL (0 unset), and whether QEFT_GEMM_V1 is set.
+ * Return QEFT_OK, QEFT_ERR_NULL without `out`, QEFT_ERR_SHAPE for m, n < 1, k < 64, group_size < 1, n_out < 0 or another gate. */
+#define QEFT_GEMM_PLAN_INTS 10
+int qeft_gemm_w4_plan(int m, int n, int k, int group_size, int n_out, int bits, int gate, long long workspace_bytes,
+                      const int* overrides, int* out);
+int qeft_gemm_w4_dx_plan(int m, int n, int k, int group_size, int n_out, int bits, long long workspace_bytes,
+                         const int* overrides, int* out);
+int qeft_grad_oweight_plan(int n, int k, int n_out, const int* overrides, int* out);
+const char* qeft_gemm_tier_name(int tier);
+
 /* Dense dequantisation Wdeq[N,K] fp16 (validation / backward helper; the role of the uncompiled
  * dequantize_weight_4bit_qeft, qeft/kernel/quantization_new/dequantize/dequantize_cuda_qeft.cu:38-118).
  * oweight (plain [N, r]) may be NULL. */

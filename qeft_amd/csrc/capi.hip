@@ -7,6 +7,7 @@
 
 #include "../../include/qeft_hip.h"
 #include "qeft_common.h"
+#include "gemm_w4.h"
 #include "gemv_v3.h"
 #include "prefill_attn.h"
 #include "attn_train.h"
@@ -126,25 +127,9 @@ hipError_t dequant_w4_launch(const void* qw, const void* scales, const void* zer
                              int K, int G, int n_out, hipStream_t st);
 hipError_t pack_oweight_launch(const void* ow, void* il, int N, int R, hipStream_t st);
 hipError_t pack_scales_launch(const void* scales, const void* zeros, void* out, int N, int ngroups, hipStream_t st);
-extern const void* const kSiluPair64;
-bool gemm_w4_pair64_ok(int M, int n2, int K, int G, int n_out);
 bool gemm_ws_supported(int m, int n, int k, int group_size, int n_out);                                  // gemm_ws.hip
 hipError_t gemm_ws_launch(const void* x, const void* qweight, const void* scales, const void* zeros, const void* oweight, const void* bias,
                           void* y, int m, int n, int k, int n_out, hipStream_t st);
-hipError_t gemm_w4_launch(const void* x, const void* qw, const void* scales, const void* zeros, const void* ow,
-                          const void* bias, void* y, int M, int N, int K, int G, int n_out, hipStream_t st,
-                          void* workspace = nullptr, size_t workspace_bytes = 0, const void* silu_gate = nullptr,
-                          bool* fused_epilogue = nullptr, int bits = 4);
-int gemm_w3_native_tile(int M, int N, int K, int G, int n_out);
-bool gemm_w3_dx_native(int M, int N, int K, int G, int n_out);
-int gemm_w4_split(int M, int N, int K, int n_out);
-int gemm_v3_split(int M, int N, int K, int n_out);
-hipError_t gemm_w4_dx_launch(const void* dy, const void* qw, const void* scales, const void* zeros, const void* ow,
-                             void* dx, int M, int N, int K, int G, int n_out, hipStream_t st, void* workspace = nullptr,
-                             size_t workspace_bytes = 0, int bits = 4);
-int gemm_w4_dx_split(int M, int N, int K);
-hipError_t grad_oweight_launch(const void* dy, const void* x, void* dow, int M, int N, int K, int n_out,
-                               hipStream_t st);
 }  // namespace qeft
 
 static thread_local int g_last_hip_error = 0;
@@ -513,7 +498,7 @@ int qeft_gemm_w4_dx(const void* dy, const void* qweight, const void* scales, con
 
 long long qeft_gemm_w4_dx_workspace_bytes(int m, int n, int k) {
     if (m < 1 || n < 1 || k < 64 || k % 4 != 0) return 0;
-    if (k % 128 == 0 && ((m + 127) / 128) * (k / 128) >= 512) return 0;       // the 128-wide tile: no split
+    if (qeft::gemm_dx128_takes(m, k)) return 0;       // the 128-wide tile: no split
     const int s = qeft::gemm_w4_dx_split(m, n, k);
     return s > 1 ? (long long)s * m * k * 4 : 0;
 }
@@ -532,6 +517,44 @@ int qeft_grad_oweight(const void* dy, const void* x, void* d_oweight_f32, int m,
     if (!dy || !x || !d_oweight_f32) return QEFT_ERR_NULL;
     return finish(qeft::grad_oweight_launch(dy, x, d_oweight_f32, m, n, k, n_out, (hipStream_t)stream));
 }
+
+/* ---- the launchers' plans as integers: no HIP call, no GPU needed (tests/test_gemm_plan.py) */
+static qeft::GemmOverrides overrides_from(const int* v) {
+    if (!v) return qeft::gemm_overrides();
+    qeft::GemmOverrides o;
+    o.v3 = v[0], o.v3m = v[1], o.v3s = v[2], o.nwv = v[3], o.dx_v3 = v[4], o.dow_bn = v[5], o.abl = v[6], o.v1 = v[7] != 0;
+    return o;
+}
+static int plan_out(const qeft::GemmPlan& p, int* out) {
+    const int v[QEFT_GEMM_PLAN_INTS] = {p.tier, (int)p.gx, (int)p.gy, (int)p.gz, p.threads, p.lds, p.S, p.reduce(), p.fused, p.supported()};
+    memcpy(out, v, sizeof(v));
+    return QEFT_OK;
+}
+// (the plans divide by tile counts: at least one row, one column and one 64-wide k-tile)
+static int plan_args(int m, int n, int k, int g, int n_out, const int* out) {
+    return !out ? QEFT_ERR_NULL : (m < 1 || n < 1 || k < 64 || g < 1 || n_out < 0) ? QEFT_ERR_SHAPE : QEFT_OK;
+}
+
+int qeft_gemm_w4_plan(int m, int n, int k, int group_size, int n_out, int bits, int gate, long long workspace_bytes,
+                      const int* overrides, int* out) {
+    if (int e = plan_args(m, n, k, group_size, n_out, out)) return e;
+    if (gate < 0 || gate > 2) return QEFT_ERR_SHAPE;
+    return plan_out(qeft::gemm_w4_plan(m, n, k, group_size, n_out, bits, gate, workspace_bytes > 0 ? (size_t)workspace_bytes : 0,
+                                       overrides_from(overrides)), out);
+}
+
+int qeft_gemm_w4_dx_plan(int m, int n, int k, int group_size, int n_out, int bits, long long workspace_bytes, const int* overrides,
+                         int* out) {
+    if (int e = plan_args(m, n, k, group_size, n_out, out)) return e;
+    return plan_out(qeft::gemm_w4_dx_plan(m, n, k, group_size, n_out, bits, workspace_bytes > 0 ? (size_t)workspace_bytes : 0,
+                                          overrides_from(overrides)), out);
+}
+
+int qeft_grad_oweight_plan(int n, int k, int n_out, const int* overrides, int* out) {
+    return out ? plan_out(qeft::grad_oweight_plan(n, k, n_out, overrides_from(overrides)), out) : QEFT_ERR_NULL;
+}
+
+const char* qeft_gemm_tier_name(int tier) { return qeft::gemm_tier_variant(tier); }
 
 int qeft_dequant_w4(const void* qweight, const void* scales, const void* scaled_zeros, const void* oweight,
                     void* w_out, int n, int k, int group_size, int n_out, qeft_stream_t stream) {

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "qeft_common.h"
+#include "gemm_w4.h"
 
 namespace qeft {
 
@@ -429,7 +430,8 @@ __global__ __launch_bounds__(64 * NWV) void gemm_w4_kernel_v2(const f16* __restr
 constexpr int G3_BM = 256, G3_BN = 128, G3_ST = 4, G3_BST = 6;
 constexpr int G3_A = G3_BM * BK * 2, G3_B = G3_BN * BK / 2, G3_S = 512;
 constexpr int G3_BOFF = G3_ST * G3_A, G3_SOFF = G3_BOFF + G3_BST * G3_B;      // [4 x A 32 KB][6 x B 4 KB][6 x scales 512 B]
-constexpr size_t G3_SMEM = (size_t)G3_SOFF + G3_BST * G3_S;                   // 158720 bytes
+constexpr int gemm_v3_smem(int mt) { return G3_ST * 32 * mt * BK * 2 + G3_BST * G3_B + G3_BST * G3_S; }   // a block of 32 * mt rows: 158720 / 93184 bytes
+static_assert(gemm_v3_smem(8) == G3_SOFF + G3_BST * G3_S, "the 256-row ring is the layout above");
 constexpr int G3_YP = G3_BN * 2 + 16;     // pitch of the fp16 output tile staged in LDS for the epilogue (256 rows: 68 KB of the ring)
 
 // n DMA pieces of 1 KB: lane's 16 bytes at (sbase + voff_i) -> LDS[lds_dst + 1024 i + 16 lane], i = 0..7 (one asm statement:
@@ -907,14 +909,50 @@ int gemm_w4_split(int M, int N, int K, int n_out) {
     return s < 2 ? 1 : s;
 }
 
-// silu_gate == kSiluPair64: the paired-halves epilogue (EPI 2) instead of an external gate tensor
 extern const void* const kSiluPair64 = (const void*)(uintptr_t)1;
+
+// tier -> name, written as the launchers' assignment of g_last_variant: the statement tests/test_variant_census.py reads the names from
+static const char* set_last_variant(int tier) {
+    return g_last_variant =
+        tier == kFwdV1 ? "gemm_v1" : tier == kFwdV2 ? "gemm_v2_128x128" : tier == kFwdV2SplitK ? "gemm_v2_128x128+splitk" :
+        tier == kFwdV2x256 ? "gemm_v2_128x256" : tier == kFwdV3x128 ? "gemm_v3_128x128" :
+        tier == kFwdV3x128SplitK ? "gemm_v3_128x128+splitk" : tier == kFwdV3x256 ? "gemm_v3_256x128" :
+        tier == kFwdV3x256Silu ? "gemm_v3_256x128+silu" : tier == kFwdV3x256SiluPair ? "gemm_v3_256x128+silu_pair" :
+        tier == kFwdV3x128W3 ? "gemm_v3_128x128_w3" : tier == kFwdV3x256W3 ? "gemm_v3_256x128_w3" :
+        tier == kDx64 ? "dx64" : tier == kDx64Split ? "dx64+split" : tier == kDx128 ? "dx128" : tier == kDx128V3 ? "dx128v3" :
+        tier == kDx256 ? "dx256" : tier == kDx128V3W3 ? "dx128v3_w3" : tier == kDx256W3 ? "dx256_w3" :
+        tier == kDowFma ? "grad_oweight_fma" : tier == kDowMfma ? "grad_oweight_mfma" :
+        tier == kDowMfmaN64 ? "grad_oweight_mfma_n64" : "";
+}
+const char* gemm_tier_variant(int tier) {      // the same table as a query: the calling thread's last variant stays what it was
+    const char* const last = g_last_variant, * const name = set_last_variant(tier);
+    g_last_variant = last;
+    return name;
+}
+
+static int env_int(const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; }
+GemmOverrides gemm_overrides() {
+    static const GemmOverrides once = {env_int("QEFT_GEMM_V3", -1), env_int("QEFT_GEMM_V3M", -1), env_int("QEFT_GEMM_V3S", -1),
+                                       env_int("QEFT_GEMM_NWV", 0),  env_int("QEFT_DX_V3", -1),    env_int("QEFT_DOW_BN", 0),
+                                       env_int("QEFT_GEMM_ABL", 0),  false};      // in the order of the struct's members
+    GemmOverrides o = once;
+    o.v1 = getenv("QEFT_GEMM_V1") != nullptr;
+    return o;
+}
+
+// What every user of the loader-wave forward kernel asks of a shape (`ok3`); each adds the bounds of its own weight stream and
+// output tile next to the call.
+// (at least two INT4 k-tiles: with exactly one, the odd-count prologue of the k loop would dequantise k-tile 1 -- an fp16
+//  outlier tile whose weight slot was never staged -- as INT4; such shapes keep the 128-row kernels)
+static bool gemm_v3_ok(int M, int K, int G, int n_out) {
+    return K / BK >= G3_BST && K % BK == 0 && n_out % 64 == 0 && (K - n_out) / BK >= 2 && (G & (G - 1)) == 0 && G >= 64 &&
+           (size_t)M * K * 2 < (1ull << 32);
+}
+static bool gemm_w4_stream_ok(int N, int K) { return (size_t)(N / 4) * K * 2 < (1ull << 32); }      // byte offsets into qweight fit 32 bits
 
 // shapes the paired gate|up launch takes (n2 = both linears' rows): the 256-row kernel's domain, whole 128-column tiles
 bool gemm_w4_pair64_ok(int M, int n2, int K, int G, int n_out) {
-    return M >= 1 && n2 % 128 == 0 && K / BK >= G3_BST && K % BK == 0 && n_out % 64 == 0 && (K - n_out) / BK >= 2 &&
-           (G & (G - 1)) == 0 && G >= 64 &&
-           (size_t)M * K * 2 < (1ull << 32) && (size_t)(n2 / 4) * K * 2 < (1ull << 32);
+    return M >= 1 && n2 % 128 == 0 && gemm_v3_ok(M, K, G, n_out) && gemm_w4_stream_ok(n2, K);
 }
 
 // 256-row or 128-row loader-wave tile?  One block per CU either way; a launch takes ceil(tiles / 256) rounds of blocks, a partly
@@ -922,6 +960,7 @@ bool gemm_w4_pair64_ok(int M, int n2, int K, int G, int n_out) {
 // profiles/r04_gemm_m_sweep.txt -- 52-57 us against 31-35 us per round at K = 4096).  The tile with the cheaper sum of rounds wins,
 // ties go to the 256-row tile.  Round 4 dropped round 2's unconditional "M >= 1024 -> 256 rows": 11008 x 4096 at M = 1408 is 516
 // tiles of 256 rows = THREE rounds (167 us) but 946 of 128 rows = four cheaper ones.
+static bool gemm_v3_takes_128(int M, int N) { return ((M + 127) / 128) * ((N + G3_BN - 1) / G3_BN) >= 112 && M > 128; }
 static bool gemm_v3_prefers_256(int M, int N) {
     const int nb = (N + G3_BN - 1) / G3_BN, t8 = ((M + G3_BM - 1) / G3_BM) * nb, t4 = ((M + 127) / 128) * nb;
     if (M <= 256 || t8 < 129) return false;
@@ -940,172 +979,124 @@ int gemm_v3_split(int M, int N, int K, int n_out) {
 
 // The tiers that read the 3-bit extension layout directly (0: none -- expand first; 8 / 4: the 256- / 128-row loader-wave tile)
 int gemm_w3_native_tile(int M, int N, int K, int G, int n_out) {
-    const int nb = (N + G3_BN - 1) / G3_BN;
-    const bool ok = K % 128 == 0 && n_out % 128 == 0 && n_out < K && (K - n_out) / BK >= 2 && K / BK >= G3_BST && N % 16 == 0 &&
-                    (G & (G - 1)) == 0 && G >= 64 && (size_t)M * K * 2 < (1ull << 32) &&
+    // whole 128-k records of 16 rows (768 bytes each), byte offsets into the 3-bit stream within 32 bits
+    const bool ok = gemm_v3_ok(M, K, G, n_out) && K % 128 == 0 && n_out % 128 == 0 && n_out < K && N % 16 == 0 &&
                     (size_t)(N / 16) * ((K - n_out) / 128) * 768 < (1ull << 32);
     if (!ok) return 0;
     if (gemm_v3_prefers_256(M, N)) return 8;
-    if (((M + 127) / 128) * nb >= 112 && M > 128) return 4;
-    return 0;
+    return gemm_v3_takes_128(M, N) ? 4 : 0;
+}
+
+// a loader-wave launch: one 512-thread block per tile of 32 * mt rows x 128 columns and per split
+static GemmPlan gemm_v3_plan(int tier, int mt, int bits, int M, int N, int n_out, int S = 1) {
+    GemmPlan p;
+    p.tier = tier, p.outl = n_out > 0, p.tile = mt, p.bits = bits, p.S = S;
+    p.gx = ((M + 32 * mt - 1) / (32 * mt)) * ((N + G3_BN - 1) / G3_BN) * S, p.threads = 512, p.lds = gemm_v3_smem(mt);
+    return p;
+}
+
+GemmPlan gemm_w4_plan(int M, int N, int K, int G, int n_out, int bits, int gate, size_t workspace_bytes, const GemmOverrides& ov) {
+    if (bits == 3) {
+        const int tile = gate ? 0 : gemm_w3_native_tile(M, N, K, G, n_out);
+        return tile ? gemm_v3_plan(tile == 8 ? kFwdV3x256W3 : kFwdV3x128W3, tile, 3, M, N, n_out) : GemmPlan();
+    }
+    const bool ok3 = gemm_v3_ok(M, K, G, n_out) && N % 4 == 0 && N >= 2 && gemm_w4_stream_ok(N, K);
+    if (gate == kGatePair && !(ok3 && N % 128 == 0)) return GemmPlan();      // capi checks gemm_w4_pair64_ok first
+    // 256 x 128 tiles, one wave per SIMD (gemm_w4_kernel_v3), when they give (nearly) every CU a block: the M >= 2048 tier
+    // of a prefill / fine-tune step.  QEFT_GEMM_V3 = 0 / 1 forces the choice (A/B).
+    if (ok3 && (gate == kGatePair || ov.v3 == 1 || (ov.v3 != 0 && gemm_v3_prefers_256(M, N))) && (!gate || N % 8 == 0)) {
+        GemmPlan p = gemm_v3_plan(gate == kGatePair ? kFwdV3x256SiluPair : gate ? kFwdV3x256Silu : kFwdV3x256, 8, 4, M, N, n_out);
+        p.epi = gate, p.fused = gate != kGateNone;      // the tier that forms silu(gate) * y in its own epilogue
+#ifdef QEFT_LAB      // lab builds only (QEFT_BUILD_LAB=1 python -m qeft_amd.build): ablations / time stamps, wrong results by design
+        if (!gate && ov.abl >= 1 && ov.abl <= 6) p.abl = ov.abl, p.outl = true;      // (the six instances exist with OUTL only)
+#endif
+        return p;
+    }
+    // The same design with 128-row tiles (round 3) for the sizes between the small-M kernels and that tier -- M = 512 .. 1024
+    // of a short prompt or a fine-tune batch, narrow N at larger M: taken from 112 tiles of 128 x 128 on (measured crossover
+    // against the 128-row kernels below, profiles/r03_gemm_mid_m.txt: 4096 x 4096 at M = 512, 128 tiles: 28.4 vs 34.6 us;
+    // 11008 x 4096 at M = 256, 172 tiles: 30.4 vs 43.6; 64 tiles lose).  QEFT_GEMM_V3M = 0 / 1 forces the choice.
+    // fewer than 192 tiles and a workspace: S blocks per tile, fp32 partials, the reduce launch (QEFT_GEMM_V3S=0 disables)
+    const int S3 = (ov.v3s == 0 || ov.v3m == 0 || !workspace_bytes || gate || !ok3) ? 1 : gemm_v3_split(M, N, K, n_out);
+    if (S3 > 1 && workspace_bytes >= (size_t)S3 * M * N * 4) return gemm_v3_plan(kFwdV3x128SplitK, 4, 4, M, N, n_out, S3);
+    if (ok3 && !gate && (ov.v3m == 1 || (ov.v3m != 0 && gemm_v3_takes_128(M, N)))) return gemm_v3_plan(kFwdV3x128, 4, 4, M, N, n_out);
+    // 128 x 256 tiles (8 waves) when they still give every CU a block: always a gain where the 128 x 128 kernel's scale
+    // array leaves room for one block per CU only (K = 11008: 747 -> 945 TFLOP/s at M = 2048), a few % otherwise at
+    // M >= 2048; smaller problems keep the 128 x 128 tile (more blocks).  QEFT_GEMM_NWV = 4 / 8 forces one (A/B).
+    const bool one_block4 = gemm_v2_smem(K, G, 4) > 80 * 1024;
+    int nwv = ov.nwv == 8 || (ov.nwv == 0 && N % 256 == 0 && ((M + BM - 1) / BM) * (N / 256) >= 256 && (one_block4 || M >= 2048)) ? 8 : 4;
+    if (gemm_v2_smem(K, G, nwv) > 160 * 1024) nwv = 4;
+    int S = workspace_bytes ? gemm_w4_split(M, N, K, n_out) : 1;
+    if (nwv == 8 || N % 4 != 0) S = 1;      // (the reduce launch writes four columns at a time)
+    while (S > 1 && (size_t)S * M * N * 4 > workspace_bytes) --S;
+    const size_t smem2 = gemm_v2_smem(K, G, nwv);
+    GemmPlan p;
+    p.outl = n_out > 0, p.gx = (M + BM - 1) / BM;
+    if (K / BK >= kStages && n_out % 64 == 0 && (G & (G - 1)) == 0 && smem2 <= 160 * 1024 && !ov.v1) {
+        p.tier = nwv == 8 ? kFwdV2x256 : S > 1 ? kFwdV2SplitK : kFwdV2;
+        p.tile = nwv, p.gy = (N + 32 * nwv - 1) / (32 * nwv), p.gz = S, p.threads = 64 * nwv, p.lds = (int)smem2, p.S = S;
+    } else {
+        p.tier = kFwdV1, p.gy = (N + BN - 1) / BN, p.threads = GEMM_THREADS;
+    }
+    return p;
+}
+
+// The one place a planned kernel is launched: dynamic LDS needs the opt-in above 64 KB.
+template <typename Kern, typename... Args>
+static hipError_t launch_planned(Kern kern, const GemmPlan& p, hipStream_t st, Args... args) {
+    const hipError_t e = p.lds ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds) : hipSuccess;
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(p.gx, p.gy, p.gz), dim3(p.threads), p.lds, st, args...);
+    return hipGetLastError();
+}
+
+// the second launch of a split plan: out[rows][cols] = fp16(the S partials summed in a fixed order + bias)
+static hipError_t launch_splitk_reduce(const void* part, const void* bias, void* out, int rows, int cols, int S, hipStream_t st) {
+    const size_t quads = (size_t)rows * cols / 4;
+    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((int)((quads + 255) / 256)), dim3(256), 0, st, (const float*)part,
+                       (const f16*)bias, (f16*)out, rows, cols, S);
+    return hipGetLastError();
 }
 
 hipError_t gemm_w4_launch(const void* x, const void* qw, const void* scales, const void* zeros, const void* ow,
                           const void* bias, void* y, int M, int N, int K, int G, int n_out, hipStream_t st,
                           void* workspace, size_t workspace_bytes, const void* silu_gate, bool* fused_epilogue, int bits) {
-    const bool outl = ow && n_out > 0;
-    if (fused_epilogue) *fused_epilogue = false;      // set by the tier that forms silu(gate) * y in its own epilogue
-    if (bits == 3) {
-        const int tile = silu_gate ? 0 : gemm_w3_native_tile(M, N, K, G, outl ? n_out : 0);
-        if (!tile) return hipErrorNotSupported;
-        const int nb = (N + G3_BN - 1) / G3_BN, mbt = (M + 32 * tile - 1) / (32 * tile);
-        const int smem = G3_ST * 32 * tile * BK * 2 + G3_BST * G3_B + G3_BST * G3_S;
-        auto go = [&](auto kern) -> hipError_t {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3(mbt * nb), dim3(512), smem, st, (const f16*)x, (const uint8_t*)qw, (const f16*)scales,
-                               (const f16*)zeros, (const f16*)(outl ? ow : nullptr), (const f16*)bias, (f16*)y, M, N, K, G,
-                               outl ? n_out : 0, nb, (const f16*)nullptr, (float*)nullptr, 1);
-            return hipGetLastError();
-        };
-        g_last_variant = tile == 8 ? "gemm_v3_256x128_w3" : "gemm_v3_128x128_w3";
-        if (tile == 8) return outl ? go(gemm_w4_kernel_v3<true, 0, 0, 8, 3>) : go(gemm_w4_kernel_v3<false, 0, 0, 8, 3>);
-        return outl ? go(gemm_w4_kernel_v3<true, 0, 0, 4, 3>) : go(gemm_w4_kernel_v3<false, 0, 0, 4, 3>);
-    }
-    // 256 x 128 tiles, one wave per SIMD (gemm_w4_kernel_v3), when they give (nearly) every CU a block: the M >= 2048 tier
-    // of a prefill / fine-tune step.  QEFT_GEMM_V3 = 0 / 1 forces the choice (A/B).
-    {
-        static const int force_v3 = getenv("QEFT_GEMM_V3") ? atoi(getenv("QEFT_GEMM_V3")) : -1;
-        const int mb = (M + G3_BM - 1) / G3_BM, nb = (N + G3_BN - 1) / G3_BN;
-        // (at least two INT4 k-tiles: with exactly one, the odd-count prologue of the k loop would dequantise k-tile 1 -- an fp16
-        //  outlier tile whose weight slot was never staged -- as INT4; such shapes keep the 128-row kernels)
-        const bool ok3 = K / BK >= G3_BST && K % BK == 0 && (!outl || n_out % 64 == 0) && (K - (outl ? n_out : 0)) / BK >= 2 &&
-                         (G & (G - 1)) == 0 && G >= 64 && N % 4 == 0 && N >= 2 && (size_t)M * K * 2 < (1ull << 32) && (size_t)(N / 4) * K * 2 < (1ull << 32);
-        if (silu_gate == kSiluPair64 && !(ok3 && N % 128 == 0)) return hipErrorNotSupported;     // capi checks gemm_w4_pair64_ok first
-        if (ok3 && (silu_gate == kSiluPair64 || force_v3 == 1 || (force_v3 != 0 && gemm_v3_prefers_256(M, N))) &&
-            (!silu_gate || N % 8 == 0)) {
-            auto go3 = [&](auto kern) -> hipError_t {
-                hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G3_SMEM);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(kern, dim3(mb * nb), dim3(512), G3_SMEM, st, (const f16*)x, (const uint8_t*)qw,
-                                   (const f16*)scales, (const f16*)zeros, (const f16*)(outl ? ow : nullptr), (const f16*)bias,
-                                   (f16*)y, M, N, K, G, outl ? n_out : 0, nb, (const f16*)silu_gate, (float*)nullptr, 1);
-                return hipGetLastError();
-            };
-            if (silu_gate == kSiluPair64) {
-                if (fused_epilogue) *fused_epilogue = true;
-                g_last_variant = "gemm_v3_256x128+silu_pair";
-                return outl ? go3(gemm_w4_kernel_v3<true, 0, 2>) : go3(gemm_w4_kernel_v3<false, 0, 2>);
-            }
-            if (silu_gate) {
-                if (fused_epilogue) *fused_epilogue = true;
-                g_last_variant = "gemm_v3_256x128+silu";
-                return outl ? go3(gemm_w4_kernel_v3<true, 0, 1>) : go3(gemm_w4_kernel_v3<false, 0, 1>);
-            }
-            g_last_variant = "gemm_v3_256x128";
-#ifdef QEFT_LAB      // lab builds only (QEFT_BUILD_LAB=1 python -m qeft_amd.build): ablations / time stamps, wrong results by design
-            static const int abl = getenv("QEFT_GEMM_ABL") ? atoi(getenv("QEFT_GEMM_ABL")) : 0;
-            if (abl == 1) return go3(gemm_w4_kernel_v3<true, 1>);
-            if (abl == 2) return go3(gemm_w4_kernel_v3<true, 2>);
-            if (abl == 3) return go3(gemm_w4_kernel_v3<true, 3>);
-            if (abl == 4) return go3(gemm_w4_kernel_v3<true, 4>);
-            if (abl == 5) return go3(gemm_w4_kernel_v3<true, 5>);
-            if (abl == 6) return go3(gemm_w4_kernel_v3<true, 6>);
+    if (!(ow && n_out > 0)) ow = nullptr, n_out = 0;
+    const int gate = silu_gate == kSiluPair64 ? kGatePair : silu_gate ? kGateTensor : kGateNone;
+    const GemmPlan p = gemm_w4_plan(M, N, K, G, n_out, bits, gate, workspace ? workspace_bytes : 0, gemm_overrides());
+    if (fused_epilogue) *fused_epilogue = p.fused;
+    if (!p.supported()) return hipErrorNotSupported;
+    set_last_variant(p.tier);
+    // one helper per kernel family: the arguments all share, then its own tail (a split loader-wave plan leaves the bias to the reduce)
+    const auto go = [&](auto kern, const void* b, auto... tail) {
+        return launch_planned(kern, p, st, (const f16*)x, (const uint8_t*)qw, (const f16*)scales, (const f16*)zeros, (const f16*)ow,
+                              (const f16*)b, (f16*)y, M, N, K, G, n_out, tail...);
+    };
+    const auto v1 = [&](auto kern) { return go(kern, bias); };
+    const auto v2 = [&](auto kern) { return go(kern, bias, (float*)workspace); };
+    const auto v3 = [&](auto kern) {
+        return go(kern, p.reduce() ? nullptr : bias, (N + G3_BN - 1) / G3_BN, (const f16*)silu_gate, (float*)(p.reduce() ? workspace : nullptr), p.S);
+    };
+    hipError_t e;
+    if (p.tier == kFwdV1) e = p.outl ? v1(gemm_w4_kernel<true>) : v1(gemm_w4_kernel<false>);
+    else if (p.tier == kFwdV2 || p.tier == kFwdV2SplitK) e = p.outl ? v2(gemm_w4_kernel_v2<true, 4>) : v2(gemm_w4_kernel_v2<false, 4>);
+    else if (p.tier == kFwdV2x256) e = p.outl ? v2(gemm_w4_kernel_v2<true, 8>) : v2(gemm_w4_kernel_v2<false, 8>);
+    else if (p.bits == 3 && p.tile == 8) e = p.outl ? v3(gemm_w4_kernel_v3<true, 0, 0, 8, 3>) : v3(gemm_w4_kernel_v3<false, 0, 0, 8, 3>);
+    else if (p.bits == 3) e = p.outl ? v3(gemm_w4_kernel_v3<true, 0, 0, 4, 3>) : v3(gemm_w4_kernel_v3<false, 0, 0, 4, 3>);
+    else if (p.tile == 4) e = p.outl ? v3(gemm_w4_kernel_v3<true, 0, 0, 4>) : v3(gemm_w4_kernel_v3<false, 0, 0, 4>);
+    else if (p.epi == 2) e = p.outl ? v3(gemm_w4_kernel_v3<true, 0, 2>) : v3(gemm_w4_kernel_v3<false, 0, 2>);
+    else if (p.epi == 1) e = p.outl ? v3(gemm_w4_kernel_v3<true, 0, 1>) : v3(gemm_w4_kernel_v3<false, 0, 1>);
+#ifdef QEFT_LAB
+    else if (p.abl == 1) e = v3(gemm_w4_kernel_v3<true, 1>);
+    else if (p.abl == 2) e = v3(gemm_w4_kernel_v3<true, 2>);
+    else if (p.abl == 3) e = v3(gemm_w4_kernel_v3<true, 3>);
+    else if (p.abl == 4) e = v3(gemm_w4_kernel_v3<true, 4>);
+    else if (p.abl == 5) e = v3(gemm_w4_kernel_v3<true, 5>);
+    else if (p.abl == 6) e = v3(gemm_w4_kernel_v3<true, 6>);
 #endif
-            return outl ? go3(gemm_w4_kernel_v3<true>) : go3(gemm_w4_kernel_v3<false>);
-        }
-        // The same design with 128-row tiles (round 3) for the sizes between the small-M kernels and that tier -- M = 512 .. 1024
-        // of a short prompt or a fine-tune batch, narrow N at larger M: taken from 112 tiles of 128 x 128 on (measured crossover
-        // against the 128-row kernels below, profiles/r03_gemm_mid_m.txt: 4096 x 4096 at M = 512, 128 tiles: 28.4 vs 34.6 us;
-        // 11008 x 4096 at M = 256, 172 tiles: 30.4 vs 43.6; 64 tiles lose).  QEFT_GEMM_V3M = 0 / 1 forces the choice.
-        {
-            static const int force_m = getenv("QEFT_GEMM_V3M") ? atoi(getenv("QEFT_GEMM_V3M")) : -1;
-            const int mb4 = (M + 127) / 128;
-            // fewer than 192 tiles and a workspace: S blocks per tile, fp32 partials, the reduce launch (QEFT_GEMM_V3S=0 disables)
-            static const int force_s = getenv("QEFT_GEMM_V3S") ? atoi(getenv("QEFT_GEMM_V3S")) : -1;
-            const int S3 = (force_s == 0 || force_m == 0 || !workspace || silu_gate || !ok3) ? 1 : gemm_v3_split(M, N, K, outl ? n_out : 0);
-            if (S3 > 1 && workspace_bytes >= (size_t)S3 * M * N * 4) {
-                constexpr int SMEM4 = G3_ST * 128 * BK * 2 + G3_BST * G3_B + G3_BST * G3_S;
-                auto go4 = [&](auto kern) -> hipError_t {
-                    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM4);
-                    if (e != hipSuccess) return e;
-                    hipLaunchKernelGGL(kern, dim3(mb4 * nb * S3), dim3(512), SMEM4, st, (const f16*)x, (const uint8_t*)qw,
-                                       (const f16*)scales, (const f16*)zeros, (const f16*)(outl ? ow : nullptr), (const f16*)nullptr,
-                                       (f16*)y, M, N, K, G, outl ? n_out : 0, nb, (const f16*)nullptr, (float*)workspace, S3);
-                    return hipGetLastError();
-                };
-                g_last_variant = "gemm_v3_128x128+splitk";
-                hipError_t e = outl ? go4(gemm_w4_kernel_v3<true, 0, 0, 4>) : go4(gemm_w4_kernel_v3<false, 0, 0, 4>);
-                if (e != hipSuccess) return e;
-                const size_t quads = (size_t)M * N / 4;
-                hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((int)((quads + 255) / 256)), dim3(256), 0, st,
-                                   (const float*)workspace, (const f16*)bias, (f16*)y, M, N, S3);
-                return hipGetLastError();
-            }
-            if (ok3 && !silu_gate && (force_m == 1 || (force_m != 0 && mb4 * nb >= 112 && M > 128))) {
-                constexpr int SMEM4 = G3_ST * 128 * BK * 2 + G3_BST * G3_B + G3_BST * G3_S;         // 93184 bytes
-                auto go4 = [&](auto kern) -> hipError_t {
-                    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM4);
-                    if (e != hipSuccess) return e;
-                    hipLaunchKernelGGL(kern, dim3(mb4 * nb), dim3(512), SMEM4, st, (const f16*)x, (const uint8_t*)qw,
-                                       (const f16*)scales, (const f16*)zeros, (const f16*)(outl ? ow : nullptr), (const f16*)bias,
-                                       (f16*)y, M, N, K, G, outl ? n_out : 0, nb, (const f16*)nullptr, (float*)nullptr, 1);
-                    return hipGetLastError();
-                };
-                g_last_variant = "gemm_v3_128x128";
-                return outl ? go4(gemm_w4_kernel_v3<true, 0, 0, 4>) : go4(gemm_w4_kernel_v3<false, 0, 0, 4>);
-            }
-        }
-    }
-    // 128 x 256 tiles (8 waves) when they still give every CU a block: always a gain where the 128 x 128 kernel's scale
-    // array leaves room for one block per CU only (K = 11008: 747 -> 945 TFLOP/s at M = 2048), a few % otherwise at
-    // M >= 2048; smaller problems keep the 128 x 128 tile (more blocks).  QEFT_GEMM_NWV = 4 / 8 forces one (A/B).
-    static const int force_nwv = getenv("QEFT_GEMM_NWV") ? atoi(getenv("QEFT_GEMM_NWV")) : 0;
-    int nwv = 4;
-    const bool one_block4 = gemm_v2_smem(K, G, 4) > 80 * 1024;
-    if (force_nwv == 8 || (force_nwv == 0 && N % 256 == 0 && ((M + BM - 1) / BM) * (N / 256) >= 256 && (one_block4 || M >= 2048)))
-        nwv = 8;
-    if (gemm_v2_smem(K, G, nwv) > 160 * 1024) nwv = 4;
-    const int bn = 32 * nwv;
-    dim3 grid((M + BM - 1) / BM, (N + bn - 1) / bn);
-    int S = workspace ? gemm_w4_split(M, N, K, outl ? n_out : 0) : 1;
-    if (nwv == 8) S = 1;
-    while (S > 1 && (size_t)S * M * N * 4 > workspace_bytes) --S;
-    if (N % 4 != 0) S = 1;
-    const size_t smem2 = gemm_v2_smem(K, G, nwv);
-    if (K / BK >= kStages && (!outl || n_out % 64 == 0) && (G & (G - 1)) == 0 && smem2 <= 160 * 1024 &&
-        getenv("QEFT_GEMM_V1") == nullptr) {
-        auto go = [&](auto kern) -> hipError_t {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3(grid.x, grid.y, S), dim3(64 * nwv), smem2, st, (const f16*)x, (const uint8_t*)qw,
-                               (const f16*)scales, (const f16*)zeros, (const f16*)(outl ? ow : nullptr), (const f16*)bias,
-                               (f16*)y, M, N, K, G, outl ? n_out : 0, (float*)workspace);
-            return hipGetLastError();
-        };
-        hipError_t e;
-        if (nwv == 8) e = outl ? go(gemm_w4_kernel_v2<true, 8>) : go(gemm_w4_kernel_v2<false, 8>);
-        else e = outl ? go(gemm_w4_kernel_v2<true, 4>) : go(gemm_w4_kernel_v2<false, 4>);
-        if (e != hipSuccess) return e;
-        g_last_variant = nwv == 8 ? "gemm_v2_128x256" : (S > 1 ? "gemm_v2_128x128+splitk" : "gemm_v2_128x128");
-        if (S > 1) {
-            const size_t quads = (size_t)M * N / 4;
-            hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((int)((quads + 255) / 256)), dim3(256), 0, st,
-                               (const float*)workspace, (const f16*)bias, (f16*)y, M, N, S);
-        }
-        return hipGetLastError();
-    }
-    grid = dim3((M + BM - 1) / BM, (N + BN - 1) / BN);
-    g_last_variant = "gemm_v1";
-    if (ow && n_out > 0)
-        hipLaunchKernelGGL(gemm_w4_kernel<true>, grid, dim3(GEMM_THREADS), 0, st, (const f16*)x, (const uint8_t*)qw,
-                           (const f16*)scales, (const f16*)zeros, (const f16*)ow, (const f16*)bias, (f16*)y, M, N, K, G,
-                           n_out);
-    else
-        hipLaunchKernelGGL(gemm_w4_kernel<false>, grid, dim3(GEMM_THREADS), 0, st, (const f16*)x, (const uint8_t*)qw,
-                           (const f16*)scales, (const f16*)zeros, (const f16*)nullptr, (const f16*)bias, (f16*)y, M, N,
-                           K, G, 0);
-    return hipGetLastError();
+    else e = p.outl ? v3(gemm_w4_kernel_v3<true>) : v3(gemm_w4_kernel_v3<false>);
+    if (e != hipSuccess || !p.reduce()) return e;
+    return launch_splitk_reduce(workspace, bias, y, M, N, p.S, st);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1396,7 +1387,8 @@ __global__ __launch_bounds__(256) void gemm_w4_dx128_kernel(const f16* __restric
 constexpr int D3_BM = 256, D3_BK = 128, D3_BN = 64, D3_ST = 4;
 constexpr int D3_A = D3_BM * D3_BN * 2, D3_W = D3_BN * D3_BK * 2;        // 32 KB dy stage, 16 KB fp16 weight tile
 constexpr int D3_WOFF = D3_ST * D3_A;
-constexpr size_t D3_SMEM = (size_t)D3_WOFF + 2 * D3_W;                  // 163840 bytes: the whole LDS of a CU
+constexpr int gemm_dx_v3_smem(int mt) { return D3_ST * 32 * mt * D3_BN * 2 + 2 * D3_W; }   // 163840 (256 rows: the whole LDS of a CU) / 98304 bytes
+static_assert(gemm_dx_v3_smem(8) == D3_WOFF + 2 * D3_W, "the 256-row ring is the layout above");
 
 // The loader lanes' ring of weights in flight lives in ACCUMULATION registers named in the asm text (set S = a[8S .. 8S+5]:
 // 16 packed bytes, scale, zero).  The loads return long after the statement that issued them; a value hipcc could see would
@@ -1772,8 +1764,6 @@ int gemm_w4_dx_split(int M, int N, int K) {
     return s < 2 ? 1 : s;
 }
 
-// bits == 3: qw is the 3-bit extension layout; only the loader-wave tier reads it (hipErrorNotSupported otherwise: the caller
-// expands to the 4-bit layout, qeft_expand_w3, and comes back with bits == 4)
 // Tile of the loader-wave dX kernel for a shape: 8 (256 rows), 4 (128 rows) or 0 (the older kernels).  Same counting of rounds of
 // blocks as the forward's choice (gemm_v3_prefers_256; dx256 takes ~1.6x a dx128v3 block: 68 against 43 us per round on 4096^2):
 // the cheaper sum of rounds, ties to the 256-row tile; 128-row tiles from 112 tiles on (M > 128).
@@ -1791,64 +1781,50 @@ bool gemm_w3_dx_native(int M, int N, int K, int G, int n_out) {
     return gemm_dx_v3_ok(M, N, K, G, n_out) && (size_t)(N / 16) * ((K - n_out) / 128) * 768 < (1ull << 32) && gemm_dx_v3_tile(M, K) != 0;
 }
 
-template <int BITS>
-static hipError_t gemm_dx_v3_go(int tile, const void* dy, const void* qw, const void* scales, const void* zeros, const void* ow, void* dx,
-                                int M, int N, int K, int G, int n_out, hipStream_t st) {
-    const int kb = K / D3_BK, mbt = (M + 32 * tile - 1) / (32 * tile);
-    const int smem = D3_ST * 32 * tile * D3_BN * 2 + 2 * D3_W;          // 163840 (256 rows) / 98304 (128 rows) bytes
-    auto go = [&](auto kern) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(mbt * kb), dim3(512), smem, st, (const f16*)dy, (const uint8_t*)qw, (const f16*)scales,
-                           (const f16*)zeros, (const f16*)ow, (f16*)dx, M, N, K, G, n_out, kb);
-        return hipGetLastError();
-    };
-    return tile == 8 ? go(gemm_w4_dx_kernel_v3<BITS, 8>) : go(gemm_w4_dx_kernel_v3<BITS, 4>);
+// the 128-wide tile (gemm_w4_dx128_kernel, no split) when it still gives every CU two blocks
+bool gemm_dx128_takes(int M, int K) { return K % 128 == 0 && ((M + DX_BM - 1) / DX_BM) * (K / 128) >= 512; }
+
+GemmPlan gemm_w4_dx_plan(int M, int N, int K, int G, int n_out, int bits, size_t workspace_bytes, const GemmOverrides& ov) {
+    GemmPlan p;
+    p.outl = n_out > 0, p.bits = bits, p.threads = 256;
+    // bits == 3: qw is the 3-bit extension layout; only the loader-wave tier reads it (not supported otherwise: the caller
+    // expands to the 4-bit layout, qeft_expand_w3, and comes back with bits == 4)
+    if (bits == 3 && !gemm_w3_dx_native(M, N, K, G, n_out)) return p;
+    // Loader-wave tiles (gemm_w4_dx_kernel_v3): 256 x 128 when they give (nearly) every CU a block -- the M >= 2048 tier of a
+    // fine-tune step --, 128 x 128 below that (round 3).  QEFT_DX_V3 = 0 / 1 forces the choice (1: the 256-row tile) (A/B).
+    const int tile = bits == 3 ? gemm_dx_v3_tile(M, K) : ov.dx_v3 == 1 ? 8 : ov.dx_v3 == 0 ? 0 : gemm_dx_v3_tile(M, K);
+    if (tile && gemm_dx_v3_ok(M, N, K, G, n_out)) {
+        p.tier = bits == 3 ? (tile == 8 ? kDx256W3 : kDx128V3W3) : (tile == 8 ? kDx256 : kDx128V3);
+        p.tile = tile, p.gx = ((M + 32 * tile - 1) / (32 * tile)) * (K / D3_BK), p.threads = 512, p.lds = gemm_dx_v3_smem(tile);
+    } else if (gemm_dx128_takes(M, K) && n_out % 32 == 0) {
+        // smaller problems keep the 64-wide tile (twice the blocks, and a split over n below 512 of them)
+        p.tier = kDx128, p.gx = (M + DX_BM - 1) / DX_BM, p.gy = K / 128;
+    } else {
+        int S = workspace_bytes ? gemm_w4_dx_split(M, N, K) : 1;
+        while (S > 1 && (size_t)S * M * K * 4 > workspace_bytes) --S;
+        p.tier = S > 1 ? kDx64Split : kDx64, p.gx = (M + DX_BM - 1) / DX_BM, p.gy = K / DX_BK, p.gz = S, p.S = S;
+    }
+    return p;
 }
 
 hipError_t gemm_w4_dx_launch(const void* dy, const void* qw, const void* scales, const void* zeros, const void* ow,
                              void* dx, int M, int N, int K, int G, int n_out, hipStream_t st, void* workspace,
                              size_t workspace_bytes, int bits) {
-    const bool outl3 = ow && n_out > 0;
-    if (bits == 3) {
-        if (!gemm_w3_dx_native(M, N, K, G, outl3 ? n_out : 0)) return hipErrorNotSupported;
-        const int tile = gemm_dx_v3_tile(M, K);
-        g_last_variant = tile == 8 ? "dx256_w3" : "dx128v3_w3";
-        return gemm_dx_v3_go<3>(tile, dy, qw, scales, zeros, outl3 ? ow : nullptr, dx, M, N, K, G, outl3 ? n_out : 0, st);
-    }
-    // Loader-wave tiles (gemm_w4_dx_kernel_v3): 256 x 128 when they give (nearly) every CU a block -- the M >= 2048 tier of a
-    // fine-tune step --, 128 x 128 below that (round 3).  QEFT_DX_V3 = 0 / 1 forces the choice (1: the 256-row tile) (A/B).
-    {
-        static const int force_v3 = getenv("QEFT_DX_V3") ? atoi(getenv("QEFT_DX_V3")) : -1;
-        const int tile = force_v3 == 1 ? 8 : force_v3 == 0 ? 0 : gemm_dx_v3_tile(M, K);
-        if (tile && gemm_dx_v3_ok(M, N, K, G, outl3 ? n_out : 0)) {
-            g_last_variant = tile == 8 ? "dx256" : "dx128v3";
-            return gemm_dx_v3_go<4>(tile, dy, qw, scales, zeros, outl3 ? ow : nullptr, dx, M, N, K, G, outl3 ? n_out : 0, st);
-        }
-    }
-    // the 128-wide tile when it still gives every CU two blocks; smaller problems keep the 64-wide tile (twice the
-    // blocks, and a split over n below 512 of them)
-    if (K % 128 == 0 && n_out % 32 == 0 && ((M + DX_BM - 1) / DX_BM) * (K / 128) >= 512) {
-        dim3 grid2((M + DX_BM - 1) / DX_BM, K / 128);
-        hipLaunchKernelGGL(gemm_w4_dx128_kernel, grid2, dim3(256), 0, st, (const f16*)dy, (const uint8_t*)qw,
-                           (const f16*)scales, (const f16*)zeros, (n_out > 0 ? (const f16*)ow : (const f16*)nullptr),
-                           (f16*)dx, M, N, K, G, n_out);
-        g_last_variant = "dx128";
-        return hipGetLastError();
-    }
-    int S = workspace ? gemm_w4_dx_split(M, N, K) : 1;
-    while (S > 1 && (size_t)S * M * K * 4 > workspace_bytes) --S;
-    dim3 grid((M + DX_BM - 1) / DX_BM, K / DX_BK, S);
-    hipLaunchKernelGGL(gemm_w4_dx_kernel, grid, dim3(256), 0, st, (const f16*)dy, (const uint8_t*)qw,
-                       (const f16*)scales, (const f16*)zeros, (n_out > 0 ? (const f16*)ow : (const f16*)nullptr),
-                       (f16*)dx, M, N, K, G, n_out, (float*)workspace);
-    g_last_variant = S > 1 ? "dx64+split" : "dx64";
-    if (S > 1) {
-        const size_t quads = (size_t)M * K / 4;
-        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((int)((quads + 255) / 256)), dim3(256), 0, st,
-                           (const float*)workspace, (const f16*)nullptr, (f16*)dx, M, K, S);
-    }
-    return hipGetLastError();
+    if (!(ow && n_out > 0)) ow = nullptr, n_out = 0;
+    const GemmPlan p = gemm_w4_dx_plan(M, N, K, G, n_out, bits, workspace ? workspace_bytes : 0, gemm_overrides());
+    if (!p.supported()) return hipErrorNotSupported;
+    set_last_variant(p.tier);
+    const auto go = [&](auto kern, auto... tail) {
+        return launch_planned(kern, p, st, (const f16*)dy, (const uint8_t*)qw, (const f16*)scales, (const f16*)zeros, (const f16*)ow,
+                              (f16*)dx, M, N, K, G, n_out, tail...);
+    };
+    hipError_t e;
+    if (p.tier == kDx64 || p.tier == kDx64Split) e = go(gemm_w4_dx_kernel, (float*)workspace);
+    else if (p.tier == kDx128) e = go(gemm_w4_dx128_kernel);
+    else if (p.bits == 3) e = p.tile == 8 ? go(gemm_w4_dx_kernel_v3<3, 8>, K / D3_BK) : go(gemm_w4_dx_kernel_v3<3, 4>, K / D3_BK);
+    else e = p.tile == 8 ? go(gemm_w4_dx_kernel_v3<4, 8>, K / D3_BK) : go(gemm_w4_dx_kernel_v3<4, 4>, K / D3_BK);
+    if (e != hipSuccess || !p.reduce()) return e;
+    return launch_splitk_reduce(workspace, nullptr, dx, M, K, p.S, st);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2053,27 +2029,26 @@ __global__ __launch_bounds__(256) void grad_oweight_wave_kernel(const f16* __res
     }
 }
 
+GemmPlan grad_oweight_plan(int N, int K, int n_out, const GemmOverrides& ov) {
+    GemmPlan p;
+    p.threads = 256;
+    if (N % 8 == 0 && n_out % 8 == 0 && K % 8 == 0) {   // 16-byte row pieces
+        const int jb = (n_out + GO_BJ - 1) / GO_BJ;
+        const bool wide = ov.dow_bn ? ov.dow_bn == 64 : (N + 31) / 32 * jb > 512;
+        p.tier = wide ? kDowMfmaN64 : kDowMfma, p.tile = wide ? 64 : 32, p.gx = (N + p.tile - 1) / p.tile, p.gy = jb;
+    } else {
+        p.tier = kDowFma, p.gx = (N + 63) / 64, p.gy = (n_out + 63) / 64;
+    }
+    return p;
+}
+
 hipError_t grad_oweight_launch(const void* dy, const void* x, void* dow, int M, int N, int K, int n_out,
                                hipStream_t st) {
-    if (N % 8 == 0 && n_out % 8 == 0 && K % 8 == 0) {   // 16-byte row pieces
-        static const int force_bn = [] { const char* e = getenv("QEFT_DOW_BN"); return e ? atoi(e) : 0; }();
-        const int jb = (n_out + GO_BJ - 1) / GO_BJ;
-        const bool wide = force_bn ? force_bn == 64 : (N + 31) / 32 * jb > 512;
-        const dim3 grid2((N + (wide ? 63 : 31)) / (wide ? 64 : 32), jb);
-        if (wide)
-            hipLaunchKernelGGL((grad_oweight_wave_kernel<64, 2>), grid2, dim3(256), 0, st, (const f16*)dy, (const f16*)x,
-                               (float*)dow, M, N, K, n_out);
-        else
-            hipLaunchKernelGGL((grad_oweight_wave_kernel<32, 2>), grid2, dim3(256), 0, st, (const f16*)dy, (const f16*)x,
-                               (float*)dow, M, N, K, n_out);
-        g_last_variant = wide ? "grad_oweight_mfma_n64" : "grad_oweight_mfma";
-        return hipGetLastError();
-    }
-    g_last_variant = "grad_oweight_fma";
-    dim3 grid((N + 63) / 64, (n_out + 63) / 64);
-    hipLaunchKernelGGL(grad_oweight_kernel, grid, dim3(256), 0, st, (const f16*)dy, (const f16*)x, (float*)dow, M, N, K,
-                       n_out);
-    return hipGetLastError();
+    const GemmPlan p = grad_oweight_plan(N, K, n_out, gemm_overrides());
+    set_last_variant(p.tier);
+    const auto go = [&](auto kern) { return launch_planned(kern, p, st, (const f16*)dy, (const f16*)x, (float*)dow, M, N, K, n_out); };
+    if (p.tier == kDowFma) return go(grad_oweight_kernel);
+    return p.tile == 64 ? go(grad_oweight_wave_kernel<64, 2>) : go(grad_oweight_wave_kernel<32, 2>);
 }
 
 }  // namespace qeft

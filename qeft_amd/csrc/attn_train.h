@@ -72,4 +72,11 @@ __host__ __device__ inline int at_dkv_kvh(const AtGeom& A, int block) { return b
 __host__ __device__ inline int at_dkv_first_tile(int kblock) { return kblock * (AT_KB / AT_QT); }
 __host__ __device__ inline int at_dkv_end_tile(const AtGeom& A) { return (A.f.g.t - 1) / AT_QT + 1; }
 
+// ---- host side: attn_train.hip
+hipError_t attn_train_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, const AtGeom& A, hipStream_t st);
+hipError_t attn_train_bwd_launch(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse,
+                                 void* dq, void* dk, void* dv, float* delta, const AtGeom& A, int parts, hipStream_t st);
+long long attn_train_fwd_count_out_of_range(const AtGeom& A);
+long long attn_train_bwd_count_out_of_range(const AtGeom& A);
+
 }  // namespace qeft

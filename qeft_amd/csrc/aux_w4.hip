@@ -1,5 +1,6 @@
 // Small helper kernels: dense dequantisation and the outlier-slice interleave.
 #include "qeft_common.h"
+#include "host_launch.h"
 
 namespace qeft {
 

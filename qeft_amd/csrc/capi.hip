@@ -7,130 +7,14 @@
 
 #include "../../include/qeft_hip.h"
 #include "qeft_common.h"
+#include "host_launch.h"
 #include "gemm_w4.h"
 #include "gemv_v3.h"
+#include "decode_rows.h"
+#include "decode_kv8.h"
 #include "prefill_attn.h"
 #include "attn_train.h"
 #include "train_glue.h"
-
-namespace qeft {
-hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st);
-int gemv_v3_max_rows(V3Args a, int m_want);
-long long gemv_v3_count_out_of_range_ckpt(const V3Geom& G, int n_rows_have, int m, bool gather);
-int gemv_v3_blocks(int nsets);
-bool gemv_v3_ok(int K, int G, int n_out);
-long long gemv_v3_count_out_of_range(const V3Geom& G, int n_rows_have, int n_ssq_in, bool xn, int bits);
-hipError_t token_begin_norm_launch(const void* embed, const void* tok, const void* rope_tab, const int* pos, void* h,
-                                   void* rope_row, const void* gamma, void* hnorm, float* ssq_out, int hidden, int vocab,
-                                   int max_seq, hipStream_t st);
-int token_begin_norm_blocks(int hidden);
-hipError_t residual_norm_launch(const void* h, const void* add, const void* gamma, void* h_out, void* hnorm, float* ssq_out,
-                                int hidden, hipStream_t st);
-hipError_t rmsnorm_f32_launch(const void* x, const void* gamma, void* y, int m, int H, float eps, hipStream_t st);
-hipError_t rope_rows_launch(void* x, const void* cs, const void* sn, int T, int H, int row_stride, hipStream_t st);
-hipError_t lm_head_f16_launch(const void* h32, const void* gamma, const void* W, void* logits, int H, int vocab, float eps,
-                              hipStream_t st);
-hipError_t gemv_w4_dispatch(const GemvArgs& a, int m, hipStream_t st);
-hipError_t gemv_w4_group_dispatch(GemvGroupArgs g, int nparts, hipStream_t st);
-hipError_t gemv_w4_silu_dispatch(const GemvArgs& a, hipStream_t st);
-hipError_t gemv_w4_smallm_dispatch(const GemvArgs& a, int m, hipStream_t st);
-hipError_t gemv_w3_dispatch(const GemvArgs& a, int m, hipStream_t st);
-hipError_t gemv_w3_group_dispatch(GemvGroupArgs g, int nparts, hipStream_t st);
-hipError_t gemv_w3_silu_dispatch(const GemvArgs& a, hipStream_t st);
-hipError_t expand_w3_launch(const void* q3, void* q4, int N, int K, int n_out, hipStream_t st);
-hipError_t rmsnorm_launch(const void* x, const void* add, const void* gamma, void* res_out, void* y, int m, int H,
-                          float eps, hipStream_t st);
-hipError_t silu_mul_launch(const void* gate, const void* up, void* out, int n, hipStream_t st);
-hipError_t rope_attn_decode_launch(const void* q, const void* k, const void* v, const void* cs, const void* sn, void* kc,
-                                   void* vc, const int* pos, const int* out_pos, void* out, void* ws, int n_heads,
-                                   int n_kv, int max_seq, int S, int tab_rows, hipStream_t st, bool k_ft_layout = false,
-                                   const float* alibi_slopes = nullptr);
-size_t attn_workspace_bytes(int n_heads, int S);
-hipError_t sqa_generic_launch(const void* q, const void* k, const void* v, void* kc, void* vc, const int* pos, const float* alibi,
-                              void* out, int n_heads, int n_kv, int max_seq, int head_dim, hipStream_t st);
-hipError_t token_begin_launch(const void* embed, const void* tok, const void* rope_tab, const int* pos, void* h,
-                              void* rope_row, int hidden, int vocab, int max_seq, hipStream_t st);
-hipError_t token_end_launch(const void* logits, void* tok, int* pos, int vocab, int greedy, hipStream_t st);
-hipError_t gemv_v3_multi_launch(V3Args a, int mode, hipStream_t st);                                   // gemv_v3_multi.hip
-long long gemv_v3_count_out_of_range_multi(const V3Geom& G, int n_rows_have, int m, int mode, int n_ssq_in);
-hipError_t token_begin_norm_m_launch(const void* embed, const void* toks, const void* rope_tab, const int* pos, void* h,  // decode_verify.hip
-                                     void* rope_rows, const void* gamma, void* hnorm, float* ssq_out, int hidden, int vocab,
-                                     int max_seq, int m, hipStream_t st);
-size_t attn_m_workspace_bytes(int n_heads, int S, int m);
-hipError_t rope_attn_m_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
-                              int tab_stride, int tab_rows, void* kc, void* vc, const int* pos, const int* out_pos, void* out,
-                              int out_stride, void* ws, int n_heads, int n_kv, int max_seq, int S, int m, hipStream_t st);
-hipError_t lm_head_m_launch(const void* h32, const void* gamma, const void* W, void* logits, int H, int vocab, float eps, int m,
-                            hipStream_t st);
-hipError_t verify_greedy_launch(const void* logits, const void* tokens, int m, int vocab, int greedy, void* out_tokens, int* n_acc,
-                                void* tok, int* pos, hipStream_t st);
-hipError_t token_begin_norm_b_launch(const void* embed, const void* toks, const void* rope_tab, const int* slot_tab,  // decode_batch.hip
-                                     const int* pos_tab, void* h, void* rope_rows, const void* gamma, void* hnorm, float* ssq_out,
-                                     int hidden, int vocab, int max_seq, int n_slots, int m, hipStream_t st);
-size_t attn_b_workspace_bytes(int n_heads, int S, int m);
-hipError_t rope_attn_b_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
-                              int tab_stride, int tab_rows, void* kc, void* vc, const int* slot_tab, const int* pos_tab,
-                              const int* done, const int* out_pos, void* out, int out_stride, void* ws, int n_slots, int n_heads,
-                              int n_kv, int max_seq, int S, int m, hipStream_t st);
-hipError_t token_end_b_launch(const void* logits, const int* slot_tab, void* tok, int* pos_tab, const int* limit, const int* eos,
-                              int* done, void* out, int* ctr, int vocab, int out_cap, int n_slots, int m, hipStream_t st);
-size_t attn_kv8_workspace_bytes(int n_heads, int S, int m);                                                           // decode_attn_kv8.hip
-hipError_t rope_attn_kv8_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
-                                int tab_stride, int tab_rows, void* kc, void* vc, void* ks, void* vs, const int* slot_tab,
-                                const int* pos_tab, const int* done, const int* out_pos, void* out, int out_stride, void* ws,
-                                int n_slots, int n_heads, int n_kv, int max_seq, int S, int m, hipStream_t st);
-// decode_verify_kv8.hip
-hipError_t rope_attn_m_kv8_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
-                                  int tab_stride, int tab_rows, void* kc, void* vc, void* ks, void* vs, const int* pos,
-                                  const int* out_pos, void* out, int out_stride, void* ws, int n_heads, int n_kv, int max_seq, int S,
-                                  int m, hipStream_t st);
-hipError_t kv8_store_rows_launch(const void* k, const void* v, int row_stride, void* kc, void* vc, void* ks, void* vs, int n_kv,
-                                 int max_seq, int p0, int T, hipStream_t st);
-extern unsigned long long* g_attn_dbg;
-hipError_t prefill_attn_launch(const void* q, const void* kc, const void* vc, void* out, const PaGeom& G, hipStream_t st);   // prefill_attn.hip
-long long prefill_attn_count_out_of_range(const PaGeom& G);
-hipError_t prefill_attn_kv8_launch(const void* q, const void* kq, const void* vq, const void* ksc, const void* vsc, const void* kn,
-                                   const void* vn, void* out, const Pa8Geom& G8, hipStream_t st);   // prefill_attn_kv8.hip
-long long prefill_attn_kv8_count_out_of_range(const Pa8Geom& G8);
-hipError_t attn_train_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, const AtGeom& A, hipStream_t st);   // attn_train.hip
-hipError_t attn_train_bwd_launch(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse,
-                                 void* dq, void* dk, void* dv, float* delta, const AtGeom& A, int parts, hipStream_t st);
-long long attn_train_fwd_count_out_of_range(const AtGeom& A);
-long long attn_train_bwd_count_out_of_range(const AtGeom& A);
-hipError_t add_rmsnorm_fwd_launch(const void* h, const void* add, const void* gamma, void* sum_out, void* y, const TgNorm& G, float eps,
-                                  hipStream_t st);                                                                       // train_glue.hip
-hipError_t add_rmsnorm_bwd_launch(const void* s, const void* gamma, const void* dy, const void* dres, void* dsum, const TgNorm& G,
-                                  float eps, hipStream_t st);
-hipError_t swiglu_fwd_launch(const void* gate, const void* up, void* out, const TgSwiglu& G, hipStream_t st);
-hipError_t swiglu_bwd_launch(const void* gate, const void* up, const void* dact, void* dgate, void* dup, const TgSwiglu& G,
-                             hipStream_t st);
-long long train_glue_norm_count_out_of_range(const TgNorm& G);
-long long train_glue_swiglu_count_out_of_range(const TgSwiglu& G, bool backward);
-size_t lm_head_nll_workspace_bytes(int t, int vocab);                                                                 // lm_head_nll.hip
-hipError_t lm_head_nll_launch(const void* x, const void* w, const int* targets, float* lse, float* tgt_logit, int* argmax, void* ws,
-                              int x_stride, int t, int hidden, int vocab, hipStream_t st);
-long long lm_head_nll_count_out_of_range(int x_stride, int t, int hidden, int vocab);
-int lm_head_nll_grad_chunk_rows();                                                                                    // lm_head_nll_grad.hip
-size_t lm_head_nll_grad_workspace_bytes(int t, int vocab);
-hipError_t lm_head_nll_grad_launch(const void* x, const void* w, const int* targets, const float* lse, const float* grad_nll, void* dx,
-                                   void* ws, int x_stride, int dx_stride, int dx_fp32, int t, int hidden, int vocab, hipStream_t st);
-long long lm_head_nll_grad_count_out_of_range(int x_stride, int dx_stride, int t, int hidden, int vocab);
-hipError_t sample_launch(const void* logits, int vocab, int m, const int* params, const int* positions, void* tokens,  // decode_sample.hip
-                         hipStream_t st);
-hipError_t token_end_sample_launch(const void* logits, void* tok, int* pos, const int* params, int vocab, hipStream_t st);
-hipError_t verify_sample_launch(const void* logits, const void* tokens, int m, int vocab, const int* params, int* work, void* out_tokens,
-                                int* n_acc, void* tok, int* pos, hipStream_t st);
-hipError_t token_end_sample_b_launch(const void* logits, const int* slot_tab, void* tok, int* pos_tab, const int* limit, const int* eos,
-                                     int* done, void* out, int* ctr, const int* params, int vocab, int out_cap, int n_slots, int m,
-                                     hipStream_t st);
-hipError_t dequant_w4_launch(const void* qw, const void* scales, const void* zeros, const void* ow, void* out, int N,
-                             int K, int G, int n_out, hipStream_t st);
-hipError_t pack_oweight_launch(const void* ow, void* il, int N, int R, hipStream_t st);
-hipError_t pack_scales_launch(const void* scales, const void* zeros, void* out, int N, int ngroups, hipStream_t st);
-bool gemm_ws_supported(int m, int n, int k, int group_size, int n_out);                                  // gemm_ws.hip
-hipError_t gemm_ws_launch(const void* x, const void* qweight, const void* scales, const void* zeros, const void* oweight, const void* bias,
-                          void* y, int m, int n, int k, int n_out, hipStream_t st);
-}  // namespace qeft
 
 static thread_local int g_last_hip_error = 0;
 thread_local const char* qeft::g_last_variant = "";
@@ -203,6 +87,36 @@ const char* qeft_error_string(int code) {
     }
 }
 
+// ---- v3 decode GEMV (gemv_v3.h).  v3_geom is the only code that fills a V3Geom, v3_args the only code that starts a V3Args.
+static int v3_geom(qeft::V3Geom& G, int n, int k, int group_size, int n_out, int mode) {
+    if (mode != qeft::V3_MODE_PLAIN && mode != qeft::V3_MODE_PAIR) return QEFT_ERR_SHAPE;
+    if (n <= 0 || n % 16 != 0) return QEFT_ERR_SHAPE;
+    if (k <= 0 || group_size <= 0 || k % group_size != 0) return QEFT_ERR_GROUP;
+    if (!qeft::gemv_v3_ok(k, group_size, n_out)) return QEFT_ERR_SHAPE;
+    G.K = k;
+    G.n_out = n_out;
+    G.nsteps = k / 128;
+    G.nfull = (k - n_out) / 128;
+    G.ngroups = group_size == k ? 1 : k / 128;
+    G.nsets = n / 16;
+    return QEFT_OK;
+}
+
+// The pack of a v3 launch: the geometry, and the operands every launch names.  The rest stays zero; what a caller adds (the
+// checkpoint-layout operands, the epilogue, xn_gamma, bits, m) it sets by name.
+static int v3_args(qeft::V3Args& a, const void* x, const void* qweight, const void* sz_packed, const void* oweight, const void* bias,
+                   void* y, int n, int k, int group_size, int n_out, int mode) {
+    a = qeft::V3Args{};
+    if (int e = v3_geom(a.g, n, k, group_size, n_out, mode)) return e;
+    a.x = (const qeft::f16*)x;
+    a.qw = (const uint8_t*)qweight;
+    a.szp = (const uint8_t*)sz_packed;
+    a.ow = (const uint8_t*)oweight;
+    a.bias = (const qeft::f16*)bias;
+    a.y = (qeft::f16*)y;
+    return QEFT_OK;
+}
+
 // m batch rows (1..16 per launch) through the v3 decode GEMV on the operands as the CHECKPOINT holds them (gemv_v3.h): the
 // scales staged raw and packed in LDS (or the sz_packed shadow when the caller has one), the outlier slab from
 // oweight_interleaved (the gemv entries) or the plain oweight [n, r] (the GEMM entries), the o_proj gather inside the
@@ -211,14 +125,10 @@ const char* qeft_error_string(int code) {
 constexpr int V3_NOT_TAKEN = -1000;
 // launches v3_rows would make for m rows of this shape on checkpoint-layout operands (0: the kernel does not serve it)
 static int v3_rows_launches(int m, int n, int k, int group_size, int n_out) {
-    if (m < 1 || !v3_route_enabled() || n <= 0 || n % 16 != 0 || !qeft::gemv_v3_ok(k, group_size, n_out)) return 0;
-    qeft::V3Args v{};
-    v.g.K = k;
-    v.g.n_out = n_out;
-    v.g.nsteps = k / 128;
-    v.g.nfull = (k - n_out) / 128;
-    v.g.ngroups = group_size == k ? 1 : k / 128;
-    v.g.nsets = n / 16;
+    qeft::V3Args v;      // (the geometry alone: v3_lds sizes the checkpoint-layout launch by szp == NULL)
+    if (m < 1 || !v3_route_enabled() ||
+        v3_args(v, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, k, group_size, n_out, qeft::V3_MODE_PLAIN) != QEFT_OK)
+        return 0;
     int mmax = qeft::gemv_v3_max_rows(v, m);
     if (mmax < m && m > 1 && xg_route_enabled()) {
         v.xg = true;
@@ -230,23 +140,14 @@ constexpr int kGemmRowsOnGemvLaunches = 2;      // the GEMM entries put up to 16
 static int v3_rows(const void* x, const void* qweight, const void* scales, const void* scaled_zeros, const void* oweight_plain,
                    const void* oweight_il, const void* bias, const int* reorder_ids, const void* sz_packed, void* y, int m, int n,
                    int k, int group_size, int n_out, qeft_stream_t stream, int max_launches) {
-    if (!v3_route_enabled() || n % 16 != 0 || !qeft::gemv_v3_ok(k, group_size, n_out) || !aligned16(scales) || !aligned16(scaled_zeros) ||
-        (reorder_ids && !aligned16(reorder_ids)))
+    qeft::V3Args v;      // (x and y: per launch, below)
+    if (!v3_route_enabled() ||
+        v3_args(v, nullptr, qweight, sz_packed, oweight_plain, bias, nullptr, n, k, group_size, n_out, qeft::V3_MODE_PLAIN) != QEFT_OK ||
+        !aligned16(scales) || !aligned16(scaled_zeros) || (reorder_ids && !aligned16(reorder_ids)))
         return V3_NOT_TAKEN;
-    qeft::V3Args v{};
-    v.g.K = k;
-    v.g.n_out = n_out;
-    v.g.nsteps = k / 128;
-    v.g.nfull = (k - n_out) / 128;
-    v.g.ngroups = group_size == k ? 1 : k / 128;
-    v.g.nsets = n / 16;
-    v.qw = (const uint8_t*)qweight;
-    v.szp = (const uint8_t*)sz_packed;
     v.scales = (const qeft::f16*)scales;
     v.zeros = (const qeft::f16*)scaled_zeros;
-    v.ow = (const uint8_t*)oweight_plain;
     v.ow_il = (const uint8_t*)oweight_il;
-    v.bias = (const qeft::f16*)bias;
     v.ids = reorder_ids;
     int mmax = qeft::gemv_v3_max_rows(v, m);
     if ((mmax < m || xg_route_mode() == 2) && m > 1 && !reorder_ids && xg_route_enabled()) {
@@ -267,6 +168,29 @@ static int v3_rows(const void* x, const void* qweight, const void* scales, const
     return QEFT_OK;
 }
 
+// The pack of the round-1 GEMV kernels (gemv_w4.hip, gemv_w3.hip): value-initialised, then the operands every site names.
+// What differs between the sites -- where x comes from, the outlier slice as ow_il or ow_plain, ids, residual, xt_aux,
+// sz_blk -- each sets by name (profiles/capi_builders_refactor.log lists every field per site).
+// gshift: log2 of a power-of-two group, 31 for one group per row.  0 for any other group: only gemm_impl's small-M branch
+// gets here with one, the GEMV entries have answered QEFT_ERR_GROUP before they build the pack.
+static qeft::GemvArgs gemv_args(const void* x, const void* qweight, const void* scales, const void* scaled_zeros, const void* bias,
+                                void* y, int n, int k, int group_size, int n_out) {
+    qeft::GemvArgs a{};
+    a.x = (const qeft::f16*)x;
+    a.qw = (const uint8_t*)qweight;
+    a.scales = (const qeft::f16*)scales;
+    a.zeros = (const qeft::f16*)scaled_zeros;
+    a.bias = (const qeft::f16*)bias;
+    a.y = (qeft::f16*)y;
+    a.N = n;
+    a.K = k;
+    a.G = group_size;
+    a.n_out = n_out;
+    a.gshift = group_size == k ? 31 : (group_size & (group_size - 1)) == 0 ? __builtin_ctz(group_size) : 0;
+    a.m_rt = 1;
+    return a;
+}
+
 static int gemv_fused_impl(const void* x, const void* qweight, const void* scales, const void* scaled_zeros,
                            const void* oweight_il, const void* bias, const int* reorder_ids, const void* residual,
                            const void* sz_packed, void* y, int m, int n, int k, int group_size, int n_out,
@@ -281,29 +205,12 @@ static int gemv_fused_impl(const void* x, const void* qweight, const void* scale
                               n_out, stream, 1 << 30);
         if (r != V3_NOT_TAKEN) return r;
     }
-    qeft::GemvArgs a;
-    a.x = (const qeft::f16*)x;
-    a.qw = (const uint8_t*)qweight;
-    a.scales = (const qeft::f16*)scales;
-    a.zeros = (const qeft::f16*)scaled_zeros;
+    if (group_size != k && (group_size & (group_size - 1)) != 0) return QEFT_ERR_GROUP;  // GEMV: power of two or == K
+    qeft::GemvArgs a = gemv_args(x, qweight, scales, scaled_zeros, bias, y, n, k, group_size, n_out);
     a.ow_il = (const qeft::f16*)oweight_il;
-    a.bias = (const qeft::f16*)bias;
     a.ids = reorder_ids;
     a.residual = (const qeft::f16*)residual;
-    a.y = (qeft::f16*)y;
-    a.N = n;
-    a.K = k;
-    a.G = group_size;
-    a.n_out = n_out;
-    a.xt_aux = nullptr;
-    a.xt_eps = 0.f;
     a.sz_blk = (const uint32_t*)sz_packed;
-    a.dbg = nullptr;
-    a.dbg2 = nullptr;
-    a.ow_plain = nullptr;
-    a.m_rt = 1;
-    if (group_size != k && (group_size & (group_size - 1)) != 0) return QEFT_ERR_GROUP;  // GEMV: power of two or == K
-    a.gshift = (group_size == k) ? 31 : __builtin_ctz(group_size);
     if (bits == 3) {
         if (m < 1 || reorder_ids) return QEFT_ERR_SHAPE;   // the gather is the caller's (qlinear.py:275) for w3
         return finish(qeft::gemv_w3_dispatch(a, m, (hipStream_t)stream));
@@ -360,21 +267,8 @@ static int gemm_impl(const void* x, const void* qweight, const void* scales, con
         !(m <= qeft::V3_MAX_M && v3_route_enabled() && n % 16 == 0 && qeft::gemv_v3_ok(k, group_size, n_out))) {
         // few rows: stream the weights once per 16 rows through the MFMA GEMV instead of 128-row GEMM tiles.
         // (gemm_4bit semantics with oweight == NULL and a non-zero slice -- dead nibbles -- stays on the GEMM kernel.)
-        qeft::GemvArgs a{};
-        a.x = (const qeft::f16*)x;
-        a.qw = (const uint8_t*)qweight;
-        a.scales = (const qeft::f16*)scales;
-        a.zeros = (const qeft::f16*)scaled_zeros;
-        a.ow_il = nullptr;
-        a.ow_plain = (const qeft::f16*)oweight;
-        a.bias = (const qeft::f16*)bias;
-        a.y = (qeft::f16*)y;
-        a.N = n;
-        a.K = k;
-        a.G = group_size;
-        a.n_out = n_out;
-        a.gshift = (group_size == k) ? 31 : ((group_size & (group_size - 1)) == 0 ? __builtin_ctz(group_size) : 0);
-        a.m_rt = 1;
+        qeft::GemvArgs a = gemv_args(x, qweight, scales, scaled_zeros, bias, y, n, k, group_size, n_out);
+        a.ow_plain = (const qeft::f16*)oweight;      // (any group that is a multiple of 32 gets here: gshift 0 for one that is no power of two)
         const hipError_t e = qeft::gemv_w4_smallm_dispatch(a, m, (hipStream_t)stream);
         if (e == hipSuccess) return QEFT_OK;
         if (e != hipErrorNotSupported) return finish(e);
@@ -643,28 +537,11 @@ static int gemv_silu_impl(const void* gate, const void* up, const void* qweight,
     if (!aligned16(gate) || !aligned16(up) || !aligned16(qweight) || (n_out > 0 && !aligned16(oweight_il)))
         return QEFT_ERR_ALIGN;
     if (group_size != k && (group_size & (group_size - 1)) != 0) return QEFT_ERR_GROUP;
-    qeft::GemvArgs a;
-    a.x = (const qeft::f16*)gate;
-    a.qw = (const uint8_t*)qweight;
-    a.scales = (const qeft::f16*)scales;
-    a.zeros = (const qeft::f16*)scaled_zeros;
-    a.ow_il = (const qeft::f16*)oweight_il;
-    a.bias = (const qeft::f16*)bias;
-    a.ids = nullptr;
-    a.residual = (const qeft::f16*)residual;
-    a.y = (qeft::f16*)y;
-    a.N = n;
-    a.K = k;
-    a.G = group_size;
-    a.n_out = n_out;
-    a.gshift = (group_size == k) ? 31 : __builtin_ctz(group_size);
+    qeft::GemvArgs a = gemv_args(gate, qweight, scales, scaled_zeros, bias, y, n, k, group_size, n_out);
     a.xt_aux = (const qeft::f16*)up;
-    a.xt_eps = 0.f;
+    a.ow_il = (const qeft::f16*)oweight_il;
+    a.residual = (const qeft::f16*)residual;
     a.sz_blk = (const uint32_t*)sz_packed;
-    a.dbg = nullptr;
-    a.dbg2 = nullptr;
-    a.ow_plain = nullptr;
-    a.m_rt = 1;
     if (bits == 3) return finish(qeft::gemv_w3_silu_dispatch(a, (hipStream_t)stream));
     return finish(qeft::gemv_w4_silu_dispatch(a, (hipStream_t)stream));
 }
@@ -796,43 +673,30 @@ int qeft_single_query_attention_alibi(const void* q, const void* k, const void* 
     return sqa_impl(q, k, v, cos_tab, sin_tab, tab_rows, k_cache_ft, v_cache, pos, out, n_heads, n_kv_heads, max_seq, alibi_slopes, stream);
 }
 
-// ---- v3 decode linear (gemv_v3.h): fills the geometry, validates, launches
-static int v3_geom(qeft::V3Geom& G, int n, int k, int group_size, int n_out, int mode) {
-    if (mode != qeft::V3_MODE_PLAIN && mode != qeft::V3_MODE_PAIR) return QEFT_ERR_SHAPE;
-    if (n <= 0 || n % 16 != 0) return QEFT_ERR_SHAPE;
-    if (k <= 0 || group_size <= 0 || k % group_size != 0) return QEFT_ERR_GROUP;
-    if (!qeft::gemv_v3_ok(k, group_size, n_out)) return QEFT_ERR_SHAPE;
-    G.K = k;
-    G.n_out = n_out;
-    G.nsteps = k / 128;
-    G.nfull = (k - n_out) / 128;
-    G.ngroups = group_size == k ? 1 : k / 128;
-    G.nsets = n / 16;
-    return QEFT_OK;
-}
-
+// ---- v3 decode linear (gemv_v3.h)
 int qeft_decode_linear_blocks(int n_rows) {
     if (n_rows <= 0 || n_rows % 16 != 0) return 0;
     return qeft::gemv_v3_blocks(n_rows / 16);
 }
 
-int qeft_decode_linear(const void* x, const void* qweight, const void* sz_packed, const void* oweight, const void* bias,
-                       void* y, int n, int k, int group_size, int n_out, int mode, const void* residual,
-                       const float* ssq_in, int n_ssq_in, float eps, const void* gamma_out, void* y_norm, float* ssq_out,
-                       qeft_stream_t stream) {
+// What the four qeft_decode_linear* entries ask of the operands they share, in the order of their return codes.  qweight_align:
+// 16, or 4 for the 3-bit stream (qeft_decode_linear_w3: 12-byte records).
+static int decode_linear_operands(const void* x, const void* qweight, uintptr_t qweight_align, const void* sz_packed, const void* oweight,
+                                  const void* y, int n_out) {
     if (!x || !qweight || !sz_packed || !y || (n_out > 0 && !oweight)) return QEFT_ERR_NULL;
-    if (!aligned16(x) || !aligned16(qweight) || !aligned16(sz_packed) || (n_out > 0 && !aligned16(oweight))) return QEFT_ERR_ALIGN;
-    qeft::V3Args a{};
-    if (int e = v3_geom(a.g, n, k, group_size, n_out, mode)) return e;
+    if (!aligned16(x) || ((uintptr_t)qweight & (qweight_align - 1)) != 0 || !aligned16(sz_packed) || (n_out > 0 && !aligned16(oweight)))
+        return QEFT_ERR_ALIGN;
+    return QEFT_OK;
+}
+
+// The fused epilogue of qeft_decode_linear, _w3 and _m: the fp32 residual (y is fp32 then), the next norm's producer form
+// (gamma_out, y_norm, ssq_out) and the sums of squares x was derived from.  Checked after the geometry.
+static int decode_linear_epilogue(qeft::V3Args& a, int mode, void* y, const void* residual, const float* ssq_in, int n_ssq_in, float eps,
+                                  const void* gamma_out, void* y_norm, float* ssq_out) {
     if ((residual || gamma_out) && mode != qeft::V3_MODE_PLAIN) return QEFT_ERR_SHAPE;
     if (gamma_out && (!residual || !y_norm || !ssq_out)) return QEFT_ERR_NULL;
     if ((residual && !aligned16(residual)) || (gamma_out && !aligned16(gamma_out))) return QEFT_ERR_ALIGN;
-    if (ssq_in && (n_ssq_in < 1 || n_ssq_in > qeft::V3_MAX_SSQ || !aligned16(ssq_in))) return QEFT_ERR_SHAPE;
-    a.x = (const qeft::f16*)x;
-    a.qw = (const uint8_t*)qweight;
-    a.szp = (const uint8_t*)sz_packed;
-    a.ow = (const uint8_t*)oweight;
-    a.bias = (const qeft::f16*)bias;
+    if (ssq_in && (n_ssq_in < 1 || n_ssq_in > qeft::V3_MAX_SSQ)) return QEFT_ERR_SHAPE;
     a.residual = (const float*)residual;
     a.y = residual ? nullptr : (qeft::f16*)y;
     a.y32 = residual ? (float*)y : nullptr;
@@ -842,6 +706,19 @@ int qeft_decode_linear(const void* x, const void* qweight, const void* sz_packed
     a.gamma_out = (const qeft::f16*)gamma_out;
     a.ynorm = (qeft::f16*)y_norm;
     a.ssq_out = ssq_out;
+    return QEFT_OK;
+}
+
+// (the differences between the four entries, and which of them a kernel needs: DESIGN.md section 9)
+int qeft_decode_linear(const void* x, const void* qweight, const void* sz_packed, const void* oweight, const void* bias,
+                       void* y, int n, int k, int group_size, int n_out, int mode, const void* residual,
+                       const float* ssq_in, int n_ssq_in, float eps, const void* gamma_out, void* y_norm, float* ssq_out,
+                       qeft_stream_t stream) {
+    if (int e = decode_linear_operands(x, qweight, 16, sz_packed, oweight, y, n_out)) return e;
+    qeft::V3Args a;
+    if (int e = v3_args(a, x, qweight, sz_packed, oweight, bias, y, n, k, group_size, n_out, mode)) return e;
+    if (int e = decode_linear_epilogue(a, mode, y, residual, ssq_in, n_ssq_in, eps, gamma_out, y_norm, ssq_out)) return e;
+    if (ssq_in && !aligned16(ssq_in)) return QEFT_ERR_SHAPE;
     return finish(qeft::gemv_v3_launch(a, mode, (hipStream_t)stream));
 }
 
@@ -849,47 +726,24 @@ int qeft_decode_linear_w3(const void* x, const void* qweight3, const void* sz_pa
                        void* y, int n, int k, int group_size, int n_out, int mode, const void* residual,
                        const float* ssq_in, int n_ssq_in, float eps, const void* gamma_out, void* y_norm, float* ssq_out,
                        qeft_stream_t stream) {
-    if (!x || !qweight3 || !sz_packed || !y || (n_out > 0 && !oweight)) return QEFT_ERR_NULL;
-    if (!aligned16(x) || ((uintptr_t)qweight3 & 3) != 0 || !aligned16(sz_packed) || (n_out > 0 && !aligned16(oweight))) return QEFT_ERR_ALIGN;
-    qeft::V3Args a{};
-    if (int e = v3_geom(a.g, n, k, group_size, n_out, mode)) return e;
-    if ((residual || gamma_out) && mode != qeft::V3_MODE_PLAIN) return QEFT_ERR_SHAPE;
-    if (gamma_out && (!residual || !y_norm || !ssq_out)) return QEFT_ERR_NULL;
-    if ((residual && !aligned16(residual)) || (gamma_out && !aligned16(gamma_out))) return QEFT_ERR_ALIGN;
-    if (ssq_in && (n_ssq_in < 1 || n_ssq_in > qeft::V3_MAX_SSQ || !aligned16(ssq_in))) return QEFT_ERR_SHAPE;
-    a.x = (const qeft::f16*)x;
-    a.qw = (const uint8_t*)qweight3;
+    if (int e = decode_linear_operands(x, qweight3, 4, sz_packed, oweight, y, n_out)) return e;
+    qeft::V3Args a;
+    if (int e = v3_args(a, x, qweight3, sz_packed, oweight, bias, y, n, k, group_size, n_out, mode)) return e;
+    if (int e = decode_linear_epilogue(a, mode, y, residual, ssq_in, n_ssq_in, eps, gamma_out, y_norm, ssq_out)) return e;
+    if (ssq_in && !aligned16(ssq_in)) return QEFT_ERR_SHAPE;
     a.bits = 3;
-    a.szp = (const uint8_t*)sz_packed;
-    a.ow = (const uint8_t*)oweight;
-    a.bias = (const qeft::f16*)bias;
-    a.residual = (const float*)residual;
-    a.y = residual ? nullptr : (qeft::f16*)y;
-    a.y32 = residual ? (float*)y : nullptr;
-    a.ssq_in = ssq_in;
-    a.n_ssq_in = ssq_in ? n_ssq_in : 0;
-    a.eps = eps;
-    a.gamma_out = (const qeft::f16*)gamma_out;
-    a.ynorm = (qeft::f16*)y_norm;
-    a.ssq_out = ssq_out;
     return finish(qeft::gemv_v3_launch(a, mode, (hipStream_t)stream));
 }
 
 int qeft_decode_linear_hnorm(const void* h32, const void* gamma_x, const void* qweight, const void* sz_packed, const void* oweight,
                              const void* bias, void* y, int n, int k, int group_size, int n_out, int mode, float eps,
                              qeft_stream_t stream) {
-    if (!h32 || !gamma_x || !qweight || !sz_packed || !y || (n_out > 0 && !oweight)) return QEFT_ERR_NULL;
-    if (!aligned16(h32) || !aligned16(gamma_x) || !aligned16(qweight) || !aligned16(sz_packed) || (n_out > 0 && !aligned16(oweight)))
-        return QEFT_ERR_ALIGN;
-    qeft::V3Args a{};
-    if (int e = v3_geom(a.g, n, k, group_size, n_out, mode)) return e;
-    a.x = (const qeft::f16*)h32;              // fp32 [k]: the kernel reads it as such when xn_gamma is set
-    a.xn_gamma = (const qeft::f16*)gamma_x;
-    a.qw = (const uint8_t*)qweight;
-    a.szp = (const uint8_t*)sz_packed;
-    a.ow = (const uint8_t*)oweight;
-    a.bias = (const qeft::f16*)bias;
-    a.y = (qeft::f16*)y;
+    if (!gamma_x) return QEFT_ERR_NULL;
+    if (int e = decode_linear_operands(h32, qweight, 16, sz_packed, oweight, y, n_out)) return e;
+    if (!aligned16(gamma_x)) return QEFT_ERR_ALIGN;
+    qeft::V3Args a;
+    if (int e = v3_args(a, h32, qweight, sz_packed, oweight, bias, y, n, k, group_size, n_out, mode)) return e;
+    a.xn_gamma = (const qeft::f16*)gamma_x;      // x is fp32 [k]: the kernel reads it as such when xn_gamma is set
     a.eps = eps;
     return finish(qeft::gemv_v3_launch(a, mode, (hipStream_t)stream));
 }
@@ -956,30 +810,12 @@ int qeft_decode_linear_m(const void* x, const void* qweight, const void* sz_pack
     if (m == 1)
         return qeft_decode_linear(x, qweight, sz_packed, oweight, bias, y, n, k, group_size, n_out, mode, residual, ssq_in, n_ssq_in,
                                   eps, gamma_out, y_norm, ssq_out, stream);
-    if (!x || !qweight || !sz_packed || !y || (n_out > 0 && !oweight)) return QEFT_ERR_NULL;
-    if (!aligned16(x) || !aligned16(qweight) || !aligned16(sz_packed) || (n_out > 0 && !aligned16(oweight))) return QEFT_ERR_ALIGN;
-    qeft::V3Args a{};
-    if (int e = v3_geom(a.g, n, k, group_size, n_out, mode)) return e;
+    if (int e = decode_linear_operands(x, qweight, 16, sz_packed, oweight, y, n_out)) return e;
+    qeft::V3Args a;
+    if (int e = v3_args(a, x, qweight, sz_packed, oweight, bias, y, n, k, group_size, n_out, mode)) return e;
     if (a.g.ngroups == 1 && k > 128) return QEFT_ERR_GROUP;            // per-channel scales: not an engine operand
-    if ((residual || gamma_out) && mode != qeft::V3_MODE_PLAIN) return QEFT_ERR_SHAPE;
-    if (gamma_out && (!residual || !y_norm || !ssq_out)) return QEFT_ERR_NULL;
-    if ((residual && !aligned16(residual)) || (gamma_out && !aligned16(gamma_out))) return QEFT_ERR_ALIGN;
-    if (ssq_in && (n_ssq_in < 1 || n_ssq_in > qeft::V3_MAX_SSQ)) return QEFT_ERR_SHAPE;
-    a.m = m;
-    a.x = (const qeft::f16*)x;
-    a.qw = (const uint8_t*)qweight;
-    a.szp = (const uint8_t*)sz_packed;
-    a.ow = (const uint8_t*)oweight;
-    a.bias = (const qeft::f16*)bias;
-    a.residual = (const float*)residual;
-    a.y = residual ? nullptr : (qeft::f16*)y;
-    a.y32 = residual ? (float*)y : nullptr;
-    a.ssq_in = ssq_in;
-    a.n_ssq_in = ssq_in ? n_ssq_in : 0;
-    a.eps = eps;
-    a.gamma_out = (const qeft::f16*)gamma_out;
-    a.ynorm = (qeft::f16*)y_norm;
-    a.ssq_out = ssq_out;
+    if (int e = decode_linear_epilogue(a, mode, y, residual, ssq_in, n_ssq_in, eps, gamma_out, y_norm, ssq_out)) return e;
+    a.m = m;                                                           // (ssq_in [m][n_ssq_in]: no alignment asked)
     hipError_t e = qeft::gemv_v3_multi_launch(a, mode, (hipStream_t)stream);
     if (e == hipErrorInvalidValue) return QEFT_ERR_SHAPE;
     return finish(e);
@@ -1006,27 +842,49 @@ int qeft_token_begin_norm_m(const void* embed, const void* tokens, const void* r
                                                   max_seq, m, (hipStream_t)stream));
 }
 
-int qeft_attn_m_workspace_bytes(int n_heads, int n_split, int m) {
+// ---- row-wise attention (m rows of one sequence: decode_verify.hip, decode_verify_kv8.hip; one row each of m sequences:
+// decode_batch.hip, decode_attn_kv8.hip).  The entries name their operands in an AttnRowsArgs (decode_rows.h), attn_rows_check
+// holds what they all ask of them, in the order of their return codes.  slots: rows of different sequences (slot_tab,
+// n_slots); scales: an e4m3 cache (ks, vs: fp32, 4-byte aligned).
+static int attn_rows_check(const qeft::AttnRowsArgs& a, bool slots, bool scales) {
+    if (!verify_m_ok(a.m)) return QEFT_ERR_BATCH;
+    if (a.n_heads < 1 || a.n_kv < 1 || a.n_heads % a.n_kv != 0 || a.n_heads > 4096 || a.max_seq < 16 || a.max_seq % 16 != 0 ||
+        a.max_seq > 32768 || (slots && (a.n_slots < 1 || a.n_slots > 4096)))
+        return QEFT_ERR_SHAPE;
+    if (a.tab_rows != a.m && a.tab_rows < a.max_seq) return QEFT_ERR_SHAPE;
+    if (a.tab_stride < 64 || a.qkv_stride < 1 || a.out_stride < 1 || (!a.out_pos && a.out_stride < a.n_heads * 128)) return QEFT_ERR_SHAPE;
+    if (a.S != 1 && a.S != 2 && a.S != 4 && a.S != 8) return QEFT_ERR_SHAPE;
+    if (!a.q || !a.k || !a.v || !a.cs || !a.sn || !a.kc || !a.vc || (scales && (!a.ks || !a.vs)) || (slots && !a.slot_tab) || !a.pos ||
+        !a.out)
+        return QEFT_ERR_NULL;
+    if (a.S > 1 && !a.ws) return QEFT_ERR_NULL;
+    if (!aligned16(a.kc) || !aligned16(a.vc) || !aligned16(a.ws) || (scales && (((uintptr_t)a.ks & 3) || ((uintptr_t)a.vs & 3))))
+        return QEFT_ERR_ALIGN;
+    return QEFT_OK;
+}
+
+// the guard of the four workspace queries: 0 for what the launch entries refuse
+static int attn_rows_workspace(size_t (*bytes)(int, int, int), int n_heads, int n_split, int m) {
     if (n_heads < 1 || n_heads > 4096 || n_split < 1 || n_split > 8 || !verify_m_ok(m)) return 0;
-    return (int)qeft::attn_m_workspace_bytes(n_heads, n_split, m);
+    return (int)bytes(n_heads, n_split, m);
+}
+
+int qeft_attn_m_workspace_bytes(int n_heads, int n_split, int m) {
+    return attn_rows_workspace(qeft::attn_m_workspace_bytes, n_heads, n_split, m);
 }
 
 int qeft_rope_attn_decode_m(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
                             int tab_stride, int tab_rows, void* k_cache, void* v_cache, const int* pos, const int* out_pos,
                             void* out, int out_stride, void* workspace, int n_split, int n_heads, int n_kv_heads, int max_seq,
                             int m, qeft_stream_t stream) {
-    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
-    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0 || n_heads > 4096 || max_seq < 16 || max_seq % 16 != 0 ||
-        max_seq > 32768)
-        return QEFT_ERR_SHAPE;
-    if (tab_rows != m && tab_rows < max_seq) return QEFT_ERR_SHAPE;
-    if (tab_stride < 64 || qkv_stride < 1 || out_stride < 1 || (!out_pos && out_stride < n_heads * 128)) return QEFT_ERR_SHAPE;
-    if (n_split != 1 && n_split != 2 && n_split != 4 && n_split != 8) return QEFT_ERR_SHAPE;
-    if (!q || !k || !v || !cos_tab || !sin_tab || !k_cache || !v_cache || !pos || !out) return QEFT_ERR_NULL;
-    if (n_split > 1 && !workspace) return QEFT_ERR_NULL;
-    if (!aligned16(k_cache) || !aligned16(v_cache) || !aligned16(workspace)) return QEFT_ERR_ALIGN;
-    return finish(qeft::rope_attn_m_launch(q, k, v, qkv_stride, cos_tab, sin_tab, tab_stride, tab_rows, k_cache, v_cache, pos, out_pos,
-                                           out, out_stride, workspace, n_heads, n_kv_heads, max_seq, n_split, m, (hipStream_t)stream));
+    qeft::AttnRowsArgs a{};
+    a.q = q, a.k = k, a.v = v, a.qkv_stride = qkv_stride;
+    a.cs = cos_tab, a.sn = sin_tab, a.tab_stride = tab_stride, a.tab_rows = tab_rows;
+    a.kc = k_cache, a.vc = v_cache;
+    a.pos = pos, a.out_pos = out_pos, a.out = out, a.out_stride = out_stride, a.ws = workspace;
+    a.S = n_split, a.n_heads = n_heads, a.n_kv = n_kv_heads, a.max_seq = max_seq, a.m = m;
+    if (int e = attn_rows_check(a, false, false)) return e;
+    return finish(qeft::rope_attn_m_launch(a, (hipStream_t)stream));
 }
 
 int qeft_lm_head_f16_m(const void* h32, const void* gamma, const void* weight, void* logits, int hidden, int vocab, float eps,
@@ -1062,27 +920,22 @@ int qeft_token_begin_norm_batch(const void* embed, const void* tokens, const voi
 }
 
 int qeft_attn_batch_workspace_bytes(int n_heads, int n_split, int m) {
-    if (n_heads < 1 || n_heads > 4096 || n_split < 1 || n_split > 8 || !verify_m_ok(m)) return 0;
-    return (int)qeft::attn_b_workspace_bytes(n_heads, n_split, m);
+    return attn_rows_workspace(qeft::attn_b_workspace_bytes, n_heads, n_split, m);
 }
 
 int qeft_rope_attn_decode_batch(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
                                 int tab_stride, int tab_rows, void* k_cache, void* v_cache, const int* slots, const int* pos,
                                 const int* done, const int* out_pos, void* out, int out_stride, void* workspace, int n_split,
                                 int n_slots, int n_heads, int n_kv_heads, int max_seq, int m, qeft_stream_t stream) {
-    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
-    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0 || n_heads > 4096 || max_seq < 16 || max_seq % 16 != 0 ||
-        max_seq > 32768 || n_slots < 1 || n_slots > 4096)
-        return QEFT_ERR_SHAPE;
-    if (tab_rows != m && tab_rows < max_seq) return QEFT_ERR_SHAPE;
-    if (tab_stride < 64 || qkv_stride < 1 || out_stride < 1 || (!out_pos && out_stride < n_heads * 128)) return QEFT_ERR_SHAPE;
-    if (n_split != 1 && n_split != 2 && n_split != 4 && n_split != 8) return QEFT_ERR_SHAPE;
-    if (!q || !k || !v || !cos_tab || !sin_tab || !k_cache || !v_cache || !slots || !pos || !out) return QEFT_ERR_NULL;
-    if (n_split > 1 && !workspace) return QEFT_ERR_NULL;
-    if (!aligned16(k_cache) || !aligned16(v_cache) || !aligned16(workspace)) return QEFT_ERR_ALIGN;
-    return finish(qeft::rope_attn_b_launch(q, k, v, qkv_stride, cos_tab, sin_tab, tab_stride, tab_rows, k_cache, v_cache, slots, pos,
-                                           done, out_pos, out, out_stride, workspace, n_slots, n_heads, n_kv_heads, max_seq, n_split, m,
-                                           (hipStream_t)stream));
+    qeft::AttnRowsArgs a{};
+    a.q = q, a.k = k, a.v = v, a.qkv_stride = qkv_stride;
+    a.cs = cos_tab, a.sn = sin_tab, a.tab_stride = tab_stride, a.tab_rows = tab_rows;
+    a.kc = k_cache, a.vc = v_cache;
+    a.slot_tab = slots, a.pos = pos, a.done = done, a.n_slots = n_slots;
+    a.out_pos = out_pos, a.out = out, a.out_stride = out_stride, a.ws = workspace;
+    a.S = n_split, a.n_heads = n_heads, a.n_kv = n_kv_heads, a.max_seq = max_seq, a.m = m;
+    if (int e = attn_rows_check(a, true, false)) return e;
+    return finish(qeft::rope_attn_b_launch(a, (hipStream_t)stream));
 }
 
 int qeft_token_end_batch(const void* logits, const int* slots, void* tokens, int* pos, const int* limit, const int* eos, int* done,
@@ -1097,8 +950,7 @@ int qeft_token_end_batch(const void* logits, const int* slots, void* tokens, int
 
 // ---- e4m3 KV cache (decode_attn_kv8.hip)
 int qeft_attn_kv8_workspace_bytes(int n_heads, int n_split, int m) {
-    if (n_heads < 1 || n_heads > 4096 || n_split < 1 || n_split > 8 || !verify_m_ok(m)) return 0;
-    return (int)qeft::attn_kv8_workspace_bytes(n_heads, n_split, m);
+    return attn_rows_workspace(qeft::attn_kv8_workspace_bytes, n_heads, n_split, m);
 }
 
 int qeft_rope_attn_decode_kv8(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
@@ -1106,21 +958,15 @@ int qeft_rope_attn_decode_kv8(const void* q, const void* k, const void* v, int q
                               const int* slots, const int* pos, const int* done, const int* out_pos, void* out, int out_stride,
                               void* workspace, int n_split, int n_slots, int n_heads, int n_kv_heads, int max_seq, int m,
                               qeft_stream_t stream) {
-    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
-    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0 || n_heads > 4096 || max_seq < 16 || max_seq % 16 != 0 ||
-        max_seq > 32768 || n_slots < 1 || n_slots > 4096)
-        return QEFT_ERR_SHAPE;
-    if (tab_rows != m && tab_rows < max_seq) return QEFT_ERR_SHAPE;
-    if (tab_stride < 64 || qkv_stride < 1 || out_stride < 1 || (!out_pos && out_stride < n_heads * 128)) return QEFT_ERR_SHAPE;
-    if (n_split != 1 && n_split != 2 && n_split != 4 && n_split != 8) return QEFT_ERR_SHAPE;
-    if (!q || !k || !v || !cos_tab || !sin_tab || !k_codes || !v_codes || !k_scales || !v_scales || !slots || !pos || !out)
-        return QEFT_ERR_NULL;
-    if (n_split > 1 && !workspace) return QEFT_ERR_NULL;
-    if (!aligned16(k_codes) || !aligned16(v_codes) || !aligned16(workspace) || ((uintptr_t)k_scales & 3) || ((uintptr_t)v_scales & 3))
-        return QEFT_ERR_ALIGN;
-    return finish(qeft::rope_attn_kv8_launch(q, k, v, qkv_stride, cos_tab, sin_tab, tab_stride, tab_rows, k_codes, v_codes, k_scales,
-                                             v_scales, slots, pos, done, out_pos, out, out_stride, workspace, n_slots, n_heads,
-                                             n_kv_heads, max_seq, n_split, m, (hipStream_t)stream));
+    qeft::AttnRowsArgs a{};
+    a.q = q, a.k = k, a.v = v, a.qkv_stride = qkv_stride;
+    a.cs = cos_tab, a.sn = sin_tab, a.tab_stride = tab_stride, a.tab_rows = tab_rows;
+    a.kc = k_codes, a.vc = v_codes, a.ks = k_scales, a.vs = v_scales;
+    a.slot_tab = slots, a.pos = pos, a.done = done, a.n_slots = n_slots;
+    a.out_pos = out_pos, a.out = out, a.out_stride = out_stride, a.ws = workspace;
+    a.S = n_split, a.n_heads = n_heads, a.n_kv = n_kv_heads, a.max_seq = max_seq, a.m = m;
+    if (int e = attn_rows_check(a, true, true)) return e;
+    return finish(qeft::rope_attn_kv8_launch(a, (hipStream_t)stream));
 }
 
 int qeft_kv8_store_rows(const void* k_rows, const void* v_rows, int row_stride, void* k_codes, void* v_codes, void* k_scales,
@@ -1135,28 +981,21 @@ int qeft_kv8_store_rows(const void* k_rows, const void* v_rows, int row_stride, 
 
 // ---- the verify pass over an e4m3 KV cache (decode_verify_kv8.hip)
 int qeft_attn_m_kv8_workspace_bytes(int n_heads, int n_split, int m) {
-    if (n_heads < 1 || n_heads > 4096 || n_split < 1 || n_split > 8 || !verify_m_ok(m)) return 0;
-    return (int)qeft::attn_m_workspace_bytes(n_heads, n_split, m);      // one layout of counters and records with the fp16 kernel
+    return attn_rows_workspace(qeft::attn_m_workspace_bytes, n_heads, n_split, m);      // one layout of counters and records with the fp16 kernel
 }
 
 int qeft_rope_attn_decode_m_kv8(const void* q, const void* k, const void* v, int qkv_stride, const void* cos_tab, const void* sin_tab,
                                 int tab_stride, int tab_rows, void* k_codes, void* v_codes, void* k_scales, void* v_scales,
                                 const int* pos, const int* out_pos, void* out, int out_stride, void* workspace, int n_split,
                                 int n_heads, int n_kv_heads, int max_seq, int m, qeft_stream_t stream) {
-    if (!verify_m_ok(m)) return QEFT_ERR_BATCH;
-    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0 || n_heads > 4096 || max_seq < 16 || max_seq % 16 != 0 ||
-        max_seq > 32768)
-        return QEFT_ERR_SHAPE;
-    if (tab_rows != m && tab_rows < max_seq) return QEFT_ERR_SHAPE;
-    if (tab_stride < 64 || qkv_stride < 1 || out_stride < 1 || (!out_pos && out_stride < n_heads * 128)) return QEFT_ERR_SHAPE;
-    if (n_split != 1 && n_split != 2 && n_split != 4 && n_split != 8) return QEFT_ERR_SHAPE;
-    if (!q || !k || !v || !cos_tab || !sin_tab || !k_codes || !v_codes || !k_scales || !v_scales || !pos || !out) return QEFT_ERR_NULL;
-    if (n_split > 1 && !workspace) return QEFT_ERR_NULL;
-    if (!aligned16(k_codes) || !aligned16(v_codes) || !aligned16(workspace) || ((uintptr_t)k_scales & 3) || ((uintptr_t)v_scales & 3))
-        return QEFT_ERR_ALIGN;
-    return finish(qeft::rope_attn_m_kv8_launch(q, k, v, qkv_stride, cos_tab, sin_tab, tab_stride, tab_rows, k_codes, v_codes, k_scales,
-                                               v_scales, pos, out_pos, out, out_stride, workspace, n_heads, n_kv_heads, max_seq,
-                                               n_split, m, (hipStream_t)stream));
+    qeft::AttnRowsArgs a{};
+    a.q = q, a.k = k, a.v = v, a.qkv_stride = qkv_stride;
+    a.cs = cos_tab, a.sn = sin_tab, a.tab_stride = tab_stride, a.tab_rows = tab_rows;
+    a.kc = k_codes, a.vc = v_codes, a.ks = k_scales, a.vs = v_scales;
+    a.pos = pos, a.out_pos = out_pos, a.out = out, a.out_stride = out_stride, a.ws = workspace;
+    a.S = n_split, a.n_heads = n_heads, a.n_kv = n_kv_heads, a.max_seq = max_seq, a.m = m;
+    if (int e = attn_rows_check(a, false, true)) return e;
+    return finish(qeft::rope_attn_m_kv8_launch(a, (hipStream_t)stream));
 }
 
 // ---- prompt attention over the cache (prefill_attn.hip)

@@ -368,17 +368,14 @@ size_t attn_kv8_workspace_bytes(int n_heads, int S, int m) {
     return S > 1 ? (attn_b_ctr_floats(n_heads) + (size_t)m * n_heads * S * kAttnRec) * 4 : 0;
 }
 
-hipError_t rope_attn_kv8_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
-                                int tab_stride, int tab_rows, void* kc, void* vc, void* ks, void* vs, const int* slot_tab,
-                                const int* pos_tab, const int* done, const int* out_pos, void* out, int out_stride, void* ws,
-                                int n_slots, int n_heads, int n_kv, int max_seq, int S, int m, hipStream_t st) {
-    const int grp = n_heads / n_kv, hc = kv8_attn_chunk(grp, 1);
+hipError_t rope_attn_kv8_launch(const AttnRowsArgs& a, hipStream_t st) {
+    const int grp = a.n_heads / a.n_kv, hc = kv8_attn_chunk(grp, 1);
     return kv8_attn_dispatch(hc, [&](auto rc) {
         constexpr int R = decltype(rc)::value;
-        hipLaunchKernelGGL(rope_attn_kv8_kernel<R>, dim3(n_kv * (grp / hc) * S, m), dim3(256), kv8_attn_smem_bytes<1>(R), st, slot_tab,
-                           pos_tab, done, out_pos, (const f16*)q, (const f16*)k, (const f16*)v, (const float*)cs, (const float*)sn,
-                           (uint8_t*)kc, (uint8_t*)vc, (float*)ks, (float*)vs, (f16*)out, (float*)ws, qkv_stride, out_stride,
-                           tab_stride, tab_rows, max_seq, n_slots, n_heads, n_kv, S, hc);
+        hipLaunchKernelGGL(rope_attn_kv8_kernel<R>, dim3(a.n_kv * (grp / hc) * a.S, a.m), dim3(256), kv8_attn_smem_bytes<1>(R), st,
+                           a.slot_tab, a.pos, a.done, a.out_pos, (const f16*)a.q, (const f16*)a.k, (const f16*)a.v, (const float*)a.cs,
+                           (const float*)a.sn, (uint8_t*)a.kc, (uint8_t*)a.vc, (float*)a.ks, (float*)a.vs, (f16*)a.out, (float*)a.ws,
+                           a.qkv_stride, a.out_stride, a.tab_stride, a.tab_rows, a.max_seq, a.n_slots, a.n_heads, a.n_kv, a.S, hc);
         return hipGetLastError();
     });
 }

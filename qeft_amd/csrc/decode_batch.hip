@@ -10,11 +10,11 @@
 #include "qeft_common.h"
 #include "decode_attn.h"      // wave_max, st_agent / ld_agent, kAttnRec
 #include "decode_rows.h"      // token_begin_norm_row, block_argmax_1024, row_slot, attn_b_ctr_floats
+#include "host_launch.h"      // token_begin_norm_blocks
 
 namespace qeft {
 
 typedef float fx2 __attribute__((ext_vector_type(2)));
-int token_begin_norm_blocks(int hidden);      // decode_aux.hip
 
 // ---- token begin, one row per sequence.  grid = (blocks of the one-row launch, m), block 256; row = blockIdx.y.  The rotary row is
 // that of pos[slot[row]].
@@ -308,17 +308,15 @@ size_t attn_b_workspace_bytes(int n_heads, int S, int m) {
     return S > 1 ? (attn_b_ctr_floats(n_heads) + (size_t)m * n_heads * S * kAttnRec) * 4 : 0;
 }
 
-hipError_t rope_attn_b_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
-                              int tab_stride, int tab_rows, void* kc, void* vc, const int* slot_tab, const int* pos_tab,
-                              const int* done, const int* out_pos, void* out, int out_stride, void* ws, int n_slots, int n_heads,
-                              int n_kv, int max_seq, int S, int m, hipStream_t st) {
-    const int grp = n_heads / n_kv, hc = attn_b_chunk(grp);
+hipError_t rope_attn_b_launch(const AttnRowsArgs& a, hipStream_t st) {
+    const int grp = a.n_heads / a.n_kv, hc = attn_b_chunk(grp);
     const int R = hc <= 1 ? 1 : hc <= 2 ? 2 : hc <= 4 ? 4 : 8;
     const size_t smem = attn_b_smem_bytes(R);
     auto go = [&](auto kern) -> hipError_t {
-        hipLaunchKernelGGL(kern, dim3(n_kv * (grp / hc) * S, m), dim3(256), smem, st, slot_tab, pos_tab, done, out_pos, (const f16*)q,
-                           (const f16*)k, (const f16*)v, (const float*)cs, (const float*)sn, (f16*)kc, (f16*)vc, (f16*)out, (float*)ws,
-                           qkv_stride, out_stride, tab_stride, tab_rows, max_seq, n_slots, n_heads, n_kv, S, hc);
+        hipLaunchKernelGGL(kern, dim3(a.n_kv * (grp / hc) * a.S, a.m), dim3(256), smem, st, a.slot_tab, a.pos, a.done, a.out_pos,
+                           (const f16*)a.q, (const f16*)a.k, (const f16*)a.v, (const float*)a.cs, (const float*)a.sn, (f16*)a.kc, (f16*)a.vc,
+                           (f16*)a.out, (float*)a.ws, a.qkv_stride, a.out_stride, a.tab_stride, a.tab_rows, a.max_seq, a.n_slots, a.n_heads,
+                           a.n_kv, a.S, hc);
         return hipGetLastError();
     };
     if (R == 1) return go(rope_attn_b_kernel<1>);

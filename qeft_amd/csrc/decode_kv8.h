@@ -10,6 +10,7 @@
 #include <type_traits>
 #include "qeft_common.h"
 #include "decode_attn.h"      // wave_max
+#include "decode_rows.h"      // AttnRowsArgs
 
 namespace qeft {
 
@@ -68,5 +69,12 @@ hipError_t kv8_attn_dispatch(int rows, Go go) {
     if (rows <= 4) return go(std::integral_constant<int, 4>());
     return go(std::integral_constant<int, 8>());
 }
+
+// decode_attn_kv8.hip (one row per slot), decode_verify_kv8.hip (m rows of one sequence; its workspace is attn_m_workspace_bytes)
+size_t attn_kv8_workspace_bytes(int n_heads, int S, int m);
+hipError_t rope_attn_kv8_launch(const AttnRowsArgs& a, hipStream_t st);
+hipError_t rope_attn_m_kv8_launch(const AttnRowsArgs& a, hipStream_t st);
+hipError_t kv8_store_rows_launch(const void* k, const void* v, int row_stride, void* kc, void* vc, void* ks, void* vs, int n_kv,
+                                 int max_seq, int p0, int T, hipStream_t st);
 
 }  // namespace qeft

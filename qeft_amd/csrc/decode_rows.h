@@ -93,4 +93,39 @@ __device__ __forceinline__ int block_argmax_1024(const f16* lg, int vocab, float
     return idx == 0x7fffffff ? 0 : idx;
 }
 
+// ---- host side
+// Operands of one row-wise attention launch, by name, as the C ABI entry hands them to rope_attn_m_launch / rope_attn_b_launch
+// (fp16 cache) and rope_attn_kv8_launch / rope_attn_m_kv8_launch (e4m3 cache, decode_kv8.h).  Host only: the kernels take
+// their arguments one by one.  A launcher reads what its kernel has: ks / vs with an e4m3 cache, slot_tab / done / n_slots
+// with rows of different sequences; the others stay zero.
+struct AttnRowsArgs {
+    const void *q, *k, *v;          // the new rows, qkv_stride apart
+    const void *cs, *sn;            // rotary tables, tab_stride apart, tab_rows of them
+    void *kc, *vc;                  // the cache (fp16, or e4m3 codes)
+    void *ks, *vs;                  // e4m3 cache: its scales
+    const int *slot_tab, *pos, *done, *out_pos;
+    void *out, *ws;
+    int qkv_stride, tab_stride, tab_rows, out_stride;
+    int n_slots, n_heads, n_kv, max_seq, S, m;      // S: the split
+};
+
+// decode_verify.hip: m rows of one sequence
+hipError_t token_begin_norm_m_launch(const void* embed, const void* toks, const void* rope_tab, const int* pos, void* h,
+                                     void* rope_rows, const void* gamma, void* hnorm, float* ssq_out, int hidden, int vocab,
+                                     int max_seq, int m, hipStream_t st);
+size_t attn_m_workspace_bytes(int n_heads, int S, int m);
+hipError_t rope_attn_m_launch(const AttnRowsArgs& a, hipStream_t st);
+hipError_t lm_head_m_launch(const void* h32, const void* gamma, const void* W, void* logits, int H, int vocab, float eps, int m,
+                            hipStream_t st);
+hipError_t verify_greedy_launch(const void* logits, const void* tokens, int m, int vocab, int greedy, void* out_tokens, int* n_acc,
+                                void* tok, int* pos, hipStream_t st);
+// decode_batch.hip: m rows of m sequences
+hipError_t token_begin_norm_b_launch(const void* embed, const void* toks, const void* rope_tab, const int* slot_tab,
+                                     const int* pos_tab, void* h, void* rope_rows, const void* gamma, void* hnorm, float* ssq_out,
+                                     int hidden, int vocab, int max_seq, int n_slots, int m, hipStream_t st);
+size_t attn_b_workspace_bytes(int n_heads, int S, int m);
+hipError_t rope_attn_b_launch(const AttnRowsArgs& a, hipStream_t st);
+hipError_t token_end_b_launch(const void* logits, const int* slot_tab, void* tok, int* pos_tab, const int* limit, const int* eos,
+                              int* done, void* out, int* ctr, int vocab, int out_cap, int n_slots, int m, hipStream_t st);
+
 }  // namespace qeft

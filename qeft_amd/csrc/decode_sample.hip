@@ -13,6 +13,7 @@
 // search are exact and the token is a function of (row, record, position) alone.  Rows up to 32768 entries keep their keys in
 // registers across the passes; longer rows are re-read from global memory (L2-resident after the first pass).
 #include "qeft_common.h"
+#include "host_launch.h"
 
 namespace qeft {
 

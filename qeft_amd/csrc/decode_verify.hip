@@ -10,11 +10,11 @@
 #include "qeft_common.h"
 #include "decode_attn.h"      // wave_max, st_agent / ld_agent, kAttnRec
 #include "decode_rows.h"      // token_begin_norm_row, block_argmax_1024, attn_m_ctr_floats
+#include "host_launch.h"      // token_begin_norm_blocks
 
 namespace qeft {
 
 typedef float fx2 __attribute__((ext_vector_type(2)));
-int token_begin_norm_blocks(int hidden);      // decode_aux.hip
 
 // ---- token begin, m rows.  grid = (blocks of the one-row launch, m), block 256; row i = blockIdx.y.
 __global__ __launch_bounds__(256) void token_begin_norm_m_kernel(const f16* __restrict__ embed, const long long* __restrict__ toks,
@@ -303,10 +303,8 @@ size_t attn_m_smem_bytes(int R) { return (size_t)R * 128 * 2 + 2 * 8 * 128 * 2 +
 
 size_t attn_m_workspace_bytes(int n_heads, int S, int m) { return S > 1 ? (attn_m_ctr_floats(n_heads) + (size_t)n_heads * m * S * kAttnRec) * 4 : 0; }
 
-hipError_t rope_attn_m_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
-                              int tab_stride, int tab_rows, void* kc, void* vc, const int* pos, const int* out_pos, void* out,
-                              int out_stride, void* ws, int n_heads, int n_kv, int max_seq, int S, int m, hipStream_t st) {
-    const int grp = n_heads / n_kv, hc = attn_m_chunk(grp, m), rows = hc * m;
+hipError_t rope_attn_m_launch(const AttnRowsArgs& a, hipStream_t st) {
+    const int grp = a.n_heads / a.n_kv, hc = attn_m_chunk(grp, a.m), rows = hc * a.m;
     const int R = rows <= 8 ? 8 : rows <= 16 ? 16 : 32;
     const size_t smem = attn_m_smem_bytes(R);
     auto go = [&](auto kern) -> hipError_t {
@@ -314,9 +312,9 @@ hipError_t rope_attn_m_launch(const void* q, const void* k, const void* v, int q
             hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
             if (e != hipSuccess) return e;
         }
-        hipLaunchKernelGGL(kern, dim3(n_kv * (grp / hc) * S), dim3(256), smem, st, pos, out_pos, (const f16*)q, (const f16*)k,
-                           (const f16*)v, (const float*)cs, (const float*)sn, (f16*)kc, (f16*)vc, (f16*)out, (float*)ws, qkv_stride,
-                           out_stride, tab_stride, tab_rows, max_seq, n_heads, n_kv, S, m, hc);
+        hipLaunchKernelGGL(kern, dim3(a.n_kv * (grp / hc) * a.S), dim3(256), smem, st, a.pos, a.out_pos, (const f16*)a.q, (const f16*)a.k,
+                           (const f16*)a.v, (const float*)a.cs, (const float*)a.sn, (f16*)a.kc, (f16*)a.vc, (f16*)a.out, (float*)a.ws,
+                           a.qkv_stride, a.out_stride, a.tab_stride, a.tab_rows, a.max_seq, a.n_heads, a.n_kv, a.S, a.m, hc);
         return hipGetLastError();
     };
     if (R == 8) return go(rope_attn_m_kernel<8>);

@@ -336,17 +336,14 @@ __global__ __launch_bounds__(256) void rope_attn_m_kv8_kernel(const int* __restr
     }
 }
 
-hipError_t rope_attn_m_kv8_launch(const void* q, const void* k, const void* v, int qkv_stride, const void* cs, const void* sn,
-                                  int tab_stride, int tab_rows, void* kc, void* vc, void* ks, void* vs, const int* pos,
-                                  const int* out_pos, void* out, int out_stride, void* ws, int n_heads, int n_kv, int max_seq, int S,
-                                  int m, hipStream_t st) {
-    const int grp = n_heads / n_kv, hc = kv8_attn_chunk(grp, m);              // hc * m <= 8: m <= 8 (the C entry checks it)
-    return kv8_attn_dispatch(hc * m, [&](auto rc) {
+hipError_t rope_attn_m_kv8_launch(const AttnRowsArgs& a, hipStream_t st) {
+    const int grp = a.n_heads / a.n_kv, hc = kv8_attn_chunk(grp, a.m);        // hc * m <= 8: m <= 8 (the C entry checks it)
+    return kv8_attn_dispatch(hc * a.m, [&](auto rc) {
         constexpr int R = decltype(rc)::value;
-        hipLaunchKernelGGL(rope_attn_m_kv8_kernel<R>, dim3(n_kv * (grp / hc) * S), dim3(256), kv8_attn_smem_bytes<8>(R), st, pos, out_pos,
-                           (const f16*)q, (const f16*)k, (const f16*)v, (const float*)cs, (const float*)sn, (uint8_t*)kc, (uint8_t*)vc,
-                           (float*)ks, (float*)vs, (f16*)out, (float*)ws, qkv_stride, out_stride, tab_stride, tab_rows, max_seq,
-                           n_heads, n_kv, S, m, hc);
+        hipLaunchKernelGGL(rope_attn_m_kv8_kernel<R>, dim3(a.n_kv * (grp / hc) * a.S), dim3(256), kv8_attn_smem_bytes<8>(R), st, a.pos,
+                           a.out_pos, (const f16*)a.q, (const f16*)a.k, (const f16*)a.v, (const float*)a.cs, (const float*)a.sn,
+                           (uint8_t*)a.kc, (uint8_t*)a.vc, (float*)a.ks, (float*)a.vs, (f16*)a.out, (float*)a.ws, a.qkv_stride,
+                           a.out_stride, a.tab_stride, a.tab_rows, a.max_seq, a.n_heads, a.n_kv, a.S, a.m, hc);
         return hipGetLastError();
     });
 }

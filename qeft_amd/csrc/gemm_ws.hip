@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "gemv_v3.h"
+#include "host_launch.h"
 
 namespace qeft {
 

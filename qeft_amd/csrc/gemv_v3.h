@@ -868,4 +868,15 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
 }
 #endif  // __HIPCC__
 
+// ---- host side: gemv_v3.hip (launches of one row, and of batch rows on checkpoint-layout operands), gemv_v3_multi.hip (m rows
+// with the engine's epilogues)
+int gemv_v3_blocks(int nsets);
+bool gemv_v3_ok(int K, int G, int n_out);
+int gemv_v3_max_rows(V3Args a, int m_want);
+hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st);
+hipError_t gemv_v3_multi_launch(V3Args a, int mode, hipStream_t st);
+long long gemv_v3_count_out_of_range(const V3Geom& G, int n_rows_have, int n_ssq_in, bool xn, int bits);
+long long gemv_v3_count_out_of_range_ckpt(const V3Geom& G, int n_rows_have, int m, bool gather);
+long long gemv_v3_count_out_of_range_multi(const V3Geom& G, int n_rows_have, int m, int mode, int n_ssq_in);
+
 }  // namespace qeft

@@ -7,7 +7,6 @@
 namespace qeft {
 
 static int ceil_div(int a, int b) { return (a + b - 1) / b; }
-hipError_t gemv_v3_dispatch_plain(const V3Args& a, int mode, size_t smem, int depth, hipStream_t st);     // gemv_v3_plain.hip
 
 // Blocks for `nsets` 16-row sets: one set per block while that leaves the 256 CUs two blocks each at most; wide launches
 // run about 256 k long-lived blocks of ~3 sets (the ring then never drains between sets and the staging is paid once per

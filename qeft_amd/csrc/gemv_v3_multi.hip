@@ -9,7 +9,6 @@
 
 namespace qeft {
 
-int gemv_v3_blocks(int nsets);                 // gemv_v3.hip
 static int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Geometry of an m-row engine launch: the one-row launch's blocks and row sets, 8 waves, x in LDS unless it does not fit.

@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "gemv_w4_mfma.h"
+#include "host_launch.h"
 
 namespace qeft {
 

@@ -17,6 +17,7 @@
 // Every global offset comes from the ln_* functions (lm_head_nll_body.h, ln_ws_off below); lm_head_nll_count_out_of_range walks
 // the same functions on the CPU.  The k loop lives in lm_head_nll_body.h, shared with the backward (lm_head_nll_grad.hip).
 #include "lm_head_nll_body.h"
+#include "host_launch.h"
 
 namespace qeft {
 

@@ -21,6 +21,7 @@
 // CPU.  The transposing read needs EXEC all ones and 8-byte aligned in-bounds addresses in every lane: the k loop has no
 // lane-dependent branch, and the tiles are full (clamped loads), never masked.
 #include "lm_head_nll_body.h"
+#include "host_launch.h"
 
 namespace qeft {
 

@@ -82,4 +82,11 @@ __host__ __device__ inline long long pa8_new_off(const Pa8Geom& G8, int row, int
 // head dimension of accumulator register e of d-block db in lane half h (the 32x32 C/D map), first of a group of four
 __host__ __device__ inline int pa_acc_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 
+// ---- host side: prefill_attn.hip, prefill_attn_kv8.hip
+hipError_t prefill_attn_launch(const void* q, const void* kc, const void* vc, void* out, const PaGeom& G, hipStream_t st);
+long long prefill_attn_count_out_of_range(const PaGeom& G);
+hipError_t prefill_attn_kv8_launch(const void* q, const void* kq, const void* vq, const void* ksc, const void* vsc, const void* kn,
+                                   const void* vn, void* out, const Pa8Geom& G8, hipStream_t st);
+long long prefill_attn_kv8_count_out_of_range(const Pa8Geom& G8);
+
 }  // namespace qeft

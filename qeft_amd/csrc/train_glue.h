@@ -6,6 +6,7 @@
 //   norm      h, add, sum_out, y, s, dy, dres, dsum   [m][hidden] fp16, dense;  gamma [hidden] fp16
 //   SwiGLU    gate, up, dact, dgate, dup  [m][>= n] fp16, each at its own stride; the forward's out [m][n] dense
 #pragma once
+#include <hip/hip_runtime.h>
 
 namespace qeft {
 
@@ -31,5 +32,16 @@ __host__ __device__ inline long long tg_swiglu_off(const TgSwiglu& G, long long 
     const int per_row = G.n / 8;
     return chunk / per_row * stride + chunk % per_row * 8;
 }
+
+// ---- host side: train_glue.hip
+hipError_t add_rmsnorm_fwd_launch(const void* h, const void* add, const void* gamma, void* sum_out, void* y, const TgNorm& G, float eps,
+                                  hipStream_t st);
+hipError_t add_rmsnorm_bwd_launch(const void* s, const void* gamma, const void* dy, const void* dres, void* dsum, const TgNorm& G,
+                                  float eps, hipStream_t st);
+hipError_t swiglu_fwd_launch(const void* gate, const void* up, void* out, const TgSwiglu& G, hipStream_t st);
+hipError_t swiglu_bwd_launch(const void* gate, const void* up, const void* dact, void* dgate, void* dup, const TgSwiglu& G,
+                             hipStream_t st);
+long long train_glue_norm_count_out_of_range(const TgNorm& G);
+long long train_glue_swiglu_count_out_of_range(const TgSwiglu& G, bool backward);
 
 }  // namespace qeft

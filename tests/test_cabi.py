@@ -258,6 +258,38 @@ def test_attention_entries_refuse_a_cache_above_the_ceiling(lib):
     assert text.count("max_seq <= 32768") >= 3 and "at most 32768" in text        # stated where the entries are declared
 
 
+def test_refusals_are_those_recorded_before_the_argument_builders(lib):
+    """tests/golden/capi_refusals_parent.json.gz: 52 348 calls that capi.hip refused before its argument builders existed, recorded
+    on a CPU by tools/capi_record.cpp (profiles/capi_builders_refactor.log) -- the GEMV, GEMM forward, decode-linear and row-wise
+    attention entries with one argument wrong (NULL, misaligned by 2 / 4 / 8, a list of integers) and with two wrong at once, which
+    pins the precedence of the checks.  Each row is [entry, arguments, code]; operands are made-up addresses, so a row must be
+    refused before anything looks at them: a complete set of valid arguments would launch where a GPU is present (DESIGN.md
+    section 8), hence no row with code 0 is ever called."""
+    import gzip
+    import json
+    from qeft_amd import _lib
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "capi_refusals_parent.json.gz")) as f:
+        rows = json.load(f)
+    assert len(rows) == 52348
+    assert len({entry for entry, _, _ in rows}) == 21
+    wrong = []
+    for entry, args, code in rows:
+        assert code in (1, 2, 3, 4, 6), (entry, args, code)       # never QEFT_OK, never QEFT_ERR_LAUNCH
+        argtypes = _lib.SIGNATURES[entry]
+        assert len(args) == len(argtypes), entry
+        call = []
+        for v in args:
+            if isinstance(v, dict):
+                v = (ctypes.c_int * 3)(*v["ints"])
+            elif isinstance(v, list):
+                v = (ctypes.c_void_p * 3)(*v)
+            call.append(v)
+        got = getattr(lib, entry)(*call)
+        if got != code:
+            wrong.append((entry, args, code, got))
+    assert not wrong, f"{len(wrong)} rows, the first: {wrong[:3]}"
+
+
 def test_gemm_workspace_follows_the_row_routing(lib):
     """No compute: the split-K workspace the shim asks for matches where gemm_impl will send the rows -- up to 16 rows of a shape
     the decode GEMV serves ride on it (no workspace), 17 .. 64 rows take the weight-stationary tier (gemm_ws.hip, one launch, no

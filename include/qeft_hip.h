@@ -576,6 +576,34 @@ int qeft_swiglu_bwd(const void* gate, const void* up, const void* dact, void* dg
                     int up_stride, int dact_stride, int dgate_stride, int dup_stride, qeft_stream_t stream);
 long long qeft_train_glue_check_extents(int op, int rows, int width, int stride0, int stride1, int stride2, int stride3, int stride4);
 
+/* The rotary of the training step (csrc/train_glue.hip; qeft_amd/glue.py: rope_qk; finetune.causal_lm_loss with rope="fused";
+ * DESIGN.md section 4.17): every head of q and of k in one launch, and the same kernel as its own backward.
+ *   q fp16 [rows][n_heads][128], rows q_stride elements apart; k fp16 [rows][n_kv_heads][128], rows k_stride apart (a [B T] view
+ *   of a fused q|k|v buffer passes as it lies); q_out, k_out the same shapes, dense, not overlapping the inputs; cos_tab, sin_tab
+ *   fp32 [t_len][64].  Row r is at position r % t_len: every sequence starts at 0, rows % t_len == 0.
+ * NeoX pairs (a, b) = (x[i], x[i + 64]), c = cos[pos][i], s = sin[pos][i]:
+ *   inverse = 0:  lo = a c - b s,  hi = b c + a s
+ *   inverse = 1:  lo = a c + b s,  hi = b c - a s   -- the transpose: the backward, applied to the gradients of q_out and k_out; it
+ *                 needs the tables alone, not the forward's inputs.  Bit for bit inverse = 0 with a negated sin table, except
+ *                 that a result of -0 is returned as +0: autograd sums the gradients of the two half-slices of x, each padded
+ *                 with +0, so the torch route never hands on a -0, and the inverse adds the same +0 to its fp16 results.
+ * The arithmetic is pinned: each of the two products is rounded to fp32 on its own, their sum or difference is rounded to fp32,
+ * and that value is converted to fp16 (round to nearest even); nothing is contracted into an FMA.  This is what the torch
+ * expression of finetune._rope and its autograd compute, one rounding per torch op, so rope="fused" equals the torch route bit
+ * for bit in both directions, and a head's bits depend on its 128 values and its position alone -- not on the head counts, the
+ * row count, a stride or the grid.  Bit parity with qeft_rope_rows is NOT a goal and does not hold: that kernel rounds some
+ * heads once and some twice, depending on how many heads its operand has; both meet the same fp64 bound.
+ * Memory-bound: 16-byte accesses of q and k, fp32 math, no LDS, no atomics, no workspace, no host synchronisation, capturable.
+ * rows 1 .. 2^20, t_len >= 1 and rows % t_len == 0, n_heads and n_kv_heads 1 .. 256, strides multiples of 8, at least heads x 128
+ * (and at most 2^24), inverse 0 or 1: QEFT_ERR_SHAPE otherwise, before any pointer is looked at; then QEFT_ERR_NULL for any of
+ * the six pointers; then QEFT_ERR_ALIGN (16 bytes).
+ * qeft_rope_qk_check_extents: CPU-only, in the manner of qeft_train_glue_check_extents -- the largest number of bytes by which
+ *   any address that any thread of any block of that launch forms (q, k, q_out, k_out, both tables) leaves its operand, 0 when
+ *   none does, -1 for arguments the entry refuses. */
+int qeft_rope_qk(const void* q, const void* k, const void* cos_tab, const void* sin_tab, void* q_out, void* k_out, int rows, int t_len,
+                 int n_heads, int n_kv_heads, int q_stride, int k_stride, int inverse, qeft_stream_t stream);
+long long qeft_rope_qk_check_extents(int rows, int t_len, int n_heads, int n_kv_heads, int q_stride, int k_stride);
+
 /* Fused lm_head + cross-entropy pieces (csrc/lm_head_nll.hip; qeft_amd/scoring.py: lm_head_nll, score, eval_nll; DESIGN.md
  * section 4.13).  x: fp16 [t][hidden], the final-norm output rows, x_stride elements apart; weight: fp16 [vocab][hidden]
  * contiguous, the checkpoint's lm_head.weight; targets: int32 [t], or NULL.  logit_ij = sum_k x_ik w_jk is accumulated in fp32 by

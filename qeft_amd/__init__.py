@@ -6,7 +6,7 @@ The scoring and fine-tuning entry points are exported here; they resolve on firs
 _SCORING = ("score", "eval_nll", "lm_head_nll", "lm_head_nll_loss")
 _FINETUNE = ("causal_lm_loss", "shift_labels")           # qeft_amd.finetune also has begin(model) / end(model)
 _ATTENTION = ("causal_attention",)
-_GLUE = ("add_rmsnorm", "swiglu")
+_GLUE = ("add_rmsnorm", "swiglu", "rope_qk")
 __all__ = [*_SCORING, *_FINETUNE, *_ATTENTION, *_GLUE]
 
 

@@ -1202,6 +1202,31 @@ int qeft_swiglu_bwd(const void* gate, const void* up, const void* dact, void* dg
     return finish(qeft::swiglu_bwd_launch(gate, up, dact, dgate, dup, G, (hipStream_t)stream));
 }
 
+static int tg_rope_geom(qeft::TgRope& G, int rows, int t_len, int n_heads, int n_kv_heads, int q_stride, int k_stride) {
+    if (rows < 1 || rows > (1 << 20) || t_len < 1 || rows % t_len != 0) return QEFT_ERR_SHAPE;
+    if (n_heads < 1 || n_heads > 256 || n_kv_heads < 1 || n_kv_heads > 256) return QEFT_ERR_SHAPE;
+    if (!tg_stride_ok(q_stride, n_heads * 128) || !tg_stride_ok(k_stride, n_kv_heads * 128)) return QEFT_ERR_SHAPE;
+    G = qeft::TgRope{rows, t_len, n_heads, n_kv_heads, q_stride, k_stride};
+    return QEFT_OK;
+}
+
+int qeft_rope_qk(const void* q, const void* k, const void* cos_tab, const void* sin_tab, void* q_out, void* k_out, int rows, int t_len,
+                 int n_heads, int n_kv_heads, int q_stride, int k_stride, int inverse, qeft_stream_t stream) {
+    qeft::TgRope G{};
+    if (int e = tg_rope_geom(G, rows, t_len, n_heads, n_kv_heads, q_stride, k_stride)) return e;
+    if (inverse != 0 && inverse != 1) return QEFT_ERR_SHAPE;
+    if (!q || !k || !cos_tab || !sin_tab || !q_out || !k_out) return QEFT_ERR_NULL;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(cos_tab) || !aligned16(sin_tab) || !aligned16(q_out) || !aligned16(k_out))
+        return QEFT_ERR_ALIGN;
+    return finish(qeft::rope_qk_launch(q, k, cos_tab, sin_tab, q_out, k_out, G, inverse == 1, (hipStream_t)stream));
+}
+
+long long qeft_rope_qk_check_extents(int rows, int t_len, int n_heads, int n_kv_heads, int q_stride, int k_stride) {
+    qeft::TgRope G{};
+    if (tg_rope_geom(G, rows, t_len, n_heads, n_kv_heads, q_stride, k_stride) != QEFT_OK) return -1;
+    return qeft::train_glue_rope_count_out_of_range(G);
+}
+
 long long qeft_train_glue_check_extents(int op, int rows, int width, int stride0, int stride1, int stride2, int stride3, int stride4) {
     switch (op) {
         case QEFT_GLUE_ADD_RMSNORM_FWD:

@@ -6,7 +6,8 @@
 // atomics, no workspace, nothing saved between forward and backward beyond the operands themselves.  A row's results depend on
 // that row's operands alone, bit for bit: a norm row is one block with a fixed reduction order, a SwiGLU chunk is one lane's
 // work.  The forwards reproduce the arithmetic of qeft_rmsnorm and qeft_silu_mul (decode_aux.hip) operation for operation, so
-// their bits are those kernels' bits.
+// their bits are those kernels' bits.  The rotary of q and k (rope_qk_kernel, section 4.17; finetune.causal_lm_loss(rope="fused"))
+// is the exception to "rounded once": it owes the torch expression of finetune._rope bit equality and rounds where that does.
 //
 // Every global address comes from train_glue.h; train_glue_count_out_of_range below walks the same functions on the CPU.
 #include "qeft_common.h"
@@ -160,7 +161,78 @@ __global__ __launch_bounds__(TG_THREADS) void swiglu_bwd_kernel(const f16* __res
     *(h8*)(dup + tg_swiglu_off(G, chunk, G.dup_stride)) = ou;
 }
 
+// ---------------------------------------------------------------- rotary of q and k
+// NeoX pairs (a, b) = (x[i], x[i + 64]) of every head of q and k in one launch: lo = a c - b s, hi = b c + a s; the backward
+// is the transpose, the same kernel on the output gradients with the sign of sin flipped (exact: b (-s) = -(b s)).
+// The arithmetic is pinned to what the torch expression of finetune._rope and its autograd compute, one rounding per torch op:
+// each product rounded to fp32 on its own, their sum rounded to fp32, that converted to fp16.  tg_pin keeps every
+// intermediate in a register of its own, so that no product is contracted into an FMA and no sum into v_fma_mixlo_f16
+// (mul_f32_to_f16's idiom, qeft_common.h); a head's bits then depend on its 128 values and its position alone.
+// One more torch op stands behind the backward: autograd sums the gradients of the two half-slices x[..., :64] and x[..., 64:],
+// each padded with +0, in fp16, and (-0) + (+0) = +0 -- the torch route never hands on a gradient of -0.  So the inverse adds
+// +0 to its fp16 results (`zero`: +0 in both halves; the forward adds -0, which changes no value), nothing else differs.
+__device__ __forceinline__ float tg_pin(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+__device__ __forceinline__ void tg_rope_head(const f16* __restrict__ x, f16* __restrict__ out, long long in_lo, long long in_hi,
+                                             long long out_lo, long long out_hi, const float (&c)[8], const float (&s)[8], h2 zero) {
+    const h8 a8 = *(const h8*)(x + in_lo), b8 = *(const h8*)(x + in_hi);
+    h8 lo, hi;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float a = (float)a8[j], b = (float)b8[j];
+        const float ac = tg_pin(a * c[j]), bs = tg_pin(b * s[j]), bc = tg_pin(b * c[j]), as = tg_pin(a * s[j]);
+        lo[j] = (f16)tg_pin(ac - bs);
+        hi[j] = (f16)tg_pin(bc + as);
+    }
+    const h8 zero8 = {zero[0], zero[1], zero[0], zero[1], zero[0], zero[1], zero[0], zero[1]};
+    *(h8*)(out + out_lo) = lo + zero8;
+    *(h8*)(out + out_hi) = hi + zero8;
+}
+
+__global__ __launch_bounds__(TG_THREADS) void rope_qk_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                             const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
+                                                             f16* __restrict__ q_out, f16* __restrict__ k_out, TgRope G, int inverse) {
+    const int slots = tg_rope_slots(G), lane = tg_rope_lane(threadIdx.x);
+    const int row = tg_rope_row(blockIdx.x, threadIdx.x, slots);
+    if (row >= G.rows) return;
+    float c[8], s[8];
+#pragma unroll
+    for (int part = 0; part < 2; ++part) {
+        const f32x4 cv = *(const f32x4*)(cos_tab + tg_rope_tab_off(G, row, lane, part));
+        const f32x4 sv = *(const f32x4*)(sin_tab + tg_rope_tab_off(G, row, lane, part));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            c[part * 4 + j] = cv[j];
+            s[part * 4 + j] = inverse ? -sv[j] : sv[j];
+        }
+    }
+    uint32_t zbits = inverse ? 0u : 0x80008000u;
+    asm volatile("" : "+v"(zbits));                    // opaque: the add below is not an identity the compiler may drop
+    const h2 zero = as_h2(zbits);
+    const int heads = tg_rope_heads(G);
+    for (int head = tg_rope_slot(threadIdx.x, slots); head < heads; head += slots) {
+        if (head < G.n_heads)
+            tg_rope_head(q, q_out, tg_rope_off(row, head, lane, 0, G.q_stride), tg_rope_off(row, head, lane, 1, G.q_stride),
+                         tg_rope_off(row, head, lane, 0, G.n_heads * 128), tg_rope_off(row, head, lane, 1, G.n_heads * 128), c, s, zero);
+        else
+            tg_rope_head(k, k_out, tg_rope_off(row, head - G.n_heads, lane, 0, G.k_stride),
+                         tg_rope_off(row, head - G.n_heads, lane, 1, G.k_stride),
+                         tg_rope_off(row, head - G.n_heads, lane, 0, G.n_kv_heads * 128),
+                         tg_rope_off(row, head - G.n_heads, lane, 1, G.n_kv_heads * 128), c, s, zero);
+    }
+}
+
 // ---------------------------------------------------------------- launchers
+hipError_t rope_qk_launch(const void* q, const void* k, const void* cos_tab, const void* sin_tab, void* q_out, void* k_out,
+                          const TgRope& G, bool inverse, hipStream_t st) {
+    hipLaunchKernelGGL(rope_qk_kernel, dim3((unsigned)tg_rope_blocks(G)), dim3(TG_THREADS), 0, st, (const f16*)q, (const f16*)k,
+                       (const float*)cos_tab, (const float*)sin_tab, (f16*)q_out, (f16*)k_out, G, inverse ? 1 : 0);
+    return hipGetLastError();
+}
+
 hipError_t add_rmsnorm_fwd_launch(const void* h, const void* add, const void* gamma, void* sum_out, void* y, const TgNorm& G, float eps,
                                   hipStream_t st) {
     hipLaunchKernelGGL(add_rmsnorm_fwd_kernel, dim3(G.m), dim3(TG_THREADS), 0, st, (const f16*)h, (const f16*)add, (const f16*)gamma,
@@ -229,6 +301,31 @@ long long train_glue_swiglu_count_out_of_range(const TgSwiglu& G, bool backward)
             } else {
                 w(2 * tg_swiglu_off(G, chunk, G.n), 16, tg_bytes(G.m, G.n, G.n));
             }
+        }
+    return w.worst;
+}
+
+long long train_glue_rope_count_out_of_range(const TgRope& G) {        // both directions form the same addresses
+    const long long q_bytes = tg_bytes(G.rows, G.q_stride, G.n_heads * 128), k_bytes = tg_bytes(G.rows, G.k_stride, G.n_kv_heads * 128);
+    const long long qo_bytes = tg_bytes(G.rows, G.n_heads * 128, G.n_heads * 128), ko_bytes = tg_bytes(G.rows, G.n_kv_heads * 128, G.n_kv_heads * 128);
+    const long long tab_bytes = 4ll * G.t_len * 64;
+    const int slots = tg_rope_slots(G);
+    TgWorst w;
+    for (int block = 0; block < tg_rope_blocks(G); ++block)
+        for (int tid = 0; tid < TG_THREADS; ++tid) {
+            const int row = tg_rope_row(block, tid, slots), lane = tg_rope_lane(tid);
+            if (row >= G.rows) continue;
+            for (int part = 0; part < 2; ++part) w(4ll * tg_rope_tab_off(G, row, lane, part), 16, tab_bytes);      // cos and sin alike
+            for (int head = tg_rope_slot(tid, slots); head < tg_rope_heads(G); head += slots)
+                for (int half = 0; half < 2; ++half) {
+                    if (head < G.n_heads) {
+                        w(2 * tg_rope_off(row, head, lane, half, G.q_stride), 16, q_bytes);
+                        w(2 * tg_rope_off(row, head, lane, half, G.n_heads * 128), 16, qo_bytes);
+                    } else {
+                        w(2 * tg_rope_off(row, head - G.n_heads, lane, half, G.k_stride), 16, k_bytes);
+                        w(2 * tg_rope_off(row, head - G.n_heads, lane, half, G.n_kv_heads * 128), 16, ko_bytes);
+                    }
+                }
         }
     return w.worst;
 }

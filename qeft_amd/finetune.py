@@ -12,10 +12,9 @@ The reference's finetune.py freezes every parameter except `*oweight*` and train
 
 causal_lm_loss is a differentiable pass of its own (llama._prefill_pass, the inference route, is not touched): the linears and
 the head run the project's kernels; norms, rotary, the activation and the residual adds are torch ops unless glue="fused" asks
-for the project's row kernels and their backward kernels (qeft_amd.glue; the rotary stays torch's), and
-so is attention unless attn="own" asks for the project's own (attention.causal_attention).  The
-activations are fp16, so a
-caller scales the loss against underflow themselves -- `(loss * s).backward()`, then divide the fp32 gradients by s; the head's
+for the project's row kernels and their backward kernels (qeft_amd.glue) and rope="fused" for the
+project's rotary of q and k (glue.rope_qk), and so is attention unless attn="own" asks for the
+project's own (attention.causal_attention, DESIGN.md section 4.15).  The activations are fp16, so a caller scales the loss against underflow themselves -- `(loss * s).backward()`, then divide the fp32 gradients by s; the head's
 backward takes the scale in fp32 and keeps its softmax - onehot unscaled, so no scale makes it overflow or underflow there.
 The optimiser loop and Trainer plumbing are out of scope.
 """
@@ -90,14 +89,20 @@ def _attend(q, k, v, s, B, T, own_attn):
     return a.transpose(1, 2).reshape(B * T, s.hidden)
 
 
-def _decoder_layer(h, L, s, B, T, cos, sin, own_attn=False):
+def _rope_qk(q, k, cos, sin, fused):
+    """q and k rotated: the torch expression twice, or one glue.rope_qk launch with the same bits (cos / sin [T, 1, 64])."""
+    if fused:
+        return _glue.rope_qk(q, k, cos[:, 0], sin[:, 0])
+    return _rope(q, cos, sin), _rope(k, cos, sin)
+
+
+def _decoder_layer(h, L, s, B, T, cos, sin, own_attn=False, fused_rope=False):
     """h [B * T, hidden] fp16 -> the layer's output, fp16; every linear is the module's own forward (training mode: the MFMA
     forward, dX and d(oweight) kernels; o_proj gathers its own column order).  own_attn: attention.causal_attention on the
-    un-repeated k / v instead of torch's SDPA."""
+    un-repeated k / v instead of torch's SDPA; fused_rope: glue.rope_qk instead of the two _rope expressions."""
     at, mlp = L.self_attn, L.mlp
     x = _rmsnorm(h, L.input_layernorm.weight, s.rms_eps)
-    q = _rope(at.q_proj(x).view(B, T, s.n_heads, 128), cos, sin)
-    k = _rope(at.k_proj(x).view(B, T, s.n_kv_heads, 128), cos, sin)
+    q, k = _rope_qk(at.q_proj(x).view(B, T, s.n_heads, 128), at.k_proj(x).view(B, T, s.n_kv_heads, 128), cos, sin, fused_rope)
     v = at.v_proj(x).view(B, T, s.n_kv_heads, 128)
     h = h + at.o_proj(_attend(q, k, v, s, B, T, own_attn))
     x = _rmsnorm(h, L.post_attention_layernorm.weight, s.rms_eps)
@@ -105,22 +110,21 @@ def _decoder_layer(h, L, s, B, T, cos, sin, own_attn=False):
     return h + mlp.down_proj(act)
 
 
-def _decoder_layer_fused(h, delta, L, s, B, T, cos, sin, own_attn=False):
+def _decoder_layer_fused(h, delta, L, s, B, T, cos, sin, own_attn=False, fused_rope=False):
     """The layer of glue="fused" (DESIGN.md section 4.16).  The residual stream arrives as (h, delta) -- the stream before the last
     MLP and that MLP's output, delta None in layer 0 -- and leaves the same way, so that every residual add happens inside the
     norm that follows it (glue.add_rmsnorm) and every sum of residual-stream gradients inside that norm's backward; SiLU * up is
-    glue.swiglu.  The rotary stays the torch expression of the default route."""
+    glue.swiglu.  The rotary is the torch expression of the default route unless fused_rope asks for glue.rope_qk."""
     at, mlp = L.self_attn, L.mlp
     s1, x = _glue.add_rmsnorm(h, delta, L.input_layernorm.weight, s.rms_eps)
-    q = _rope(at.q_proj(x).view(B, T, s.n_heads, 128), cos, sin)
-    k = _rope(at.k_proj(x).view(B, T, s.n_kv_heads, 128), cos, sin)
+    q, k = _rope_qk(at.q_proj(x).view(B, T, s.n_heads, 128), at.k_proj(x).view(B, T, s.n_kv_heads, 128), cos, sin, fused_rope)
     v = at.v_proj(x).view(B, T, s.n_kv_heads, 128)
     s2, x = _glue.add_rmsnorm(s1, at.o_proj(_attend(q, k, v, s, B, T, own_attn)), L.post_attention_layernorm.weight, s.rms_eps)
     act = _glue.swiglu(mlp.gate_proj(x), mlp.up_proj(x))
     return s2, mlp.down_proj(act)
 
 
-def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused", attn="sdpa", glue="torch"):
+def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused", attn="sdpa", glue="torch", rope="torch"):
     """Mean NLL (fp32 scalar) of the shifted labels under `model`, differentiable with respect to the oweight parameters that
     begin(model) returned.  tokens [T] or [B, T] (right-padded; label the padding -100), labels as shift_labels takes them; a
     label outside [0, vocab) is ignored, and the mean runs over the others (0 when there is none).  Every sequence starts at
@@ -131,7 +135,9 @@ def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused",
     attention.causal_attention, the project's forward and backward kernels on the un-repeated k / v.
     glue="torch": norms, rotary, SiLU * up and the residual adds are torch ops; glue="fused": norms and SiLU * up on the project's
     row kernels and their backward kernels (qeft_amd.glue), with every residual add inside the norm that
-    follows it; the rotary stays torch's.
+    follows it.  rope="torch": the rotary of q and k is finetune._rope, twice per layer, on either glue; rope="fused":
+    one glue.rope_qk launch per layer and one for its backward, the same bits in both directions, with
+    either glue and either attn.
     fp16 activations: scale the loss yourself, `(loss * s).backward()`."""
     if head not in ("fused", "torch"):
         raise ValueError(f"head must be 'fused' or 'torch', got {head!r}")
@@ -139,8 +145,10 @@ def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused",
         raise ValueError(f"attn must be 'sdpa' or 'own', got {attn!r}")
     if glue not in ("torch", "fused"):
         raise ValueError(f"glue must be 'torch' or 'fused', got {glue!r}")
+    if rope not in ("torch", "fused"):
+        raise ValueError(f"rope must be 'torch' or 'fused', got {rope!r}")
     s = model.shape
-    own = attn == "own"
+    own, frope = attn == "own", rope == "fused"
     if own and (s.n_heads % s.n_kv_heads != 0 or s.hidden != s.n_heads * 128):
         raise ValueError(f"attn='own' takes heads of 128 and n_heads % n_kv_heads == 0, got hidden {s.hidden}, "
                          f"{s.n_heads} / {s.n_kv_heads} heads")
@@ -159,16 +167,16 @@ def causal_lm_loss(model, tokens, labels=None, *, checkpoint=True, head="fused",
         delta = None
         for L in model.model.layers:
             if checkpoint:
-                h, delta = _checkpoint(_decoder_layer_fused, h, delta, L, s, B, T, cos, sin, own, use_reentrant=False)
+                h, delta = _checkpoint(_decoder_layer_fused, h, delta, L, s, B, T, cos, sin, own, frope, use_reentrant=False)
             else:
-                h, delta = _decoder_layer_fused(h, delta, L, s, B, T, cos, sin, own)
+                h, delta = _decoder_layer_fused(h, delta, L, s, B, T, cos, sin, own, frope)
         hn = _glue.add_rmsnorm(h, delta, model.model.norm.weight, s.rms_eps)[1]
     else:
         for L in model.model.layers:
             if checkpoint:
-                h = _checkpoint(_decoder_layer, h, L, s, B, T, cos, sin, own, use_reentrant=False)
+                h = _checkpoint(_decoder_layer, h, L, s, B, T, cos, sin, own, frope, use_reentrant=False)
             else:
-                h = _decoder_layer(h, L, s, B, T, cos, sin, own)
+                h = _decoder_layer(h, L, s, B, T, cos, sin, own, frope)
         hn = _rmsnorm(h, model.model.norm.weight, s.rms_eps)
     W = model.lm_head.weight
     ok = (targets >= 0) & (targets < s.vocab)

@@ -3,9 +3,12 @@ linears, attention and the head of finetune.causal_lm_loss(glue="fused").
 
     add_rmsnorm(h, add, gamma, eps) -> (s, y)   s = fp16(h + add) (h itself when add is None), y = rmsnorm(s) * gamma
     swiglu(gate, up)                -> act      fp16(silu(gate) * up)
+    rope_qk(q, k, cos, sin)         -> (q_rot, k_rot)   the rotary of every head of q and k in one launch (section 4.17;
+                                                causal_lm_loss(rope="fused")), the bits of finetune._rope in both directions
 
 Each is a torch.autograd.Function over one forward and one backward entry: fp32 math, every result rounded to fp16 once, nothing
-saved but the operands (the norm's statistic is recomputed).  add_rmsnorm's backward takes the gradient of s -- what reaches the
+saved but the operands (the norm's statistic is recomputed).  rope_qk is one entry in both directions, saves the tables alone
+and rounds where the torch expression rounds.  add_rmsnorm's backward takes the gradient of s -- what reaches the
 residual stream from further on -- and the gradient of y in one launch and returns their sum through the norm with a single
 rounding, so a decoder layer that threads
 (s, delta) through add_rmsnorm has no residual add left for torch in either direction.  gamma is frozen: it gets no gradient.  A
@@ -162,3 +165,78 @@ def swiglu(gate, up):
     if not 1 <= m <= MAX_ROWS:
         raise ValueError(f"swiglu takes 1 .. 2^20 rows, got {m}")
     return _SwiGLU.apply(_rows2d(gate), _rows2d(up)).view(gate.shape)
+
+
+# ------------------------------------------------------------------------------------------------ rotary of q and k
+HEAD = 128
+
+
+def _head_rows(x):
+    """x [B, T, heads, 128] as qeft_rope_qk takes it, as attention._rows does: heads * 128 dense fp16 per row, a row stride that
+    is a multiple of 8, batch b at row b * T, 16-byte aligned -- a [B, T] view of a fused q|k|v buffer passes as it lies -- or a
+    dense copy."""
+    B, T, Hn, _ = x.shape
+    ok = x.stride(3) == 1 and x.stride(2) == HEAD and x.stride(1) % 8 == 0 and Hn * HEAD <= x.stride(1) <= 1 << 24 \
+        and x.data_ptr() % 16 == 0 and (B == 1 or x.stride(0) == T * x.stride(1))
+    return x if ok else _dense(x)
+
+
+def rope_qk_entry(q, k, cos, sin, inverse=False):
+    """The entry on q [B, T, H, 128], k [B, T, Hkv, 128] (rows as _head_rows leaves them) and dense cos / sin [T, 64] fp32:
+    (q_out, k_out), dense.  inverse: the transpose -- the backward, on the gradients of the outputs."""
+    B, T, H, _ = q.shape
+    Hkv = k.shape[2]
+    q_out = torch.empty(B, T, H, HEAD, dtype=torch.float16, device=q.device)
+    k_out = torch.empty(B, T, Hkv, HEAD, dtype=torch.float16, device=q.device)
+    _lib.check(_lib.lib().qeft_rope_qk(q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), q_out.data_ptr(), k_out.data_ptr(),
+                                       B * T, T, H, Hkv, q.stride(1), k.stride(1), 1 if inverse else 0, _stream(q.device)))
+    return q_out, k_out
+
+
+class _RopeQK(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, cos, sin):
+        ctx.save_for_backward(cos, sin)
+        ctx.shapes = (q.shape, k.shape)
+        ctx.set_materialize_grads(False)
+        return rope_qk_entry(q, k, cos, sin)
+
+    @staticmethod
+    def backward(ctx, dq, dk):
+        need_q, need_k = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (dq is None and dk is None) or not (need_q or need_k):
+            return None, None, None, None
+        cos, sin = ctx.saved_tensors
+        # one launch for both; a missing gradient is zero, and the transpose of zero is exactly zero
+        dq = torch.zeros(ctx.shapes[0], dtype=torch.float16, device=cos.device) if dq is None else _head_rows(dq)
+        dk = torch.zeros(ctx.shapes[1], dtype=torch.float16, device=cos.device) if dk is None else _head_rows(dk)
+        gq, gk = rope_qk_entry(dq, dk, cos, sin, inverse=True)
+        return gq if need_q else None, gk if need_k else None, None, None
+
+
+def rope_qk(q, k, cos, sin):
+    """The NeoX rotary of finetune._rope on q [B, T, H, 128] and k [B, T, Hkv, 128] (fp16, GPU) in one launch of qeft_rope_qk:
+    cos / sin fp32 [T, 64], row t of every sequence at position t.  Returns (q_rot, k_rot), dense, in the inputs' shapes, with
+    the bits of the torch expression (each product and their sum rounded to fp32, then to fp16); differentiable in q and k through
+    one inverse launch on (dq_rot, dk_rot), which gives the bits of that expression's autograd.  Inputs and gradients are taken
+    as views where they already are rows at a legal stride, as a dense copy otherwise."""
+    _need_gpu_f16("rope_qk", q=q, k=k)
+    for nm, x in (("cos", cos), ("sin", sin)):
+        if not torch.is_tensor(x):
+            raise ValueError(f"rope_qk: {nm} must be a tensor")
+        if not x.is_cuda:
+            raise RuntimeError(f"rope_qk needs GPU tensors (there is no CPU path): {nm} is on {x.device}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"rope_qk takes fp32 tables, got {nm} {x.dtype}")
+    if q.dim() != 4 or k.dim() != 4 or q.shape[3] != HEAD or k.shape[3] != HEAD:
+        raise ValueError(f"rope_qk takes q [B, T, H, 128] and k [B, T, Hkv, 128], got {tuple(q.shape)} and {tuple(k.shape)}")
+    B, T, H, _ = q.shape
+    if k.shape[:2] != (B, T):
+        raise ValueError(f"rope_qk: k {tuple(k.shape)} for q {tuple(q.shape)}")
+    if not (1 <= H <= 256 and 1 <= k.shape[2] <= 256):
+        raise ValueError(f"rope_qk takes 1 .. 256 heads, got {H} and {k.shape[2]}")
+    if T < 1 or not 1 <= B * T <= MAX_ROWS:
+        raise ValueError(f"rope_qk takes 1 .. 2^20 rows, got {B} x {T}")
+    if cos.shape != (T, HEAD // 2) or sin.shape != (T, HEAD // 2):
+        raise ValueError(f"rope_qk: cos {tuple(cos.shape)} and sin {tuple(sin.shape)} for T = {T}: both must be [T, 64]")
+    return _RopeQK.apply(_head_rows(q), _head_rows(k), _dense(cos), _dense(sin))

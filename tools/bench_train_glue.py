@@ -1,4 +1,4 @@
-"""The training glue (qeft_amd.glue: add_rmsnorm, swiglu over csrc/train_glue.hip) against the torch
+"""The training glue (qeft_amd.glue: add_rmsnorm, swiglu, rope_qk over csrc/train_glue.hip) against the torch
 expressions finetune.causal_lm_loss runs by default: one GPU, one process, HIP events, a warm-up before every measurement, the
 two sides of a point alternating (medians of --reps windows of 5 calls).
 
@@ -8,14 +8,17 @@ Per op, forward + backward under autograd at T = 2048 rows on the 7B widths (hid
 28672):
   add_rmsnorm   (s, y) = add_rmsnorm(h, add, gamma) with gradients arriving for both s and y, against s = h + add,
                 y = finetune._rmsnorm(s) -- the residual add and the sum of the two gradients are part of both sides;
-  swiglu        against (silu(gate.float()) * up.float()).half().
+  swiglu        against (silu(gate.float()) * up.float()).half();
+  rope_qk       (q_rot, k_rot) = rope_qk(q, k, cos, sin) at 32 / 32 and 64 / 8 heads, against finetune._rope on q and on k; its
+                algorithmic bytes are 4 per element of q and k and direction (read once, written once) plus the two tables.
 Per point: the medians in us, fused / torch, GB/s on the algorithmic bytes (every operand read once and every result written once,
 forward and backward: 16 bytes per element) against the 8 TB/s peak, the
 peak memory each side adds to its operands, and the largest difference of the two routes' gradients.  At these sizes the fused
 side of a point is partly the autograd function's Python (two ctypes calls, three to four allocations), so the forward and the
 backward entry are also timed alone (glue.*_fwd / *_bwd, outputs allocated per call), with their own GB/s.
---step adds the whole step: the Llama-2-7B shape cut to 4 layers, T = 2048, checkpointing on, attn="own", glue="torch" against
-glue="fused" in alternating windows, with each side's peak memory over the model.
+--step adds the whole step: the Llama-2-7B shape cut to 4 layers, T = 2048, checkpointing on, attn="own"; glue="torch",
+glue="fused" with rope="torch" and glue="fused" with rope="fused" in alternating windows, with each side's peak memory over the
+model.
 Every point runs under its own time limit (a watchdog ends the process when it overruns) and the first failure ends the run.  One
 JSON line per point; no threshold."""
 import argparse
@@ -152,8 +155,33 @@ def points(name, T, hidden, inter, reps):
                16 * T * inter, reps, lambda: glue.swiglu_fwd(gd, ud), lambda: glue.swiglu_bwd(gd, ud, dact))
 
 
+def rope_points(T, reps):
+    """rope_qk at the 7B (32 / 32) and 70B (64 / 8) head counts, one sequence of T rows."""
+    from qeft_amd import finetune, glue, qeft_cuda
+    cos, sin = (x.to(DEV) for x in qeft_cuda.rope_cos_sin(10000.0, 64, T))
+    c3, s3 = cos[:, None, :], sin[:, None, :]
+    for H, Hkv in ((32, 32), (64, 8)):
+        g = torch.Generator(device=DEV).manual_seed(H + T)
+        rn = lambda h, scale=1.0: (torch.randn(1, T, h, 128, generator=g, device=DEV) * scale).half()
+        q, k = rn(H).requires_grad_(True), rn(Hkv).requires_grad_(True)
+        dq, dk = rn(H, 2.0 ** -4), rn(Hkv, 2.0 ** -4)
+
+        def rope_fused():
+            torch.autograd.backward(list(glue.rope_qk(q, k, cos, sin)), [dq, dk])
+
+        def rope_torch():
+            torch.autograd.backward([finetune._rope(q, c3, s3), finetune._rope(k, c3, s3)], [dq, dk])
+
+        with limit(120):
+            qd, kd = q.detach(), k.detach()
+            report(dict(bench="train_glue", op="rope_qk", heads=f"{H}/{Hkv}", t=T), rope_fused, rope_torch, [q, k],
+                   2 * (4 * T * (H + Hkv) * 128 + 2 * 4 * T * 64), reps, lambda: glue.rope_qk_entry(qd, kd, cos, sin),
+                   lambda: glue.rope_qk_entry(dq, dk, cos, sin, inverse=True))
+        del q, k, dq, dk
+
+
 def step(T, layers, reps):
-    """The whole training step, glue="torch" against glue="fused", alternating."""
+    """The whole training step on attn="own": glue="torch", glue="fused" and glue="fused" with rope="fused", alternating."""
     from qeft_amd import finetune
     from qeft_amd.llama import LLAMA2_7B, QuantLlama
     model = QuantLlama(dataclasses.replace(LLAMA2_7B, max_seq=T, n_layers=layers), DEV, seed=0, fast_init=True)
@@ -161,23 +189,26 @@ def step(T, layers, reps):
     params = finetune.begin(model)
     losses = {}
 
-    def side(glue):
+    def side(glue, rope):
         def run():
             for p in params:
                 p.grad = None
-            loss = finetune.causal_lm_loss(model, toks, attn="own", glue=glue)
+            loss = finetune.causal_lm_loss(model, toks, attn="own", glue=glue, rope=rope)
             (loss * 1024.0).backward()
-            losses[glue] = loss
+            losses[glue, rope] = loss
         return run
 
-    f, t = side("fused"), side("torch")
-    f(), t()
-    mem_f, mem_t = peak_rise(f), peak_rise(t)
-    us = medians_us([f, t], reps, 5)
+    f, t, r = side("fused", "torch"), side("torch", "torch"), side("fused", "fused")
+    f(), t(), r()
+    mem_f, mem_t, mem_r = peak_rise(f), peak_rise(t), peak_rise(r)
+    us = medians_us([f, t, r], reps, 5)
     print(json.dumps(dict(bench="train_glue", op="step", layers=layers, t=T, attn="own", checkpoint=True, reps=reps,
                           fused_ms=round(us[0] * 1e-3, 3), torch_ms=round(us[1] * 1e-3, 3), fused_over_torch=round(us[0] / us[1], 4),
+                          fused_rope_ms=round(us[2] * 1e-3, 3), fused_rope_over_fused=round(us[2] / us[0], 4),
                           fused_peak_over_model_MiB=round(mem_f / 2 ** 20, 1), torch_peak_over_model_MiB=round(mem_t / 2 ** 20, 1),
-                          loss_fused=round(losses["fused"].item(), 6), loss_torch=round(losses["torch"].item(), 6))), flush=True)
+                          fused_rope_peak_over_model_MiB=round(mem_r / 2 ** 20, 1),
+                          loss_fused=round(losses["fused", "torch"].item(), 6), loss_torch=round(losses["torch", "torch"].item(), 6),
+                          loss_fused_rope=round(losses["fused", "fused"].item(), 6))), flush=True)
 
 
 if __name__ == "__main__":
@@ -190,6 +221,8 @@ if __name__ == "__main__":
     points("7B", a.T, 4096, 11008, a.reps)
     torch.cuda.empty_cache()
     points("70B", a.T, 8192, 28672, a.reps)
+    torch.cuda.empty_cache()
+    rope_points(a.T, a.reps)
     torch.cuda.empty_cache()
     if a.step:
         with limit(400):

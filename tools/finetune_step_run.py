@@ -8,8 +8,8 @@ model's construction and the first step's one-off work.
     python tools/finetune_step_run.py --group OUT3/.../run_kernel_stats.csv --minus OUT1/.../run_kernel_stats.csv --steps 2
 
 --group reads the per-kernel tables and prints their difference grouped into linears / attention / head / own glue (the kernels of
-csrc/train_glue.hip) / torch glue, per step.  --glue fused runs the step with those kernels; the default is the
-torch route.  A plain run (no profiler) also prints the wall time of every step and the last step's peak memory over the model."""
+csrc/train_glue.hip) / torch glue, per step.  --glue fused runs the step with those kernels, --rope fused with the rotary kernel
+(§4.17); the default is the torch route.  A plain run (no profiler) also prints the wall time of every step and the last step's peak memory over the model."""
 import argparse
 import csv
 import dataclasses
@@ -20,7 +20,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(attn, layers, T, steps, glue="torch"):
+def run(attn, layers, T, steps, glue="torch", rope="torch"):
     import time
     import torch
     from qeft_amd import finetune
@@ -37,12 +37,12 @@ def run(attn, layers, T, steps, glue="torch"):
             p.grad = None
         torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
-        loss = finetune.causal_lm_loss(model, toks, attn=attn, glue=glue)
+        loss = finetune.causal_lm_loss(model, toks, attn=attn, glue=glue, rope=rope)
         (loss * 1024.0).backward()
         torch.cuda.synchronize()
         ms.append((time.perf_counter() - t0) * 1e3)
     # wall time of the later steps (the first carries one-off work) and the last step's peak over the model and its gradients' home
-    print(json.dumps(dict(run="finetune_step", attn=attn, glue=glue, layers=layers, T=T, steps=steps, loss=round(loss.item(), 6),
+    print(json.dumps(dict(run="finetune_step", attn=attn, glue=glue, rope=rope, layers=layers, T=T, steps=steps, loss=round(loss.item(), 6),
                           step_ms=[round(x, 2) for x in ms], median_later_ms=round(sorted(ms[1:])[len(ms[1:]) // 2], 2) if steps > 1 else None,
                           peak_over_model_MiB=round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1))), flush=True)
 
@@ -51,7 +51,7 @@ def family(name):
     n = name.lower()
     if "lm_head_nll" in n:
         return "head"
-    if "add_rmsnorm" in n or "swiglu" in n:
+    if "add_rmsnorm" in n or "swiglu" in n or "rope_qk" in n:
         return "own glue"
     if "attn_train" in n or "prefill_attn" in n or "attention" in n or "fmha" in n or "flash" in n or "softmax" in n or "cijk_" in n \
             or "bmm" in n or "aotriton" in n or "attn_" in n or "bwd_kernel_d" in n or "bwd_preprocess" in n:
@@ -92,6 +92,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--attn", default="own", choices=("own", "sdpa"))
     ap.add_argument("--glue", default="torch", choices=("torch", "fused"))
+    ap.add_argument("--rope", default="torch", choices=("torch", "fused"))
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--T", type=int, default=2048)
     ap.add_argument("--group")
@@ -101,4 +102,4 @@ if __name__ == "__main__":
     if a.group:
         group(a.group, a.minus, a.steps)
     else:
-        run(a.attn, a.layers, a.T, a.steps, a.glue)
+        run(a.attn, a.layers, a.T, a.steps, a.glue, a.rope)

@@ -21,6 +21,7 @@
  * Every function returns QEFT_OK (0) or a QEFT_ERR_* code; qeft_error_string()
  * gives the message.  Kernel-launch failures return QEFT_ERR_LAUNCH and the
  * hipError_t is available from qeft_last_hip_error().
+ * Which kernel a call ran: qeft_last_variant(), and for the v3 decode GEMV the instance itself, qeft_gemv_v3_last_plan().
  */
 #ifndef QEFT_HIP_H
 #define QEFT_HIP_H
@@ -283,6 +284,28 @@ long long qeft_gemv_v3_check_extents(int n, int k, int group_size, int n_out, in
  * qeft_gemv_w4_qeft, qeft_gemv_w4_fused): scales / scaled_zeros fp16 [k/g][n] staged raw, oweight_interleaved, m = 1..7 batch
  * rows, optional reorder_ids gather; also checks every LDS destination of the staging against the block's LDS carve-up. */
 long long qeft_gemv_v3_check_extents_ckpt(int n, int k, int group_size, int n_out, int m, int gather, int shrink_rows);
+/* Which instance of the v3 decode GEMV a launch runs (csrc/gemv_v3.hip gemv_v3_plan).  qeft_last_variant
+ * says "gemv_v3" for some 170 instances of one kernel template; these two entries say which one.
+ * out[QEFT_GEMV_V3_PLAN_INTS] = { blocks, row sets per block (RSC), nsets / blocks, nsets % blocks (that many blocks hold RSC
+ * sets, the others one fewer; 0: all hold RSC), waves per block, ring depth D, 1 with an outlier step (OUTL), mode 0 PLAIN / 1 PAIR,
+ * bits 4 / 3, 1 for the half with the run-time flag paths (0: the flag-free half), MB (1: one batch row, 2: several), 1 if the
+ * batch rows' x is read from global memory (xg), dynamic LDS bytes }.
+ * qeft_gemv_v3_plan: host arithmetic only, no GPU needed.  m batch rows (>= 1); flags: the QEFT_V3_F_* bits below the operands
+ *   would set (per-channel follows from group_size == k and need not be given).  Returns QEFT_OK, QEFT_ERR_NULL without `out`,
+ *   and -1 for what the launcher refuses: a shape outside the requirements above, m > 16, a block that does not fit the LDS,
+ *   several rows in PAIR mode / with 3 bits / with XN, XG with one row or with GATHER, XN with SZN, an unknown or contradictory flag.
+ *   The lab overrides QEFT_GEMV_BLOCKS / _NW / _NW12 / _DEPTH of the process's environment act on it as on the launcher.
+ * qeft_gemv_v3_last_plan: what the calling thread's last v3 launch through qeft_decode_linear / _w3 / _hnorm, the gemv entries
+ *   or the GEMM entries' few-row route ran (all zero before the first); qeft_decode_linear_m's m-row launches do not set it. */
+#define QEFT_GEMV_V3_PLAN_INTS 13
+#define QEFT_V3_F_PERCH (1u << 24)  /* one group per row (group_size == k) */
+#define QEFT_V3_F_XN (1u << 25)     /* qeft_decode_linear_hnorm: the whole RMSNorm in the launch */
+#define QEFT_V3_F_SZN (1u << 26)    /* scales / scaled_zeros in the checkpoint layout (the gemv and GEMM entries without sz_packed) */
+#define QEFT_V3_F_OWIL (1u << 27)   /* outlier slice from oweight_interleaved (the gemv entries) */
+#define QEFT_V3_F_XG (1u << 28)     /* several rows whose x does not fit the LDS: fragments from global memory */
+#define QEFT_V3_F_GATHER (1u << 31) /* reorder_ids gathered inside the launch */
+int qeft_gemv_v3_plan(int n, int k, int group_size, int n_out, int m, int mode, int bits, int flags, int* out);
+int qeft_gemv_v3_last_plan(int* out);
 
 /* Producer-form helpers for the same scheme.
  * qeft_token_begin_norm: qeft_token_begin + h32 = float(embed[*tok]), h_norm = fp16(embed[*tok] * gamma),

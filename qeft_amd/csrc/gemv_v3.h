@@ -872,6 +872,18 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
 // with the engine's epilogues)
 int gemv_v3_blocks(int nsets);
 bool gemv_v3_ok(int K, int G, int n_out);
+// What gemv_v3_launch runs: the grid (nblk blocks; the first sets_r of them hold rs_cap row sets, the others sets_q), the instance
+// gemv_v3_kernel<nw, D, outl, mode, bits, mb, rs_cap, fl, xg> and its dynamic LDS.  gemv_v3_plan (gemv_v3.hip) is the one place
+// that decides any of it; the launcher executes the plan and keeps it per thread (gemv_v3_last_plan) beside g_last_variant.
+// flags: the V3_F_* bits of the operands (v3_flags), and V3_PLAN_XG for V3Args::xg (a bit of the plan only, never the kernel's).
+constexpr uint32_t V3_PLAN_XG = 1u << 28;
+struct V3Plan {
+    int nblk, rs_cap, sets_q, sets_r, nw, D, outl, mode, bits, fl, mb, xg;
+    size_t smem;
+    bool ok;                // false: the launcher refuses (the other fields then say what it would have needed)
+};
+V3Plan gemv_v3_plan(const V3Geom& g, int m, int mode, int bits, uint32_t flags);
+const V3Plan& gemv_v3_last_plan();
 int gemv_v3_max_rows(V3Args a, int m_want);
 hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st);
 hipError_t gemv_v3_multi_launch(V3Args a, int mode, hipStream_t st);

@@ -42,60 +42,87 @@ static int env_int(const char* name) {
     return e ? atoi(e) : 0;
 }
 
-// Geometry of a launch: blocks, row sets per block, waves per block, LDS bytes.  Returns false when the configuration does
-// not fit the chip's 160 KB of LDS per block (many batch rows of a long x: the caller splits the batch).
-static bool gemv_v3_plan(V3Args& a, int& nw, size_t& smem) {
-    const int nblk = gemv_v3_blocks(a.g.nsets);
-    a.rs_cap = ceil_div(a.g.nsets, nblk);
-    a.nblk = nblk;
-    a.sets_q = a.g.nsets / nblk;
-    a.sets_r = a.g.nsets % nblk;
-    if (a.m < 1) a.m = 1;
+// The plan of a launch: everything gemv_v3_launch decides, in one place (gemv_v3.h: V3Plan).  Host arithmetic only.
+//   grid      gemv_v3_blocks; the first sets_r blocks hold rs_cap row sets, the others rs_cap - 1 (all of them when sets_r == 0)
+//   waves     8; 4 where a CU holds several blocks (more than 256 blocks, one batch row); 12 for one-set blocks with a long K
+//   ring      2 loads in flight per wave; the deep ring (4, or 6 with three or four row sets per block: two whole steps) where a
+//             CU holds ONE block and a wave has at least 8 loads to make, and for every xg launch; 4-wave blocks are
+//             instantiated with 4 only, 12-wave blocks with 2 only
+//   half      the instances without the flag paths (gemv_v3_plain.hip) for one batch row and no run-time flag, else the flagged ones
+//   MB        2 for several batch rows (8 waves, 4 bits, PLAIN, flagged half)
+// ok is false for what the launcher refuses: more than V3_MAX_M batch rows, a block that does not fit the chip's 160 KB of LDS
+// (many batch rows of a long x: the caller splits the batch, gemv_v3_max_rows), 65536 blocks or more, batch rows in PAIR mode /
+// with 3 bits / with the consumer-side norm, xg without batch rows or with a gather, the consumer-side norm on checkpoint-layout
+// scales.  The lab overrides (QEFT_GEMV_BLOCKS, _NW, _NW12, _DEPTH; read once per process) act here and nowhere else.
+V3Plan gemv_v3_plan(const V3Geom& g, int m, int mode, int bits, uint32_t flags) {
+    V3Plan p{};
+    if (m < 1) m = 1;
+    if (g.ngroups == 1 && g.K > 128) flags |= V3_F_PERCH;
+    const bool xn = (flags & V3_F_XN) != 0, szn = (flags & V3_F_SZN) != 0, gather = (flags & V3_F_GATHER) != 0, xg = (flags & V3_PLAN_XG) != 0;
+    p.nblk = gemv_v3_blocks(g.nsets);
+    p.rs_cap = ceil_div(g.nsets, p.nblk);
+    p.sets_q = g.nsets / p.nblk;
+    p.sets_r = g.nsets % p.nblk;
     static const int f_nw = env_int("QEFT_GEMV_NW");      // lab override: 4 or 8
     // several blocks per CU (more than 256 blocks): 4-wave blocks, one wave per SIMD each
-    nw = f_nw == 4 || f_nw == 8 ? f_nw : (nblk > 256 && a.m <= 1 ? 4 : V3_NW);
-    if (a.m > 1) nw = V3_NW;
+    p.nw = f_nw == 4 || f_nw == 8 ? f_nw : (p.nblk > 256 && m <= 1 ? 4 : V3_NW);
+    if (m > 1) p.nw = V3_NW;
     // one row set per block and many steps per wave (down_proj: K = 11008, 85 full steps): 12 waves share the steps 8 / 7 instead of
     // 11 / 10: down_proj 7.42 -> 7.33 us (profiles/r04_gemv_lab.txt; the same file holds the correction sums tabulated up front per
     // wave instead of 4 MFMAs per step: +0.4 us on o_proj, +1.0 us on down_proj, not adopted); QEFT_GEMV_NW12=0 keeps 8 (A/B)
     static const int no_nw12 = getenv("QEFT_GEMV_NW12") && atoi(getenv("QEFT_GEMV_NW12")) == 0;
-    if (!no_nw12 && !f_nw && a.m <= 1 && nblk <= 256 && a.rs_cap == 1 && a.g.nfull >= 64) nw = 12;
-    a.nw = nw;
-    smem = v3_lds(a.g.K, a.g.ngroups, a.g.n_out, a.rs_cap, a.m, nw, a.xn_gamma != nullptr && a.szp != nullptr, a.szp == nullptr, a.ids != nullptr, a.xg).total;
-    return smem <= 160 * 1024 && nblk < 65536;       // (nblk, sets_r share dwords with rs_cap, sets_q)
-}
-
-// Batch rows one launch of this configuration can take (0: not even one): LDS holds m rows of x (twice with a gather)
-int gemv_v3_max_rows(V3Args a, int m_want) {
-    for (int m = m_want < V3_MAX_M ? m_want : V3_MAX_M; m >= 1; --m) {
-        int nw;
-        size_t smem;
-        a.m = m;
-        if (gemv_v3_plan(a, nw, smem)) return m;
-    }
-    return 0;
-}
-
-hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st) {
-    int nw;
-    size_t smem;
-    if (a.m > V3_MAX_M || !gemv_v3_plan(a, nw, smem)) return hipErrorInvalidValue;
-    if (a.m > 1 && (mode != V3_MODE_PLAIN || a.bits == 3 || a.residual || a.ssq_in || a.xn_gamma)) return hipErrorInvalidValue;
-    if (a.xg && (a.m <= 1 || a.ids)) return hipErrorInvalidValue;      // x from global memory: batch-row launches without a gather
-    if (!a.szp && (a.xn_gamma || !a.scales || !a.zeros)) return hipErrorInvalidValue;     // (the zeros pointer uses xn_gamma's slot)
+    if (!no_nw12 && !f_nw && m <= 1 && p.nblk <= 256 && p.rs_cap == 1 && g.nfull >= 64) p.nw = 12;
+    p.smem = v3_lds(g.K, g.ngroups, g.n_out, p.rs_cap, m, p.nw, xn && !szn, szn, gather, xg).total;
     static const int f_d = env_int("QEFT_GEMV_DEPTH");     // lab override: 2, or 4 (= the deep form of the block's RSC: 4 or 6 loads)
     // Ring depth (tools/gemv_v3_lab.hip, interleaved timing, profiles/r03_gemv_lab.txt): where a CU holds ONE block and a wave has
     // at least 8 loads to make, 4 loads in flight per wave (6 with three or four row sets per block: two whole steps) --
     // q|k|v 7.06 (6) / 7.44 (4) / 7.69 us (2), down_proj 7.18 (4) / 7.59 (2) (the batch-row launches likewise: 8.65 vs 8.81); short launches (o_proj: 4 loads per wave) and
     // two blocks per CU (gate|up) keep 2: 4.58 vs 4.78, 10.97 vs 11.07 / 11.50.
-    const int loads_per_wave = ceil_div(a.g.nfull, nw) * a.rs_cap;
-    const int depth = a.xg ? 4 : f_d == 2 || f_d == 4 ? f_d : (a.nblk <= 256 && loads_per_wave >= 8 ? 4 : 2);     // (xg: the deep-ring instantiations only)
-    const bool w3 = a.bits == 3;
-    g_last_variant = a.m > 1 ? (a.xg ? "gemv_v3_mb_xg" : "gemv_v3_mb") : mode == V3_MODE_PAIR ? (w3 ? "gemv_v3_w3_pair" : "gemv_v3_pair") : (w3 ? "gemv_v3_w3" : "gemv_v3");
+    const int loads_per_wave = ceil_div(g.nfull, p.nw) * p.rs_cap;
+    const int depth = xg ? 4 : f_d == 2 || f_d == 4 ? f_d : (p.nblk <= 256 && loads_per_wave >= 8 ? 4 : 2);     // (xg: the deep-ring instantiations only)
+    p.D = p.nw == 4 ? 4 : p.nw == 12 ? 2 : depth < 4 ? 2 : p.rs_cap >= 3 ? 6 : 4;      // the instantiations of gemv_v3_dispatch.h
+    p.outl = g.n_out > 0;
+    p.mode = mode;
+    p.bits = bits == 3 ? 3 : 4;
+    p.mb = m > 1 ? 2 : 1;
+    p.xg = xg;
     // plain launches (no run-time flag, one batch row): the instantiations without the flag paths (gemv_v3_plain.hip)
-    if (a.m <= 1 && (v3_flags(a) & (V3_F_PERCH | V3_F_XN | V3_F_SZN | V3_F_OWIL | V3_F_GATHER)) == 0)
-        return gemv_v3_dispatch_plain(a, mode, smem, depth, st);
-    return w3 ? launch_b<3, true>(a, mode, a.nblk, smem, depth, st) : launch_b<4, true>(a, mode, a.nblk, smem, depth, st);
+    p.fl = !(m <= 1 && (flags & (V3_F_PERCH | V3_F_XN | V3_F_SZN | V3_F_OWIL | V3_F_GATHER)) == 0);
+    p.ok = m <= V3_MAX_M && p.smem <= 160 * 1024 && p.nblk < 65536 &&        // (nblk, sets_r share dwords with rs_cap, sets_q)
+           (mode == V3_MODE_PLAIN || mode == V3_MODE_PAIR) && p.rs_cap <= V3_MAX_RS &&
+           !(m > 1 && (mode != V3_MODE_PLAIN || p.bits == 3 || xn)) &&
+           !(xg && (m <= 1 || gather)) &&          // x from global memory: batch-row launches without a gather
+           !(szn && xn);                           // (the zeros pointer uses xn_gamma's slot)
+    return p;
+}
+
+// The flags of the plan for a pack: the run-time flags the kernel will see, and xg
+static uint32_t v3_plan_flags(const V3Args& a) {
+    return (v3_flags(a) & (V3_F_PERCH | V3_F_XN | V3_F_SZN | V3_F_OWIL | V3_F_GATHER)) | (a.xg ? V3_PLAN_XG : 0u);
+}
+
+// Batch rows one launch of this configuration can take (0: not even one): LDS holds m rows of x (twice with a gather)
+int gemv_v3_max_rows(V3Args a, int m_want) {
+    for (int m = m_want < V3_MAX_M ? m_want : V3_MAX_M; m >= 1; --m)
+        if (gemv_v3_plan(a.g, m, V3_MODE_PLAIN, a.bits, v3_plan_flags(a)).ok) return m;
+    return 0;
+}
+
+static thread_local V3Plan g_last_plan{};
+const V3Plan& gemv_v3_last_plan() { return g_last_plan; }
+
+hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st) {
+    if (a.m < 1) a.m = 1;
+    const V3Plan p = gemv_v3_plan(a.g, a.m, mode, a.bits, v3_plan_flags(a));
+    if (!p.ok) return hipErrorInvalidValue;
+    if (a.m > 1 && (a.residual || a.ssq_in)) return hipErrorInvalidValue;
+    if (!a.szp && (!a.scales || !a.zeros)) return hipErrorInvalidValue;
+    a.nblk = p.nblk, a.rs_cap = p.rs_cap, a.sets_q = p.sets_q, a.sets_r = p.sets_r, a.nw = p.nw;
+    const bool w3 = p.bits == 3;
+    g_last_variant = p.mb > 1 ? (p.xg ? "gemv_v3_mb_xg" : "gemv_v3_mb") : mode == V3_MODE_PAIR ? (w3 ? "gemv_v3_w3_pair" : "gemv_v3_pair") : (w3 ? "gemv_v3_w3" : "gemv_v3");
+    g_last_plan = p;
+    if (!p.fl) return gemv_v3_dispatch_plain(a, p, st);
+    return w3 ? launch_b<3, true>(a, p, st) : launch_b<4, true>(a, p, st);
 }
 
 // ---- host-side enumeration of every address the kernel can form for a configuration (no GPU involved).

@@ -4,8 +4,8 @@
 
 namespace qeft {
 
-hipError_t gemv_v3_dispatch_plain(const V3Args& a, int mode, size_t smem, int depth, hipStream_t st) {
-    return a.bits == 3 ? launch_b<3, false>(a, mode, a.nblk, smem, depth, st) : launch_b<4, false>(a, mode, a.nblk, smem, depth, st);
+hipError_t gemv_v3_dispatch_plain(const V3Args& a, const V3Plan& p, hipStream_t st) {
+    return p.bits == 3 ? launch_b<3, false>(a, p, st) : launch_b<4, false>(a, p, st);
 }
 
 }  // namespace qeft

@@ -15,7 +15,7 @@ and the fp16 output adds half an fp16 ulp of the value (it must also equal fp32_
 NaN buffer, the weight sits inside a NaN buffer, dx is a strided view between NaN bands that must stay NaN, workspace and dx sit
 between guard margins that must come back intact.  Every test prints its worst error / bound ratio ([lm_head_nll_grad] ...).
 
-The model-level tests compare causal_lm_loss with a dense pass the test writes itself, run once in fp64 and once with fp16 tensors
+The model-level tests compare causal_lm_loss with the dense pass of tests/dense_ref.py, run once in fp64 and once with fp16 tensors
 and plain torch ops: the project's route may be off the fp64 pass by at most twice what the fp16 torch pass is (the same rounding
 points summed in another order, plus the backward's dY rounded to fp16 once more)."""
 import math
@@ -23,6 +23,8 @@ import os
 
 import pytest
 import torch
+
+from dense_ref import dense_pass
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -369,49 +371,8 @@ def test_no_logits_in_memory():
     assert rises[4096] - rises[2048] <= added + 2 ** 20
 
 
-# ---- the tiny model: causal_lm_loss against a dense pass of the test's own, in fp64 and in fp16
+# ---- the tiny model: causal_lm_loss against the dense pass of tests/dense_ref.py, in fp64 and in fp16
 T_DOC = 48
-
-
-def _dense_pass(model, dense, leaves, tok2, targets, dt):
-    """Causal-LM mean NLL of tok2 [B, T] over dense weights; each linear's last n_out columns are leaves[li][name].  dt = F64: all
-    of it in fp64.  dt = F16: fp16 tensors and plain torch ops, rounded where causal_lm_loss rounds (norm, rotary and activation in
-    fp32 then fp16; fp16 matmuls and attention; fp32 cross-entropy of the fp16 logits)."""
-    s = model.shape
-    lo = dt == F16
-    up = F32 if lo else F64
-    B, T = tok2.shape
-    cos, sin = model.rope_cos[:T, None, :].to(up), model.rope_sin[:T, None, :].to(up)
-
-    def rms(x, g):
-        xf = x.to(up)
-        return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + s.rms_eps) * g.to(up)).to(dt)
-
-    def rope(x):
-        a, b = x[..., :64].to(up), x[..., 64:].to(up)
-        return torch.cat([a * cos - b * sin, b * cos + a * sin], dim=-1).to(dt)
-
-    def lin(x, li, name):
-        leaf = leaves[li][name]
-        W = torch.cat([dense[li][name][:, :-leaf.shape[1]].to(dt), leaf.to(dt)], dim=1)
-        return x @ W.t()
-
-    h = model.model.embed_tokens.weight[tok2.reshape(-1)].to(dt)
-    for li, L in enumerate(model.model.layers):
-        x = rms(h, L.input_layernorm.weight)
-        q = rope(lin(x, li, "q_proj").view(B, T, s.n_heads, 128))
-        k = rope(lin(x, li, "k_proj").view(B, T, s.n_kv_heads, 128))
-        v = lin(x, li, "v_proj").view(B, T, s.n_kv_heads, 128)
-        a = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True)
-        a = a.transpose(1, 2).reshape(B * T, s.hidden)[:, L.self_attn.o_proj.reorder_ids]
-        h = h + lin(a, li, "o_proj")
-        x = rms(h, L.post_attention_layernorm.weight)
-        act = (torch.nn.functional.silu(lin(x, li, "gate_proj").to(up)) * lin(x, li, "up_proj").to(up)).to(dt)
-        h = h + lin(act, li, "down_proj")
-    hn = rms(h, model.model.norm.weight)
-    logits = (hn @ model.lm_head.weight.to(dt).t()).to(up)
-    return torch.nn.functional.cross_entropy(logits, targets.long(), ignore_index=IGNORE, reduction="mean")
-
 
 NAMES = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
 SCALE = 1024.0
@@ -441,7 +402,7 @@ def tiny_train():
             out = []
             for dt in (F64, F16):
                 leaves = [{nm: v.to(F64 if dt == F64 else F32).requires_grad_(True) for nm, v in d.items()} for d in ow]
-                loss = _dense_pass(model, dense, leaves, tok2, targets, dt)
+                loss = dense_pass(model, dense, leaves, tok2, targets, dt)
                 (loss * (SCALE if dt == F16 else 1.0)).backward()
                 grads = [{nm: (v.grad.to(F64) / (SCALE if dt == F16 else 1.0)) for nm, v in d.items()} for d in leaves]
                 out += [loss.item(), grads]

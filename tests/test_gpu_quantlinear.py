@@ -179,18 +179,57 @@ def test_checkpoint_roundtrip_and_finetuned_delta(tmp_path):
     assert not torch.allclose(y0, y1)
 
 
+_SHARD_FULL = {}
+
+
+def _shard_layer(bits):
+    """(full layer, its buffers as numpy) of the row-shard test: made once per bit width, shared, never written."""
+    if bits not in _SHARD_FULL:
+        n, k, r, g = 2048, 1024, 128, 128
+        if bits == 4:
+            full, bufs, _ = build(n, k, r, g, "model.layers.0.mlp.up_proj", bias=True, seed=8)
+        else:
+            from qeft_amd.llama import synthetic_quantlinear
+            full = synthetic_quantlinear("model.layers.0.mlp.up_proj", k, n, r, g, 8, DEV, bits=3)
+            full.bias = (torch.randn(n, generator=torch.Generator().manual_seed(8)) * 0.1).half().to(DEV)
+            bufs = {kk: v.cpu().numpy() for kk, v in full.state_dict().items()}
+            bufs["bias"] = full.bias.cpu().numpy()
+        _SHARD_FULL[bits] = (full, bufs)
+    return _SHARD_FULL[bits]
+
+
 @pytest.mark.parametrize("world", [2, 4, 8])
-@pytest.mark.parametrize("m", [1, 3, 16])
+@pytest.mark.parametrize("m", [1, 3, 16, 40])
 def test_row_shards_on_gpu_concatenate_to_full_output(world, m):
     """sharded output == single-GPU output.  Every shard runs the same HIP kernels on its rows; the
     concatenation (what the all-gather produces) must equal the full layer's output bit for bit."""
+    _row_shards_concatenate(4, world, m)
+
+
+@pytest.mark.parametrize("world", [2, 4, 8])
+@pytest.mark.parametrize("m", [1, 3, 16, 40])
+def test_row_shards_of_a_3bit_layer_concatenate_to_full_output(world, m):
+    """The same for bits = 3 (a function of its own so that the 4-bit cases keep their ids): shards of whole 16-row sets
+    (sharded.shard_bounds), m on both sides of _forward_w3's 16-row switch (gemv_3bit: one row, 2..16 rows) and past it
+    (gemm_3bit_qeft)."""
+    _row_shards_concatenate(3, world, m)
+
+
+def _row_shards_concatenate(bits, world, m):
+    from qeft_amd import _lib
     from qeft_amd.sharded import shard_quantlinear
     n, k, r, g = 2048, 1024, 128, 128
-    full, bufs, _ = build(n, k, r, g, "model.layers.0.mlp.up_proj", bias=True, seed=8)
+    full, bufs = _shard_layer(bits)
     x = torch.from_numpy(O.make_activation(m, k, r, seed=m)).to(DEV)
     y_full = full(x)
-    parts = [shard_quantlinear(full, rank, world).to(DEV)(x) for rank in range(world)]
+    shards = [shard_quantlinear(full, rank, world).to(DEV) for rank in range(world)]
+    assert all(sh.bits == bits and sh.outfeatures == n // world and sh.qweight.dtype == full.qweight.dtype for sh in shards)
+    parts = [sh(x) for sh in shards]
+    variant = _lib.last_variant()
     torch.cuda.synchronize()
+    if bits == 3:
+        assert variant == ("gemv_w3" if m == 1 else "gemv_w3_rows") or m > 16, variant
+        assert variant not in ("gemv_w3", "gemv_w3_rows") or m <= 16, variant
     y = torch.cat(parts, dim=-1)
     assert torch.equal(y, y_full)
     yref = O.quant_linear(x.cpu().numpy(), bufs["qweight"], bufs["scales"], bufs["scaled_zeros"], bufs["oweight"],

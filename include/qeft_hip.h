@@ -222,7 +222,10 @@ int qeft_rope_attn_decode(const void* q, const void* k, const void* v, const voi
  *   k_cache_ft  fp16 [n_kv][128/8][max_seq][8]   (FasterTransformer key layout, ft_attention.cpp:131-133)
  *   v_cache     fp16 [n_kv][max_seq][128]
  * one sequence, head_dim 128, neox rotary from the cos/sin table (tab_rows as above), one block per head, natural output
- * order, max_seq % 16 == 0 and at most 32768 as above.  The Python shim loops over the batch and raises for ALiBi / other head sizes / interleaved rotary. */
+ * order, max_seq % 16 == 0 and at most 32768 as above.  The Python shim loops over the batch; it sends ALiBi to
+ * qeft_single_query_attention_alibi and the other head sizes to qeft_single_query_attention_generic (both below), and rotates
+ * q / k itself, in front of a launch with an identity table, for a partial or an interleaved (GPT-J) rotary.  It raises for
+ * fp32 / bf16 and for head sizes that are no multiple of 8 or above 256. */
 int qeft_single_query_attention(const void* q, const void* k, const void* v, const void* cos_tab, const void* sin_tab,
                                 int tab_rows, void* k_cache_ft, void* v_cache, const int* pos, void* out, int n_heads,
                                 int n_kv_heads, int max_seq, qeft_stream_t stream);

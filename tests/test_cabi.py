@@ -233,7 +233,8 @@ def test_attention_entries_refuse_a_cache_above_the_ceiling(lib):
     """include/qeft_hip.h: max_seq <= 32768 on the four attention entries that share a cache (the one-token kernel keeps one
     raw fp32 score per cache row in LDS).  32768 + 16 is a multiple of 16 and nothing else about the call is wrong, so the
     ceiling alone answers QEFT_ERR_SHAPE, before any pointer is looked at; at 32768 the same calls pass the shape checks
-    (their NULL cache is what is refused then)."""
+    (their NULL cache is what is refused then).  qeft_single_query_attention_generic has the same ceiling for the same reason,
+    without the multiple-of-16 rule: 32769 is refused, and it looks at its pointers first."""
     P, ERR_SHAPE, ERR_NULL = 1 << 20, 2, 4
     heads, kv = 32, 8
 
@@ -252,10 +253,46 @@ def test_attention_entries_refuse_a_cache_above_the_ceiling(lib):
         assert code == ERR_SHAPE, (name, code)
     for name, code in calls(32768, None).items():
         assert code == ERR_NULL, (name, code)
+    # the generic entry keeps one score per cache row in LDS too: the same ceiling, without the multiple-of-16 rule
+    generic = lib.qeft_single_query_attention_generic
+    assert generic(P, P, P, P, P, P, P, heads, kv, 32768 + 1, 64, None, None) == ERR_SHAPE
+    assert generic(P, P, P, None, P, P, P, heads, kv, 32768, 64, None, None) == ERR_NULL
     # the whole-table rotary form at the ceiling's far side: still the shape, not the table
     assert lib.qeft_rope_attn_decode(P, P, P, P, P, 32768 + 16, P, P, P, None, P, P, 8, heads, kv, 32768 + 16, None) == ERR_SHAPE
     text = re.sub(r"\s*\n \*\s*", " ", open(os.path.join(ROOT, "include", "qeft_hip.h")).read())
     assert text.count("max_seq <= 32768") >= 3 and "at most 32768" in text        # stated where the entries are declared
+
+
+def test_generic_single_query_attention_refusals(lib):
+    """qeft_single_query_attention_generic refuses, in this order, a NULL operand (QEFT_ERR_NULL; alibi_slopes alone is optional),
+    a shape it does not take (QEFT_ERR_SHAPE: head_dim outside the multiples of 8 in [8, 256], n_heads % n_kv_heads, an empty
+    cache) and a cache that is not 16-byte aligned (QEFT_ERR_ALIGN).  Operands are made-up addresses: every call has something
+    wrong, so none reaches a launch."""
+    P, ERR_SHAPE, ERR_NULL, ERR_ALIGN = 1 << 20, 2, 4, 6
+    generic = lib.qeft_single_query_attention_generic
+
+    def call(ptrs=None, heads=8, kv=2, max_seq=64, head_dim=64, alibi=None):
+        return generic(*(ptrs or [P] * 7), heads, kv, max_seq, head_dim, alibi, None)
+
+    names = ["q", "k", "v", "k_cache_ft", "v_cache", "pos", "out"]
+    for i, name in enumerate(names):
+        ptrs = [P] * 7
+        ptrs[i] = None
+        assert call(ptrs) == ERR_NULL, name
+        assert call(ptrs, alibi=P) == ERR_NULL, name
+        assert call(ptrs, head_dim=12) == ERR_NULL, name                # NULL is looked at before the shape
+    for head_dim in (0, 4, 12, 264, -8):
+        assert call(head_dim=head_dim) == ERR_SHAPE, head_dim
+    assert call(heads=8, kv=3) == ERR_SHAPE
+    assert call(heads=0) == ERR_SHAPE and call(kv=0) == ERR_SHAPE
+    assert call(max_seq=0) == ERR_SHAPE
+    for i in (3, 4):
+        ptrs = [P] * 7
+        ptrs[i] = P + 2
+        assert call(ptrs) == ERR_ALIGN, names[i]
+        assert call(ptrs, alibi=P) == ERR_ALIGN, names[i]
+        assert call(ptrs, head_dim=12) == ERR_SHAPE, names[i]           # the shape before the alignment
+        assert call(ptrs, max_seq=0) == ERR_SHAPE, names[i]
 
 
 def test_refusals_are_those_recorded_before_the_argument_builders(lib):

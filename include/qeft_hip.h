@@ -565,6 +565,35 @@ int qeft_attn_train_bwd_part(const void* q, int q_stride, const void* k, const v
 long long qeft_attn_train_bwd_check_extents(int q_stride, int kv_stride, int out_stride, int dout_stride, int dq_stride, int dkv_stride,
                                             int n_seq, int t, int n_heads, int n_kv_heads);
 
+/* The same attention over PACKED sequences of unequal length (the varlen kernels of csrc/attn_train.hip; qeft_amd/attention.py:
+ * causal_attention_packed; finetune.causal_lm_loss(seq_lens=...)).  The operands are those above over R
+ * rows; `n_seq, t` give way to `seq_rows, n_seq`: seq_rows is a HOST array of n_seq + 1 ints, the prefix of the lengths --
+ * seq_rows[0] = 0, strictly increasing, seq_rows[n_seq] = R -- and sequence i is rows seq_rows[i] .. seq_rows[i + 1] - 1 of every
+ * operand, from position 0, attending itself alone.  The prefix is copied into the launches' arguments during the call (nothing
+ * on the device, nothing read after the call returns; capturable into a graph, which then holds these lengths).  The bodies are
+ * those of the fixed-length kernels: a sequence's out, lse, dq, dk, dv are, bit for bit, what qeft_attn_train_fwd / _bwd give
+ * for that sequence alone, whatever is packed around it, in whatever order and at whatever strides.  Grids (blocks of the
+ * longest sequence, n_seq); the delta launch runs over the R rows as it is.  Workspace: 4 * R * n_heads bytes.
+ * QEFT_ERR_SHAPE: n_seq outside 1 .. 128, the head and stride rules above; then QEFT_ERR_NULL for seq_rows (it is read here);
+ * then QEFT_ERR_SHAPE for a prefix that does not start at 0, is not strictly increasing or ends above 2^20, and for a short
+ * workspace -- all before any device pointer is looked at; then QEFT_ERR_NULL, then QEFT_ERR_ALIGN as above.
+ * _bwd_workspace_bytes: 0 for what the entries refuse; _bwd_part, _check_extents, _bwd_check_extents: as their namesakes above. */
+int qeft_attn_train_varlen_fwd(const void* q, int q_stride, const void* k, const void* v, int kv_stride, void* out, int out_stride,
+                               float* lse, const int* seq_rows, int n_seq, int n_heads, int n_kv_heads, qeft_stream_t stream);
+long long qeft_attn_train_varlen_check_extents(int q_stride, int kv_stride, int out_stride, const int* seq_rows, int n_seq, int n_heads,
+                                               int n_kv_heads);
+long long qeft_attn_train_varlen_bwd_workspace_bytes(const int* seq_rows, int n_seq, int n_heads, int n_kv_heads);
+int qeft_attn_train_varlen_bwd(const void* q, int q_stride, const void* k, const void* v, int kv_stride, const void* out, int out_stride,
+                               const void* dout, int dout_stride, const float* lse, void* dq, int dq_stride, void* dk, void* dv,
+                               int dkv_stride, void* workspace, long long workspace_bytes, const int* seq_rows, int n_seq, int n_heads,
+                               int n_kv_heads, qeft_stream_t stream);
+int qeft_attn_train_varlen_bwd_part(const void* q, int q_stride, const void* k, const void* v, int kv_stride, const void* out,
+                                    int out_stride, const void* dout, int dout_stride, const float* lse, void* dq, int dq_stride,
+                                    void* dk, void* dv, int dkv_stride, void* workspace, long long workspace_bytes, const int* seq_rows,
+                                    int n_seq, int n_heads, int n_kv_heads, int part, qeft_stream_t stream);
+long long qeft_attn_train_varlen_bwd_check_extents(int q_stride, int kv_stride, int out_stride, int dout_stride, int dq_stride,
+                                                   int dkv_stride, const int* seq_rows, int n_seq, int n_heads, int n_kv_heads);
+
 /* The glue of the training step (csrc/train_glue.hip; qeft_amd/glue.py: add_rmsnorm, swiglu; finetune.causal_lm_loss
  * with glue="fused"): forwards over a batch of rows and a backward for each.  Memory-bound row kernels:
  * 16-byte accesses, fp32 math, every output rounded to fp16 exactly once, no atomics, no workspace.  A row's results depend on

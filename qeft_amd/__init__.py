@@ -4,8 +4,8 @@ The scoring and fine-tuning entry points are exported here; they resolve on firs
 `qeft_amd.build`, which runs before the library exists) stays free of torch and of the HIP library.
 """
 _SCORING = ("score", "eval_nll", "lm_head_nll", "lm_head_nll_loss")
-_FINETUNE = ("causal_lm_loss", "shift_labels")           # qeft_amd.finetune also has begin(model) / end(model)
-_ATTENTION = ("causal_attention",)
+_FINETUNE = ("causal_lm_loss", "shift_labels", "pack_sequences")       # qeft_amd.finetune also has begin(model) / end(model)
+_ATTENTION = ("causal_attention", "causal_attention_packed")
 _GLUE = ("add_rmsnorm", "swiglu", "rope_qk")
 __all__ = [*_SCORING, *_FINETUNE, *_ATTENTION, *_GLUE]
 

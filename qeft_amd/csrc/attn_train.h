@@ -7,6 +7,10 @@
 //   q, out, dout, dq  [n_seq t][>= n_heads 128]  fp16 at q_stride / out_stride / dout_stride / dq_stride
 //   k, v              [n_seq t][>= n_kv 128]     fp16 at kv_stride (both)            dk, dv the same at dkv_stride (both)
 //   lse, delta        [n_seq t][n_heads]         fp32, contiguous
+//
+// The variable-length launches take the same operands over R rows with sequence i at rows
+// cu[i] .. cu[i + 1] - 1: a block builds the AtGeom of its own sequence alone (at_var_seq) and offsets every pointer by
+// at_var_base, and everything behind that is the code above, at seq = 0.
 #pragma once
 #include "prefill_attn.h"
 
@@ -72,11 +76,47 @@ __host__ __device__ inline int at_dkv_kvh(const AtGeom& A, int block) { return b
 __host__ __device__ inline int at_dkv_first_tile(int kblock) { return kblock * (AT_KB / AT_QT); }
 __host__ __device__ inline int at_dkv_end_tile(const AtGeom& A) { return (A.f.g.t - 1) / AT_QT + 1; }
 
+// ---- variable-length launches: n_seq <= AT_MAX_SEQ sequences of cu[i + 1] - cu[i] >= 1 rows, the prefix by value in the kernel
+// arguments (no device-side table: what the host validated is what the kernel reads)
+constexpr int AT_MAX_SEQ = 128;
+struct AtVarGeom {
+    AtGeom a;                               // strides and heads; a.f.g.t = a.f.g.kv_rows = the LONGEST sequence (the grids), a.n_seq
+    int cu[AT_MAX_SEQ + 1];                 // cu[0] = 0 < cu[1] < ... < cu[n_seq] = R; the rest unused
+};
+__host__ __device__ inline int at_var_rows(const AtVarGeom& V) { return V.cu[V.a.n_seq]; }
+__host__ __device__ inline long long at_var_base(const AtVarGeom& V, int seq, int stride) { return (long long)V.cu[seq] * stride; }
+// sequence `seq` as one sequence of its own length: the geometry every at_* / pa_* function above takes, at seq = 0
+__host__ __device__ inline AtGeom at_var_seq(const AtVarGeom& V, int seq) {
+    AtGeom A = V.a;
+    A.f.g.t = A.f.g.kv_rows = V.cu[seq + 1] - V.cu[seq];
+    A.n_seq = 1;
+    return A;
+}
+// all R rows as one sequence: the delta launch is row-wise over global rows
+__host__ __device__ inline AtGeom at_var_all(const AtVarGeom& V) {
+    AtGeom A = V.a;
+    A.f.g.t = A.f.g.kv_rows = at_var_rows(V);
+    A.n_seq = 1;
+    return A;
+}
+// grids (x, y = n_seq): x covers the longest sequence; a block whose x is past its own sequence's count returns at once.  Within
+// a sequence x is the block index of the fixed-length launches: the heaviest Q tile first, key block 0 first.
+__host__ __device__ inline int at_dkv_blocks_per_seq(const AtGeom& A) { return at_kblocks(A) * A.f.g.n_kv; }
+__host__ __device__ inline int at_var_q_grid_x(const AtVarGeom& V) { return at_q_blocks_per_seq(V.a); }
+__host__ __device__ inline int at_var_dkv_grid_x(const AtVarGeom& V) { return at_dkv_blocks_per_seq(V.a); }
+
 // ---- host side: attn_train.hip
 hipError_t attn_train_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, const AtGeom& A, hipStream_t st);
 hipError_t attn_train_bwd_launch(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse,
                                  void* dq, void* dk, void* dv, float* delta, const AtGeom& A, int parts, hipStream_t st);
 long long attn_train_fwd_count_out_of_range(const AtGeom& A);
 long long attn_train_bwd_count_out_of_range(const AtGeom& A);
+hipError_t attn_train_varlen_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, const AtVarGeom& V,
+                                        hipStream_t st);
+hipError_t attn_train_varlen_bwd_launch(const void* q, const void* k, const void* v, const void* out, const void* dout,
+                                        const float* lse, void* dq, void* dk, void* dv, float* delta, const AtVarGeom& V, int parts,
+                                        hipStream_t st);
+long long attn_train_varlen_fwd_count_out_of_range(const AtVarGeom& V);
+long long attn_train_varlen_bwd_count_out_of_range(const AtVarGeom& V);
 
 }  // namespace qeft

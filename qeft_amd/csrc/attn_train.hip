@@ -19,8 +19,15 @@
 //   p = exp(s 128^-0.5 - lse) in fp32 (no running max); P rounded to fp16 for dV; dS = p (dP - delta) in fp32, rounded once to
 //   fp16; the 128^-0.5 of dK and dQ applied in fp32 in the epilogue.  Masked (key, row) pairs are SELECTED to p = dS = 0; rows
 //   past t are staged as zeros where a transposed product reads them, computed where a lane owns them, never stored.
-// Every global address comes from attn_train.h / prefill_attn.h, clamped into its sequence; the two *_count_out_of_range below
+// Every global address comes from attn_train.h / prefill_attn.h, clamped into its sequence; the *_count_out_of_range below
 // walk the same functions on the CPU.
+//
+// Packed sequences of unequal length (qeft_attn_train_varlen_fwd / _bwd): the three bodies are device
+// functions of one block of one sequence (at_fwd_block, at_dkv_block, at_dq_block), each called by two kernels.  The
+// fixed-length kernel finds its sequence in blockIdx.x; the variable-length kernel takes it from blockIdx.y, reads its first row
+// and length out of the prefix in its own arguments (AtVarGeom, by value: no table on the device), builds that sequence's AtGeom,
+// puts at_var_base on every pointer and runs the body at seq = 0 -- so a sequence's bits are those of the fixed-length launch on
+// it alone.  A block past its sequence's count returns before it forms an address.  delta is row-wise and runs as it is.
 #include "attn_train.h"
 #include "prefill_attn_body.h"
 
@@ -55,6 +62,14 @@ struct PaStageTrain {
     }
 };
 
+// block `block` of ONE sequence of A.f.g.t rows, every operand at the sequence's first row: what both forward kernels run
+__device__ __forceinline__ void at_fwd_block(const f16* q, const f16* k, const f16* v, f16* out, float* lse, const AtGeom& A, int block,
+                                             unsigned char* lds_k, unsigned char* lds_v) {
+    const PaGeom& G = A.f.g;
+    PaStageTrain stage{k, v, A.f, pa_kv_head(G, pa_block_head(G, block)), (int)threadIdx.x};
+    pa_attend<true>(q, out, G, stage, lds_k, lds_v, block, lse);
+}
+
 __global__ __launch_bounds__(PA_THREADS) void attn_train_fwd_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
                                                                     const f16* __restrict__ v, f16* __restrict__ out,
                                                                     float* __restrict__ lse, AtGeom A) {
@@ -67,14 +82,40 @@ __global__ __launch_bounds__(PA_THREADS) void attn_train_fwd_kernel(const f16* _
     v += at_seq_base(A, seq, A.f.new_stride);
     out += at_seq_base(A, seq, G.out_stride);
     lse += at_seq_base(A, seq, G.n_heads);
-    PaStageTrain stage{k, v, A.f, pa_kv_head(G, pa_block_head(G, block)), (int)threadIdx.x};
-    pa_attend<true>(q, out, G, stage, lds_k, lds_v, block, lse);
+    at_fwd_block(q, k, v, out, lse, A, block, lds_k, lds_v);
+}
+
+// the variable-length forward: grid (blocks of the longest sequence, n_seq).  The block's sequence becomes a geometry of its own
+// and a base on every pointer; a block past its sequence's count leaves before it forms an address.
+__global__ __launch_bounds__(PA_THREADS) void attn_train_varlen_fwd_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                           const f16* __restrict__ v, f16* __restrict__ out,
+                                                                           float* __restrict__ lse, AtVarGeom V) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_k[PA_KT * PA_HD * 2];
+    __shared__ __attribute__((aligned(16))) unsigned char lds_v[PA_KT * PA_HD * 2];
+    const int seq = blockIdx.y, block = blockIdx.x;
+    const AtGeom A = at_var_seq(V, seq);
+    if (block >= at_q_blocks_per_seq(A)) return;
+    const PaGeom& G = A.f.g;
+    q += at_var_base(V, seq, G.q_stride);
+    k += at_var_base(V, seq, A.f.new_stride);
+    v += at_var_base(V, seq, A.f.new_stride);
+    out += at_var_base(V, seq, G.out_stride);
+    lse += at_var_base(V, seq, G.n_heads);
+    at_fwd_block(q, k, v, out, lse, A, block, lds_k, lds_v);
 }
 
 hipError_t attn_train_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, const AtGeom& A, hipStream_t st) {
     g_last_variant = "attn_train_fwd";
     hipLaunchKernelGGL(attn_train_fwd_kernel, dim3((unsigned)at_q_blocks(A)), dim3(PA_THREADS), 0, st, (const f16*)q, (const f16*)k,
                        (const f16*)v, (f16*)out, lse, A);
+    return hipGetLastError();
+}
+
+hipError_t attn_train_varlen_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, const AtVarGeom& V,
+                                        hipStream_t st) {
+    g_last_variant = "attn_train_varlen_fwd";
+    hipLaunchKernelGGL(attn_train_varlen_fwd_kernel, dim3((unsigned)at_var_q_grid_x(V), (unsigned)V.a.n_seq), dim3(PA_THREADS), 0, st,
+                       (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, lse, V);
     return hipGetLastError();
 }
 
@@ -124,16 +165,13 @@ __global__ __launch_bounds__(AT_THREADS) void attn_train_delta_kernel(const f16*
 // VGPR / AGPR budget of a wave (one wave per SIMD, 512 registers): K and V fragments 32 + 32, dK^T and dV^T accumulators
 // 64 + 64, S and dP of one 64-row tile 32 + 32, P and dS in fp16 16 + 16, the next tile's staging 33.  LDS: 16 KiB per image,
 // two images, 512 bytes of lse | delta.
-__global__ __launch_bounds__(AT_THREADS) void attn_train_dkv_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
-                                                                    const f16* __restrict__ v, const f16* __restrict__ dout,
-                                                                    const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                    f16* __restrict__ dk, f16* __restrict__ dv, AtGeom A) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds_q[AT_QT * PA_HD * 2];
-    __shared__ __attribute__((aligned(16))) unsigned char lds_do[AT_QT * PA_HD * 2];
-    __shared__ __attribute__((aligned(16))) float lds_ld[2 * AT_QT];               // lse of the tile's rows, then delta
+// The body: key block `kblock` of kv head `kvh` of sequence `seq` of A (the variable-length kernel: of its one sequence, seq = 0,
+// behind the bases it put on the pointers).  lds_ld: lse of the tile's rows, then delta.
+__device__ __forceinline__ void at_dkv_block(const f16* q, const f16* k, const f16* v, const f16* dout, const float* lse,
+                                             const float* delta, f16* dk, f16* dv, const AtGeom& A, int seq, int kblock, int kvh,
+                                             unsigned char* lds_q, unsigned char* lds_do, float* lds_ld) {
     const PaGeom& G = A.f.g;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int seq = at_dkv_seq(A, blockIdx.x), kblock = at_dkv_kblock(A, blockIdx.x), kvh = at_dkv_kvh(A, blockIdx.x);
     const int rep = G.n_heads / G.n_kv;
     const int wave_key0 = kblock * AT_KB + wave * 32, key = wave_key0 + r, krow = at_row(A, key);
     const bool wave_on = wave_key0 < G.t;                            // wave-uniform
@@ -252,18 +290,50 @@ __global__ __launch_bounds__(AT_THREADS) void attn_train_dkv_kernel(const f16* _
     }
 }
 
+__global__ __launch_bounds__(AT_THREADS) void attn_train_dkv_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                    const f16* __restrict__ v, const f16* __restrict__ dout,
+                                                                    const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                    f16* __restrict__ dk, f16* __restrict__ dv, AtGeom A) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_q[AT_QT * PA_HD * 2];
+    __shared__ __attribute__((aligned(16))) unsigned char lds_do[AT_QT * PA_HD * 2];
+    __shared__ __attribute__((aligned(16))) float lds_ld[2 * AT_QT];
+    at_dkv_block(q, k, v, dout, lse, delta, dk, dv, A, at_dkv_seq(A, blockIdx.x), at_dkv_kblock(A, blockIdx.x),
+                 at_dkv_kvh(A, blockIdx.x), lds_q, lds_do, lds_ld);
+}
+
+// variable-length: grid (key blocks x kv heads of the longest sequence, n_seq); see attn_train_varlen_fwd_kernel
+__global__ __launch_bounds__(AT_THREADS) void attn_train_varlen_dkv_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                           const f16* __restrict__ v, const f16* __restrict__ dout,
+                                                                           const float* __restrict__ lse,
+                                                                           const float* __restrict__ delta, f16* __restrict__ dk,
+                                                                           f16* __restrict__ dv, AtVarGeom V) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_q[AT_QT * PA_HD * 2];
+    __shared__ __attribute__((aligned(16))) unsigned char lds_do[AT_QT * PA_HD * 2];
+    __shared__ __attribute__((aligned(16))) float lds_ld[2 * AT_QT];
+    const int seq = blockIdx.y, block = blockIdx.x;
+    const AtGeom A = at_var_seq(V, seq);
+    if (block >= at_dkv_blocks_per_seq(A)) return;
+    const PaGeom& G = A.f.g;
+    q += at_var_base(V, seq, G.q_stride);
+    k += at_var_base(V, seq, A.f.new_stride);
+    v += at_var_base(V, seq, A.f.new_stride);
+    dout += at_var_base(V, seq, A.dout_stride);
+    lse += at_var_base(V, seq, G.n_heads);
+    delta += at_var_base(V, seq, G.n_heads);
+    dk += at_var_base(V, seq, A.dkv_stride);
+    dv += at_var_base(V, seq, A.dkv_stride);
+    at_dkv_block(q, k, v, dout, lse, delta, dk, dv, A, 0, at_dkv_kblock(A, block), at_dkv_kvh(A, block), lds_q, lds_do, lds_ld);
+}
+
 // ---------------------------------------------------------------- dQ
 // Registers of a wave: Q and dO fragments 32 + 32, dQ^T accumulators 64, S^T and dP^T of one 64-key tile 32 + 32, dS in fp16 16,
 // the next tile's staging 32.  LDS: a K and a V image of 16 KiB.
-__global__ __launch_bounds__(AT_THREADS) void attn_train_dq_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
-                                                                   const f16* __restrict__ v, const f16* __restrict__ dout,
-                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                   f16* __restrict__ dq, AtGeom A) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds_k[PA_KT * PA_HD * 2];
-    __shared__ __attribute__((aligned(16))) unsigned char lds_v[PA_KT * PA_HD * 2];
+// The body: block `block` (head, Q tile) of sequence `seq` of A (the variable-length kernel: of its one sequence, seq = 0).
+__device__ __forceinline__ void at_dq_block(const f16* q, const f16* k, const f16* v, const f16* dout, const float* lse,
+                                            const float* delta, f16* dq, const AtGeom& A, int seq, int block, unsigned char* lds_k,
+                                            unsigned char* lds_v) {
     const PaGeom& G = A.f.g;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int per_seq = at_q_blocks_per_seq(A), seq = blockIdx.x / per_seq, block = blockIdx.x % per_seq;
     const int qtile = pa_block_qtile(G, block), head = pa_block_head(G, block), kvh = pa_kv_head(G, head);
     const int n_tiles = pa_key_tiles(G, qtile);
 
@@ -365,6 +435,38 @@ __global__ __launch_bounds__(AT_THREADS) void attn_train_dq_kernel(const f16* __
     }
 }
 
+__global__ __launch_bounds__(AT_THREADS) void attn_train_dq_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                   const f16* __restrict__ v, const f16* __restrict__ dout,
+                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                   f16* __restrict__ dq, AtGeom A) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_k[PA_KT * PA_HD * 2];
+    __shared__ __attribute__((aligned(16))) unsigned char lds_v[PA_KT * PA_HD * 2];
+    const int per_seq = at_q_blocks_per_seq(A);
+    at_dq_block(q, k, v, dout, lse, delta, dq, A, blockIdx.x / per_seq, blockIdx.x % per_seq, lds_k, lds_v);
+}
+
+// variable-length: grid (heads x Q tiles of the longest sequence, n_seq); see attn_train_varlen_fwd_kernel
+__global__ __launch_bounds__(AT_THREADS) void attn_train_varlen_dq_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
+                                                                          const f16* __restrict__ v, const f16* __restrict__ dout,
+                                                                          const float* __restrict__ lse,
+                                                                          const float* __restrict__ delta, f16* __restrict__ dq,
+                                                                          AtVarGeom V) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_k[PA_KT * PA_HD * 2];
+    __shared__ __attribute__((aligned(16))) unsigned char lds_v[PA_KT * PA_HD * 2];
+    const int seq = blockIdx.y, block = blockIdx.x;
+    const AtGeom A = at_var_seq(V, seq);
+    if (block >= at_q_blocks_per_seq(A)) return;
+    const PaGeom& G = A.f.g;
+    q += at_var_base(V, seq, G.q_stride);
+    k += at_var_base(V, seq, A.f.new_stride);
+    v += at_var_base(V, seq, A.f.new_stride);
+    dout += at_var_base(V, seq, A.dout_stride);
+    lse += at_var_base(V, seq, G.n_heads);
+    delta += at_var_base(V, seq, G.n_heads);
+    dq += at_var_base(V, seq, A.dq_stride);
+    at_dq_block(q, k, v, dout, lse, delta, dq, A, 0, block, lds_k, lds_v);
+}
+
 // parts: bit 0 the delta launch, bit 1 dK / dV, bit 2 dQ, in this order (qeft_attn_train_bwd: all three; qeft_attn_train_bwd_part:
 // one alone, for the timing tool and the variant tests)
 hipError_t attn_train_bwd_launch(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse,
@@ -390,7 +492,38 @@ hipError_t attn_train_bwd_launch(const void* q, const void* k, const void* v, co
     return hipSuccess;
 }
 
+// the same three launches over a prefix of sequence lengths; delta is row-wise over global rows and runs as it is, with all R
+// rows as one sequence
+hipError_t attn_train_varlen_bwd_launch(const void* q, const void* k, const void* v, const void* out, const void* dout,
+                                        const float* lse, void* dq, void* dk, void* dv, float* delta, const AtVarGeom& V, int parts,
+                                        hipStream_t st) {
+    const dim3 seqs_q((unsigned)at_var_q_grid_x(V), (unsigned)V.a.n_seq), seqs_k((unsigned)at_var_dkv_grid_x(V), (unsigned)V.a.n_seq);
+    if (parts & 1) {
+        const AtGeom D = at_var_all(V);
+        g_last_variant = "attn_train_delta";
+        hipLaunchKernelGGL(attn_train_delta_kernel, dim3((unsigned)at_delta_blocks(D)), dim3(AT_THREADS), 0, st, (const f16*)out,
+                           (const f16*)dout, delta, D);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    if (parts & 2) {
+        g_last_variant = "attn_train_varlen_dkv";
+        hipLaunchKernelGGL(attn_train_varlen_dkv_kernel, seqs_k, dim3(AT_THREADS), 0, st, (const f16*)q, (const f16*)k, (const f16*)v,
+                           (const f16*)dout, lse, (const float*)delta, (f16*)dk, (f16*)dv, V);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    if (parts & 4) {
+        g_last_variant = "attn_train_varlen_dq";
+        hipLaunchKernelGGL(attn_train_varlen_dq_kernel, seqs_q, dim3(AT_THREADS), 0, st, (const f16*)q, (const f16*)k, (const f16*)v,
+                           (const f16*)dout, lse, (const float*)delta, (f16*)dq, V);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
+}
+
 // ---------------------------------------------------------------- the address enumerations (CPU)
+// One walker per launch and sequence, shared by the fixed-length enumerations (sequence `seq` of A, no further base) and the
+// variable-length ones (A = at_var_seq, seq = 0, behind the at_var_base of every operand): the functions the kernels call, in
+// the kernels' order of composition.
 namespace {
 struct AtWorst {
     long long worst = 0;
@@ -399,102 +532,154 @@ struct AtWorst {
         if (b + bytes - operand_bytes > worst) worst = b + bytes - operand_bytes;
     }
 };
-// bytes of an operand of n_seq t rows at `stride`, the last one `width` elements wide
-inline long long at_bytes(const AtGeom& A, int stride, int width) {
-    return 2 * (((long long)A.n_seq * A.f.g.t - 1) * stride + width);
-}
-}  // namespace
-
-// The forward: the largest number of bytes by which an address passes the end of its operand or runs in front of it, 0 when
-// none does.  q and out per sequence as prefill_attn_count_out_of_range; K, V: n_seq t rows at kv_stride, the last n_kv * 128
-// wide; lse fp32 [n_seq t][n_heads].
-long long attn_train_fwd_count_out_of_range(const AtGeom& A) {
-    const PaGeom& G = A.f.g;
-    const long long kv_bytes = at_bytes(A, A.f.new_stride, G.n_kv * PA_HD), q_bytes = at_bytes(A, G.q_stride, G.n_heads * PA_HD);
-    const long long out_bytes = at_bytes(A, G.out_stride, G.n_heads * PA_HD), lse_bytes = 4ll * A.n_seq * G.t * G.n_heads;
-    AtWorst w;
-    const int per_seq = at_q_blocks_per_seq(A);
-    for (int seq = 0; seq < A.n_seq; ++seq) {
-        const long long qb = 2 * at_seq_base(A, seq, G.q_stride), ob = 2 * at_seq_base(A, seq, G.out_stride);
-        const long long kb = 2 * at_seq_base(A, seq, A.f.new_stride), lb = 4 * at_seq_base(A, seq, G.n_heads);
-        for (int block = 0; block < per_seq; ++block) {
-            const int qtile = pa_block_qtile(G, block), head = pa_block_head(G, block), kvh = pa_kv_head(G, head);
-            // pa_walk_q_out names the operand by its size within one sequence: q loads are 16 bytes, out stores 8
-            pa_walk_q_out(G, block, [&](long long b, int bytes, long long) {
-                if (bytes == 16) w(qb + b, bytes, q_bytes); else w(ob + b, bytes, out_bytes);
-            });
-            for (int row = qtile * PA_QT; row < qtile * PA_QT + PA_QT && row < G.t; ++row)
-                w(lb + 4 * pa_lse_off(G, row, head), 4, lse_bytes);
-            const int n_tiles = pa_key_tiles(G, qtile);
-            for (int tile = 0; tile < n_tiles; ++tile)
-                for (int c = 0; c < PA_CHUNKS; ++c)                // K and V share the offset
-                    w(kb + 2 * pa8_new_off(A.f, pa8_new_row(G, tile * PA_KT + (c >> 4)), kvh, c & 15), 16, kv_bytes);
-        }
+// bytes of an operand of `rows` rows at `stride`, the last one `width` elements wide
+inline long long at_bytes(long long rows, int stride, int width) { return 2 * ((rows - 1) * stride + width); }
+struct AtSizes {                             // bytes of every operand of a launch over `rows` rows
+    long long q, out, dout, dq, kv, dkv, lse;
+    AtSizes(const AtGeom& A, long long rows) {
+        const PaGeom& G = A.f.g;
+        const int hw = G.n_heads * PA_HD, kw = G.n_kv * PA_HD;
+        q = at_bytes(rows, G.q_stride, hw), out = at_bytes(rows, G.out_stride, hw), dout = at_bytes(rows, A.dout_stride, hw);
+        dq = at_bytes(rows, A.dq_stride, hw), kv = at_bytes(rows, A.f.new_stride, kw), dkv = at_bytes(rows, A.dkv_stride, kw);
+        lse = 4ll * rows * G.n_heads;
     }
-    return w.worst;
+};
+struct AtBase {                              // element offsets a kernel put on its pointers before the body: at_var_base, or none
+    long long q = 0, out = 0, dout = 0, dq = 0, kv = 0, dkv = 0, lse = 0;
+    AtBase() {}
+    AtBase(const AtVarGeom& V, int seq) {
+        const PaGeom& G = V.a.f.g;
+        q = at_var_base(V, seq, G.q_stride), out = at_var_base(V, seq, G.out_stride), dout = at_var_base(V, seq, V.a.dout_stride);
+        dq = at_var_base(V, seq, V.a.dq_stride), kv = at_var_base(V, seq, V.a.f.new_stride);
+        dkv = at_var_base(V, seq, V.a.dkv_stride), lse = at_var_base(V, seq, G.n_heads);
+    }
+};
+
+// the forward blocks of one sequence.  q and out as prefill_attn_count_out_of_range; K, V rows at kv_stride; lse fp32 [rows][n_heads]
+void at_walk_fwd(const AtGeom& A, int seq, const AtBase& B, const AtSizes& S, AtWorst& w) {
+    const PaGeom& G = A.f.g;
+    const long long qb = 2 * (B.q + at_seq_base(A, seq, G.q_stride)), ob = 2 * (B.out + at_seq_base(A, seq, G.out_stride));
+    const long long kb = 2 * (B.kv + at_seq_base(A, seq, A.f.new_stride)), lb = 4 * (B.lse + at_seq_base(A, seq, G.n_heads));
+    const int per_seq = at_q_blocks_per_seq(A);
+    for (int block = 0; block < per_seq; ++block) {
+        const int qtile = pa_block_qtile(G, block), head = pa_block_head(G, block), kvh = pa_kv_head(G, head);
+        // pa_walk_q_out names the operand by its size within one sequence: q loads are 16 bytes, out stores 8
+        pa_walk_q_out(G, block, [&](long long b, int bytes, long long) {
+            if (bytes == 16) w(qb + b, bytes, S.q); else w(ob + b, bytes, S.out);
+        });
+        for (int row = qtile * PA_QT; row < qtile * PA_QT + PA_QT && row < G.t; ++row)
+            w(lb + 4 * pa_lse_off(G, row, head), 4, S.lse);
+        const int n_tiles = pa_key_tiles(G, qtile);
+        for (int tile = 0; tile < n_tiles; ++tile)
+            for (int c = 0; c < PA_CHUNKS; ++c)                // K and V share the offset
+                w(kb + 2 * pa8_new_off(A.f, pa8_new_row(G, tile * PA_KT + (c >> 4)), kvh, c & 15), 16, S.kv);
+    }
 }
 
-// The three backward launches, the same way, over q, k, v, out, dout, lse, delta, dq, dk, dv.
-long long attn_train_bwd_count_out_of_range(const AtGeom& A) {
+// the delta launch over all of A's rows
+void at_walk_delta(const AtGeom& A, const AtSizes& S, AtWorst& w) {
     const PaGeom& G = A.f.g;
-    const int hw = G.n_heads * PA_HD, kw = G.n_kv * PA_HD, rep = G.n_heads / G.n_kv;
-    const long long q_bytes = at_bytes(A, G.q_stride, hw), out_bytes = at_bytes(A, G.out_stride, hw);
-    const long long dout_bytes = at_bytes(A, A.dout_stride, hw), dq_bytes = at_bytes(A, A.dq_stride, hw);
-    const long long kv_bytes = at_bytes(A, A.f.new_stride, kw), dkv_bytes = at_bytes(A, A.dkv_stride, kw);
-    const long long lse_bytes = 4ll * A.n_seq * G.t * G.n_heads;
-    AtWorst w;
-    // delta
     for (long long block = 0; block < at_delta_blocks(A); ++block)
         for (int slot = 0; slot < AT_DELTA_PAIRS; ++slot) {
             const long long pair = at_delta_pair(A, block, slot), grow = pair / G.n_heads;
             const int head = (int)(pair % G.n_heads), seq = (int)(grow / G.t), row = (int)(grow % G.t);
             for (int ch = 0; ch < 16; ++ch) {
-                w(2 * at_out_off(A, seq, row, head, ch), 16, out_bytes);
-                w(2 * at_dout_off(A, seq, row, head, ch), 16, dout_bytes);
+                w(2 * at_out_off(A, seq, row, head, ch), 16, S.out);
+                w(2 * at_dout_off(A, seq, row, head, ch), 16, S.dout);
             }
-            w(4 * at_lse_off(A, seq, row, head), 4, lse_bytes);
+            w(4 * at_lse_off(A, seq, row, head), 4, S.lse);
         }
-    // dK / dV
-    for (long long block = 0; block < at_dkv_blocks(A); ++block) {
-        const int seq = at_dkv_seq(A, (int)block), kblock = at_dkv_kblock(A, (int)block), kvh = at_dkv_kvh(A, (int)block);
+}
+
+// the dK / dV blocks of one sequence
+void at_walk_dkv(const AtGeom& A, int seq, const AtBase& B, const AtSizes& S, AtWorst& w) {
+    const PaGeom& G = A.f.g;
+    const int rep = G.n_heads / G.n_kv;
+    for (int block = 0; block < at_dkv_blocks_per_seq(A); ++block) {
+        const int kblock = at_dkv_kblock(A, block), kvh = at_dkv_kvh(A, block);
         for (int kr = 0; kr < AT_KB; ++kr) {
             const int key = kblock * AT_KB + kr;
-            for (int ch = 0; ch < 16; ++ch) w(2 * at_kv_off(A, seq, at_row(A, key), kvh, ch), 16, kv_bytes);
+            for (int ch = 0; ch < 16; ++ch) w(2 * (B.kv + at_kv_off(A, seq, at_row(A, key), kvh, ch)), 16, S.kv);
             if (key < G.t)
-                for (int d = 0; d < PA_HD; d += 4) w(2 * at_dkv_off(A, seq, key, kvh, d), 8, dkv_bytes);
+                for (int d = 0; d < PA_HD; d += 4) w(2 * (B.dkv + at_dkv_off(A, seq, key, kvh, d)), 8, S.dkv);
         }
         const int tile0 = at_dkv_first_tile(kblock), n_tiles = at_dkv_end_tile(A) - tile0;
         for (int step = 0; step < rep * n_tiles; ++step) {
             const int head = kvh * rep + step / n_tiles, tile = tile0 + step % n_tiles;
             for (int c = 0; c < PA_CHUNKS; ++c) {
                 const int rr = at_row(A, tile * AT_QT + (c >> 4));
-                w(2 * at_q_off(A, seq, rr, head, c & 15), 16, q_bytes);
-                w(2 * at_dout_off(A, seq, rr, head, c & 15), 16, dout_bytes);
+                w(2 * (B.q + at_q_off(A, seq, rr, head, c & 15)), 16, S.q);
+                w(2 * (B.dout + at_dout_off(A, seq, rr, head, c & 15)), 16, S.dout);
             }
-            for (int lane = 0; lane < 64; ++lane) w(4 * at_lse_off(A, seq, at_row(A, tile * AT_QT + lane), head), 4, lse_bytes);
+            for (int lane = 0; lane < 64; ++lane)
+                w(4 * (B.lse + at_lse_off(A, seq, at_row(A, tile * AT_QT + lane), head)), 4, S.lse);
         }
     }
-    // dQ
+}
+
+// the dQ blocks of one sequence
+void at_walk_dq(const AtGeom& A, int seq, const AtBase& B, const AtSizes& S, AtWorst& w) {
+    const PaGeom& G = A.f.g;
     const int per_seq = at_q_blocks_per_seq(A);
-    for (int seq = 0; seq < A.n_seq; ++seq)
-        for (int block = 0; block < per_seq; ++block) {
-            const int qtile = pa_block_qtile(G, block), head = pa_block_head(G, block), kvh = pa_kv_head(G, head);
-            for (int wave = 0; wave < PA_WAVES; ++wave)
-                for (int r = 0; r < 32; ++r) {
-                    const int qpos = pa_q_row(G, qtile, wave, r), row = qtile * PA_QT + wave * 32 + r;
-                    for (int ch = 0; ch < 16; ++ch) {
-                        w(2 * at_q_off(A, seq, qpos, head, ch), 16, q_bytes);
-                        w(2 * at_dout_off(A, seq, qpos, head, ch), 16, dout_bytes);
-                    }
-                    w(4 * at_lse_off(A, seq, qpos, head), 4, lse_bytes);
-                    if (row < G.t)
-                        for (int d = 0; d < PA_HD; d += 4) w(2 * at_dq_off(A, seq, row, head, d), 8, dq_bytes);
+    for (int block = 0; block < per_seq; ++block) {
+        const int qtile = pa_block_qtile(G, block), head = pa_block_head(G, block), kvh = pa_kv_head(G, head);
+        for (int wave = 0; wave < PA_WAVES; ++wave)
+            for (int r = 0; r < 32; ++r) {
+                const int qpos = pa_q_row(G, qtile, wave, r), row = qtile * PA_QT + wave * 32 + r;
+                for (int ch = 0; ch < 16; ++ch) {
+                    w(2 * (B.q + at_q_off(A, seq, qpos, head, ch)), 16, S.q);
+                    w(2 * (B.dout + at_dout_off(A, seq, qpos, head, ch)), 16, S.dout);
                 }
-            const int n_tiles = pa_key_tiles(G, qtile);
-            for (int tile = 0; tile < n_tiles; ++tile)
-                for (int c = 0; c < PA_CHUNKS; ++c)
-                    w(2 * at_kv_off(A, seq, at_row(A, tile * PA_KT + (c >> 4)), kvh, c & 15), 16, kv_bytes);
-        }
+                w(4 * (B.lse + at_lse_off(A, seq, qpos, head)), 4, S.lse);
+                if (row < G.t)
+                    for (int d = 0; d < PA_HD; d += 4) w(2 * (B.dq + at_dq_off(A, seq, row, head, d)), 8, S.dq);
+            }
+        const int n_tiles = pa_key_tiles(G, qtile);
+        for (int tile = 0; tile < n_tiles; ++tile)
+            for (int c = 0; c < PA_CHUNKS; ++c)
+                w(2 * (B.kv + at_kv_off(A, seq, at_row(A, tile * PA_KT + (c >> 4)), kvh, c & 15)), 16, S.kv);
+    }
+}
+}  // namespace
+
+// The forward: the largest number of bytes by which an address passes the end of its operand or runs in front of it, 0 when
+// none does.
+long long attn_train_fwd_count_out_of_range(const AtGeom& A) {
+    const AtSizes S(A, (long long)A.n_seq * A.f.g.t);
+    AtWorst w;
+    for (int seq = 0; seq < A.n_seq; ++seq) at_walk_fwd(A, seq, AtBase(), S, w);
+    return w.worst;
+}
+
+// The three backward launches, the same way, over q, k, v, out, dout, lse, delta, dq, dk, dv.
+long long attn_train_bwd_count_out_of_range(const AtGeom& A) {
+    const AtSizes S(A, (long long)A.n_seq * A.f.g.t);
+    AtWorst w;
+    at_walk_delta(A, S, w);
+    for (int seq = 0; seq < A.n_seq; ++seq) {
+        at_walk_dkv(A, seq, AtBase(), S, w);
+        at_walk_dq(A, seq, AtBase(), S, w);
+    }
+    return w.worst;
+}
+
+// The variable-length launches: every block of the grid that does not return at once, as its kernel composes it -- the
+// sequence's own geometry, the prefix's base on every pointer, the walkers above at seq = 0 -- against operands of cu[n_seq] rows.
+long long attn_train_varlen_fwd_count_out_of_range(const AtVarGeom& V) {
+    const AtSizes S(V.a, at_var_rows(V));
+    AtWorst w;
+    for (int seq = 0; seq < V.a.n_seq; ++seq) at_walk_fwd(at_var_seq(V, seq), 0, AtBase(V, seq), S, w);
+    return w.worst;
+}
+
+long long attn_train_varlen_bwd_count_out_of_range(const AtVarGeom& V) {
+    const AtSizes S(V.a, at_var_rows(V));
+    AtWorst w;
+    at_walk_delta(at_var_all(V), S, w);
+    for (int seq = 0; seq < V.a.n_seq; ++seq) {
+        at_walk_dkv(at_var_seq(V, seq), 0, AtBase(V, seq), S, w);
+        at_walk_dq(at_var_seq(V, seq), 0, AtBase(V, seq), S, w);
+    }
     return w.worst;
 }
 

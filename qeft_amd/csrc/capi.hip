@@ -1175,6 +1175,103 @@ long long qeft_attn_train_bwd_check_extents(int q_stride, int kv_stride, int out
     return qeft::attn_train_bwd_count_out_of_range(A);
 }
 
+// ---- training attention over packed sequences (attn_train.hip, the varlen launches).  seq_rows is a HOST array, the n_seq + 1
+// prefix of the lengths; it is copied into the launch's arguments here, so what is validated is what the kernels read.
+// Order: the scalars (QEFT_ERR_SHAPE), seq_rows itself (QEFT_ERR_NULL), its contents (QEFT_ERR_SHAPE); the entries go on with
+// the workspace size, then NULL, then alignment of the device operands.
+static int attn_train_varlen_geom(qeft::AtVarGeom& V, int q_stride, int kv_stride, int out_stride, int dout_stride, int dq_stride,
+                                  int dkv_stride, const int* seq_rows, int n_seq, int n_heads, int n_kv_heads) {
+    if (n_seq < 1 || n_seq > qeft::AT_MAX_SEQ) return QEFT_ERR_SHAPE;
+    V = qeft::AtVarGeom{};
+    if (int e = attn_train_bwd_geom(V.a, q_stride, kv_stride, out_stride, dout_stride, dq_stride, dkv_stride, 1, 1, n_heads, n_kv_heads))
+        return e;
+    if (!seq_rows) return QEFT_ERR_NULL;
+    if (seq_rows[0] != 0) return QEFT_ERR_SHAPE;
+    int longest = 0;
+    for (int i = 0; i < n_seq; ++i) {
+        if (seq_rows[i + 1] <= seq_rows[i] || seq_rows[i + 1] > (1 << 20)) return QEFT_ERR_SHAPE;       // len >= 1, R <= 2^20
+        if (seq_rows[i + 1] - seq_rows[i] > longest) longest = seq_rows[i + 1] - seq_rows[i];
+    }
+    for (int i = 0; i <= n_seq; ++i) V.cu[i] = seq_rows[i];
+    V.a.f.g.t = V.a.f.g.kv_rows = longest;
+    V.a.n_seq = n_seq;
+    return QEFT_OK;
+}
+
+static int attn_train_varlen_fwd_geom(qeft::AtVarGeom& V, int q_stride, int kv_stride, int out_stride, const int* seq_rows, int n_seq,
+                                      int n_heads, int n_kv_heads) {
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads > 4096) return QEFT_ERR_SHAPE;     // before they size the gradients' default strides
+    return attn_train_varlen_geom(V, q_stride, kv_stride, out_stride, n_heads * 128, n_heads * 128, n_kv_heads * 128, seq_rows, n_seq,
+                                  n_heads, n_kv_heads);
+}
+
+int qeft_attn_train_varlen_fwd(const void* q, int q_stride, const void* k, const void* v, int kv_stride, void* out, int out_stride,
+                               float* lse, const int* seq_rows, int n_seq, int n_heads, int n_kv_heads, qeft_stream_t stream) {
+    qeft::AtVarGeom V;
+    if (int e = attn_train_varlen_fwd_geom(V, q_stride, kv_stride, out_stride, seq_rows, n_seq, n_heads, n_kv_heads)) return e;
+    if (!q || !k || !v || !out || !lse) return QEFT_ERR_NULL;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || ((uintptr_t)lse & 3)) return QEFT_ERR_ALIGN;
+    return finish(qeft::attn_train_varlen_fwd_launch(q, k, v, out, lse, V, (hipStream_t)stream));
+}
+
+long long qeft_attn_train_varlen_check_extents(int q_stride, int kv_stride, int out_stride, const int* seq_rows, int n_seq, int n_heads,
+                                               int n_kv_heads) {
+    qeft::AtVarGeom V;
+    if (attn_train_varlen_fwd_geom(V, q_stride, kv_stride, out_stride, seq_rows, n_seq, n_heads, n_kv_heads) != QEFT_OK) return -1;
+    return qeft::attn_train_varlen_fwd_count_out_of_range(V);
+}
+
+long long qeft_attn_train_varlen_bwd_workspace_bytes(const int* seq_rows, int n_seq, int n_heads, int n_kv_heads) {
+    qeft::AtVarGeom V;
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads > 4096) return 0;
+    if (attn_train_varlen_fwd_geom(V, n_heads * 128, n_kv_heads * 128, n_heads * 128, seq_rows, n_seq, n_heads, n_kv_heads) != QEFT_OK)
+        return 0;
+    return 4ll * qeft::at_var_rows(V) * n_heads;                       // delta, fp32 [R][n_heads]
+}
+
+static int attn_train_varlen_bwd_entry(const void* q, int q_stride, const void* k, const void* v, int kv_stride, const void* out,
+                                       int out_stride, const void* dout, int dout_stride, const float* lse, void* dq, int dq_stride,
+                                       void* dk, void* dv, int dkv_stride, void* workspace, long long workspace_bytes,
+                                       const int* seq_rows, int n_seq, int n_heads, int n_kv_heads, int parts, qeft_stream_t stream) {
+    qeft::AtVarGeom V;
+    if (int e = attn_train_varlen_geom(V, q_stride, kv_stride, out_stride, dout_stride, dq_stride, dkv_stride, seq_rows, n_seq, n_heads,
+                                       n_kv_heads))
+        return e;
+    if (workspace_bytes < 4ll * qeft::at_var_rows(V) * n_heads) return QEFT_ERR_SHAPE;
+    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !workspace) return QEFT_ERR_NULL;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(dout) || !aligned16(dq) || !aligned16(dk) ||
+        !aligned16(dv) || !aligned16(workspace) || ((uintptr_t)lse & 3))
+        return QEFT_ERR_ALIGN;
+    return finish(qeft::attn_train_varlen_bwd_launch(q, k, v, out, dout, lse, dq, dk, dv, (float*)workspace, V, parts,
+                                                     (hipStream_t)stream));
+}
+
+int qeft_attn_train_varlen_bwd(const void* q, int q_stride, const void* k, const void* v, int kv_stride, const void* out, int out_stride,
+                               const void* dout, int dout_stride, const float* lse, void* dq, int dq_stride, void* dk, void* dv,
+                               int dkv_stride, void* workspace, long long workspace_bytes, const int* seq_rows, int n_seq, int n_heads,
+                               int n_kv_heads, qeft_stream_t stream) {
+    return attn_train_varlen_bwd_entry(q, q_stride, k, v, kv_stride, out, out_stride, dout, dout_stride, lse, dq, dq_stride, dk, dv,
+                                       dkv_stride, workspace, workspace_bytes, seq_rows, n_seq, n_heads, n_kv_heads, 7, stream);
+}
+
+int qeft_attn_train_varlen_bwd_part(const void* q, int q_stride, const void* k, const void* v, int kv_stride, const void* out,
+                                    int out_stride, const void* dout, int dout_stride, const float* lse, void* dq, int dq_stride,
+                                    void* dk, void* dv, int dkv_stride, void* workspace, long long workspace_bytes, const int* seq_rows,
+                                    int n_seq, int n_heads, int n_kv_heads, int part, qeft_stream_t stream) {
+    if (part < 0 || part > 2) return QEFT_ERR_SHAPE;
+    return attn_train_varlen_bwd_entry(q, q_stride, k, v, kv_stride, out, out_stride, dout, dout_stride, lse, dq, dq_stride, dk, dv,
+                                       dkv_stride, workspace, workspace_bytes, seq_rows, n_seq, n_heads, n_kv_heads, 1 << part, stream);
+}
+
+long long qeft_attn_train_varlen_bwd_check_extents(int q_stride, int kv_stride, int out_stride, int dout_stride, int dq_stride,
+                                                   int dkv_stride, const int* seq_rows, int n_seq, int n_heads, int n_kv_heads) {
+    qeft::AtVarGeom V;
+    if (attn_train_varlen_geom(V, q_stride, kv_stride, out_stride, dout_stride, dq_stride, dkv_stride, seq_rows, n_seq, n_heads,
+                               n_kv_heads) != QEFT_OK)
+        return -1;
+    return qeft::attn_train_varlen_bwd_count_out_of_range(V);
+}
+
 // ---- training glue (train_glue.hip)
 static bool tg_stride_ok(int stride, int width) { return stride % 8 == 0 && stride >= width && stride <= (1 << 24); }
 

@@ -659,6 +659,49 @@ int qeft_rope_qk(const void* q, const void* k, const void* cos_tab, const void* 
                  int n_heads, int n_kv_heads, int q_stride, int k_stride, int inverse, qeft_stream_t stream);
 long long qeft_rope_qk_check_extents(int rows, int t_len, int n_heads, int n_kv_heads, int q_stride, int k_stride);
 
+/* The update of the training step (csrc/oweight_optim.hip, csrc/oweight_optim.h; qeft_amd/optim.py: OWeightAdamW;
+ * finetune.train_step): loss-scale removal, overflow detection, global-norm clipping and AdamW in two
+ * launches over ONE flat fp32 arena.  p, g, m, v: fp32 [n], the parameters, their (loss-scaled) gradients and the two moments;
+ * n % 64 == 0, 0 < n <= 2^31 - 2^20.  No atomics, no host synchronisation, nothing read back, capturable.
+ * The state is a 32-byte record in device memory, 16-byte aligned, 8 words in this order:
+ *   float scale; int step; int good_steps; int skipped_last; int n_skipped; float grad_norm; float clip_coef; int reserved
+ * (step counts applied updates only).  A step reads state_in and writes state_out, which must be another record: every block
+ * reads the one, block 0 writes the other, and the caller swaps them afterwards.
+ * Geometry: 256 threads, 16-byte accesses, U = 2 chunks per thread per iteration, min(ceil(n / 4 / (256 U)), 2048) blocks at a
+ * fixed grid stride; which thread takes which element depends on n alone, so the results do not depend on the device.
+ * qeft_oweight_grad_stats: x = g * (1 / scale) (one rounding), each thread adds x * x in fp32 in program order, the block folds its
+ *   256 sums through a fixed tree and stores ONE fp32 partial: partials fp32 [qeft_oweight_optim_blocks(n)].  An inf or NaN
+ *   gradient makes its partial non-finite; that is the overflow signal.
+ * qeft_oweight_adamw: every block adds all partials in double in index order (the same bits in every block) and takes
+ *   norm = sqrt(sum).  A non-finite sum skips the step: no element of p, m, v is touched; state_out = state_in with
+ *   skipped_last = 1, n_skipped + 1, good_steps = 0 and, when dynamic, scale * backoff_factor.  Otherwise
+ *   coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1 (torch's clip_grad_norm_; 0 turns clipping off), t = step + 1,
+ *   bc1 = 1 - beta1^t, bc2 = 1 - beta2^t (double), and per element, in fp32 with one rounding per operation and no FMA:
+ *     gh = g * (1 / scale) * coef;   p1 = p * (1 - lr * weight_decay);   m' = m + (gh - m) * (1 - beta1);
+ *     v' = beta2 * v + (1 - beta2) * (gh * gh);   p' = p1 - float(lr / bc1) * (m' / (sqrt(v') / float(sqrt(bc2)) + eps))
+ *   (csrc/oweight_optim.h states the order of every operation).  g is left as it is.  state_out: step = t, good_steps + 1,
+ *   skipped_last = 0, grad_norm = norm, clip_coef = coef; when dynamic and good_steps reaches growth_interval, scale *
+ *   growth_factor and good_steps = 0.  An element whose p, g, m, v are all zero stays zero, so zero padding stays zero.
+ * Both refuse, before any HIP call and in this order: QEFT_ERR_SHAPE (n <= 0, n % 64 != 0, n above the ceiling; for the update
+ *   also a beta outside [0, 1), eps <= 0, a scale factor <= 0, a negative lr, weight_decay or max_norm, growth_interval < 1, dynamic
+ *   other than 0 or 1), then QEFT_ERR_NULL (every pointer is required; state_out == state_in counts as a missing record), then
+ *   QEFT_ERR_ALIGN (16 bytes).
+ * qeft_oweight_optim_blocks: CPU-only, the grid of both launches and the length of partials (0 for a refused n).
+ * qeft_oweight_optim_thread_elems: CPU-only, the most elements one thread adds into its sum (0 for a refused n).
+ * qeft_oweight_optim_check_extents: CPU-only -- walks every address both launches form and returns how many fall outside
+ *   [0, n), plus the number of 16-byte chunks of the arena not visited exactly once; 0 when all is well, -1 for a refused n.
+ * qeft_oweight_optim_lab: for measurement (tools/bench_oweight_optim.py): u = 1, 2 or 4 chunks per thread per iteration (0: the
+ *   built-in choice), nontemporal_g = 1: launch 2 loads g, its last use, non-temporally.  Process-wide; the three functions
+ *   above follow it.  The results' bits depend on u (the order of a thread's sum), not on nontemporal_g. */
+int qeft_oweight_optim_lab(int u, int nontemporal_g);
+int qeft_oweight_optim_blocks(long long n);
+long long qeft_oweight_optim_thread_elems(long long n);
+long long qeft_oweight_optim_check_extents(long long n);
+int qeft_oweight_grad_stats(const void* g, long long n, const void* state_in, void* partials, qeft_stream_t stream);
+int qeft_oweight_adamw(void* p, const void* g, void* m, void* v, long long n, const void* state_in, void* state_out,
+                       const void* partials, float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                       float growth_factor, float backoff_factor, int growth_interval, int dynamic, qeft_stream_t stream);
+
 /* Fused lm_head + cross-entropy pieces (csrc/lm_head_nll.hip; qeft_amd/scoring.py: lm_head_nll, score, eval_nll; DESIGN.md
  * section 4.13).  x: fp16 [t][hidden], the final-norm output rows, x_stride elements apart; weight: fp16 [vocab][hidden]
  * contiguous, the checkpoint's lm_head.weight; targets: int32 [t], or NULL.  logit_ij = sum_k x_ik w_jk is accumulated in fp32 by

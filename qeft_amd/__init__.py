@@ -4,10 +4,11 @@ The scoring and fine-tuning entry points are exported here; they resolve on firs
 `qeft_amd.build`, which runs before the library exists) stays free of torch and of the HIP library.
 """
 _SCORING = ("score", "eval_nll", "lm_head_nll", "lm_head_nll_loss")
-_FINETUNE = ("causal_lm_loss", "shift_labels", "pack_sequences")       # qeft_amd.finetune also has begin(model) / end(model)
+_FINETUNE = ("causal_lm_loss", "shift_labels", "pack_sequences", "train_step", "warmup_constant_lr")     # qeft_amd.finetune also has begin(model) / end(model)
 _ATTENTION = ("causal_attention", "causal_attention_packed")
 _GLUE = ("add_rmsnorm", "swiglu", "rope_qk")
-__all__ = [*_SCORING, *_FINETUNE, *_ATTENTION, *_GLUE]
+_OPTIM = ("OWeightAdamW",)
+__all__ = [*_SCORING, *_FINETUNE, *_ATTENTION, *_GLUE, *_OPTIM]
 
 
 def __getattr__(name):
@@ -23,4 +24,7 @@ def __getattr__(name):
     if name in _GLUE:
         from . import glue
         return getattr(glue, name)
+    if name in _OPTIM:
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

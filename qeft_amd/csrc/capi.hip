@@ -15,6 +15,7 @@
 #include "prefill_attn.h"
 #include "attn_train.h"
 #include "train_glue.h"
+#include "oweight_optim.h"
 
 static thread_local int g_last_hip_error = 0;
 thread_local const char* qeft::g_last_variant = "";
@@ -1373,6 +1374,65 @@ long long qeft_train_glue_check_extents(int op, int rows, int width, int stride0
         }
         default: return -1;
     }
+}
+
+// ---- training update (oweight_optim.hip)
+// qeft_oweight_optim_lab: the measurement override of the geometry (chunks per thread per iteration, non-temporal loads of g)
+static int g_oo_u = 0, g_oo_nt = 0;
+
+static int oo_geom(qeft::OoGeom& G, long long n) {
+    if (n <= 0 || n % 64 != 0 || n > qeft::OO_MAX_N) return QEFT_ERR_SHAPE;
+    G = qeft::OoGeom{n, g_oo_u ? g_oo_u : qeft::OO_U};
+    return QEFT_OK;
+}
+
+int qeft_oweight_optim_lab(int u, int nontemporal_g) {
+    if ((u != 0 && u != 1 && u != 2 && u != 4) || (nontemporal_g != 0 && nontemporal_g != 1)) return QEFT_ERR_SHAPE;
+    g_oo_u = u;
+    g_oo_nt = nontemporal_g;
+    return QEFT_OK;
+}
+
+int qeft_oweight_optim_blocks(long long n) {
+    qeft::OoGeom G{};
+    return oo_geom(G, n) == QEFT_OK ? qeft::oo_blocks(G) : 0;
+}
+
+long long qeft_oweight_optim_thread_elems(long long n) {
+    qeft::OoGeom G{};
+    return oo_geom(G, n) == QEFT_OK ? qeft::oo_thread_elems(G) : 0;
+}
+
+long long qeft_oweight_optim_check_extents(long long n) {
+    qeft::OoGeom G{};
+    if (oo_geom(G, n) != QEFT_OK) return -1;
+    return qeft::oweight_optim_count_out_of_range(G);
+}
+
+int qeft_oweight_grad_stats(const void* g, long long n, const void* state_in, void* partials, qeft_stream_t stream) {
+    qeft::OoGeom G{};
+    if (int e = oo_geom(G, n)) return e;
+    if (!g || !state_in || !partials) return QEFT_ERR_NULL;
+    if (!aligned16(g) || !aligned16(state_in) || !aligned16(partials)) return QEFT_ERR_ALIGN;
+    return finish(qeft::oweight_grad_stats_launch(g, G, state_in, partials, (hipStream_t)stream));
+}
+
+int qeft_oweight_adamw(void* p, const void* g, void* m, void* v, long long n, const void* state_in, void* state_out,
+                       const void* partials, float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                       float growth_factor, float backoff_factor, int growth_interval, int dynamic, qeft_stream_t stream) {
+    qeft::OoGeom G{};
+    if (int e = oo_geom(G, n)) return e;
+    // written so that a NaN fails every one of them
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f) || !(growth_factor > 0.f) ||
+        !(backoff_factor > 0.f) || !(lr >= 0.f) || !(weight_decay >= 0.f) || !(max_norm >= 0.f) || growth_interval < 1 ||
+        (dynamic != 0 && dynamic != 1))
+        return QEFT_ERR_SHAPE;
+    if (!p || !g || !m || !v || !state_in || !state_out || !partials || state_in == state_out) return QEFT_ERR_NULL;   // two records
+    if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || !aligned16(state_in) || !aligned16(state_out) ||
+        !aligned16(partials))
+        return QEFT_ERR_ALIGN;
+    const qeft::OoHyper H{lr, beta1, beta2, eps, weight_decay, max_norm, growth_factor, backoff_factor, growth_interval, dynamic};
+    return finish(qeft::oweight_adamw_launch(p, g, m, v, G, state_in, state_out, partials, H, g_oo_nt != 0, (hipStream_t)stream));
 }
 
 // ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)

@@ -7,20 +7,25 @@ The reference's finetune.py freezes every parameter except `*oweight*` and train
     params = begin(model)                       every QuantLinear in training mode; the fp32 oweight parameters
     loss = causal_lm_loss(model, tokens, labels)
     loss.backward()                             dX / d(oweight) kernels per linear, qeft_lm_head_nll_grad at the head
-    ... an optimiser of the caller's over params ...
+    opt.step()                                  optim.OWeightAdamW(params): unscale, overflow check, global-norm clip, AdamW
     end(model)                                  back to inference: prefill, score and a new DecodeEngine see the trained weights
 
 causal_lm_loss is a differentiable pass of its own (llama._prefill_pass, the inference route, is not touched): the linears and
 the head run the project's kernels; norms, rotary, the activation and the residual adds are torch ops unless glue="fused" asks
 for the project's row kernels and their backward kernels (qeft_amd.glue) and rope="fused" for the
 project's rotary of q and k (glue.rope_qk), and so is attention unless attn="own" asks for the
-project's own (attention.causal_attention, DESIGN.md section 4.15).  The activations are fp16, so a caller scales the loss against underflow themselves -- `(loss * s).backward()`, then divide the fp32 gradients by s; the head's
-backward takes the scale in fp32 and keeps its softmax - onehot unscaled, so no scale makes it overflow or underflow there.
+project's own (attention.causal_attention).  The activations are fp16, so the loss is scaled against underflow -- opt.scale_loss(loss).backward(), the scale a device scalar
+of the optimiser's that its update divides out again (or by hand: `(loss * s).backward()`, then divide the fp32 gradients by s);
+the head's backward takes the scale in fp32 and keeps its softmax - onehot unscaled, so no scale makes it overflow or underflow there.
 Sequences of unequal length go in as ONE packed row stream: pack_sequences(seqs) makes (tokens [R], labels, seq_lens) packs and
 causal_lm_loss(model, tokens, labels, seq_lens=seq_lens) runs them -- the row-wise kernels over the R rows as they lie, the rotary
 restarting per sequence, attention.causal_attention_packed keeping every sequence to itself.
-The optimiser loop and Trainer plumbing are out of scope.
+train_step(model, opt, batches) is one whole update over a list of packed micro-batches: zero_grad, one scaled backward per
+micro-batch, opt.step() (qeft_amd.optim.OWeightAdamW, DESIGN.md section 4.19: two launches, no host synchronisation);
+warmup_constant_lr is the reference's schedule.  Trainer plumbing and datasets are out of scope.
 """
+import math
+
 import torch
 from torch.utils.checkpoint import checkpoint as _checkpoint
 
@@ -205,7 +210,7 @@ def causal_lm_loss(model, tokens, labels=None, *, seq_lens=None, checkpoint=True
     follows it.  rope="torch": the rotary of q and k is finetune._rope, twice per layer, on either glue; rope="fused":
     one glue.rope_qk launch per layer and one for its backward, the same bits in both directions, with
     either glue and either attn.
-    fp16 activations: scale the loss yourself, `(loss * s).backward()`."""
+    fp16 activations: scale the loss, opt.scale_loss(loss).backward() (optim.OWeightAdamW) or `(loss * s).backward()` by hand."""
     if head not in ("fused", "torch"):
         raise ValueError(f"head must be 'fused' or 'torch', got {head!r}")
     if attn not in ("sdpa", "own"):
@@ -258,3 +263,32 @@ def causal_lm_loss(model, tokens, labels=None, *, seq_lens=None, checkpoint=True
     logits = torch.matmul(hn, W.t()).float()
     lab = torch.where(ok, targets, torch.full_like(targets, IGNORE_INDEX)).long()
     return torch.nn.functional.cross_entropy(logits, lab, ignore_index=IGNORE_INDEX, reduction="sum") / n
+
+
+def warmup_constant_lr(i, total, base, warmup_ratio=0.03):
+    """The reference's schedule (a constant learning rate behind a linear warm-up over warmup_ratio of the run) as a pure function:
+    the rate of update i (0-based) of `total`.  The warm-up lasts ceil(total * warmup_ratio) updates and update i of it runs at
+    base * i / that count -- the first at 0, as the scheduler the reference's Trainer builds does; from there on `base`."""
+    if total < 1 or i < 0:
+        raise ValueError(f"update {i} of {total}")
+    warmup = math.ceil(total * warmup_ratio)
+    return base * i / max(1.0, warmup) if i < warmup else base
+
+
+def train_step(model, opt, batches, **loss_kwargs):
+    """One update of the oweight parameters: opt.zero_grad(); for every (tokens, labels, seq_lens) of `batches` (what
+    pack_sequences returns; labels and seq_lens may be None) the backward of opt.scale_loss(causal_lm_loss(...), accum=len(batches));
+    opt.step().  loss_kwargs go to causal_lm_loss (attn, glue, rope, head, checkpoint).  Returns the unscaled mean of the
+    micro-batch losses as a device scalar; nothing here synchronises the host.  A step whose gradient overflowed is skipped by the
+    optimiser (opt.stats() tells), the returned loss is that of the forward passes either way."""
+    batches = list(batches)
+    if not batches:
+        raise ValueError("train_step needs at least one micro-batch")
+    opt.zero_grad()
+    total = None
+    for tokens, labels, seq_lens in batches:
+        loss = causal_lm_loss(model, tokens, labels, seq_lens=seq_lens, **loss_kwargs)
+        opt.scale_loss(loss, accum=len(batches)).backward()
+        total = loss.detach() if total is None else total + loss.detach()
+    opt.step()
+    return total / len(batches)

@@ -309,6 +309,15 @@ long long qeft_gemv_v3_check_extents_ckpt(int n, int k, int group_size, int n_ou
 #define QEFT_V3_F_GATHER (1u << 31) /* reorder_ids gathered inside the launch */
 int qeft_gemv_v3_plan(int n, int k, int group_size, int n_out, int m, int mode, int bits, int flags, int* out);
 int qeft_gemv_v3_last_plan(int* out);
+/* Compile-time K.  The instances that the decode engine's Llama-2-7B / -13B launches run (q|k|v, o_proj, gate|up at K = 4096 /
+ * 5120, down at K = 11008 / 13824; flag-free half, one row, 4 bits, outlier step) are built a second time with K as a template
+ * argument: same loads, same arithmetic, same bits, a shorter scalar prologue.  The 13 integers above and
+ * qeft_last_variant are the same for both; these two entries say which one a launch takes.
+ * qeft_gemv_v3_plan_kct: the K compiled into the instance the plan names, 0 for the run-time-K instance, -1 where
+ *   qeft_gemv_v3_plan refuses.  QEFT_GEMV_CTK=0 in the process's environment sends every launch to the run-time-K instance.
+ * qeft_gemv_v3_last_kct: the same of the calling thread's last v3 launch (0 before the first). */
+int qeft_gemv_v3_plan_kct(int n, int k, int group_size, int n_out, int m, int mode, int bits, int flags);
+int qeft_gemv_v3_last_kct(void);
 
 /* Producer-form helpers for the same scheme.
  * qeft_token_begin_norm: qeft_token_begin + h32 = float(embed[*tok]), h_norm = fp16(embed[*tok] * gamma),

@@ -792,6 +792,16 @@ int qeft_gemv_v3_last_plan(int* out) {
     return QEFT_OK;
 }
 
+int qeft_gemv_v3_plan_kct(int n, int k, int group_size, int n_out, int m, int mode, int bits, int flags) {
+    int out[QEFT_GEMV_V3_PLAN_INTS];
+    if (qeft_gemv_v3_plan(n, k, group_size, n_out, m, mode, bits, flags, out) != QEFT_OK) return -1;
+    qeft::V3Geom G{};
+    v3_geom(G, n, k, group_size, n_out, mode);
+    return qeft::gemv_v3_plan(G, m, mode, bits, (uint32_t)flags).kct;
+}
+
+int qeft_gemv_v3_last_kct(void) { return qeft::gemv_v3_last_plan().kct; }
+
 int qeft_token_begin_norm_blocks(int hidden) { return hidden >= 8 ? qeft::token_begin_norm_blocks(hidden) : 0; }
 
 int qeft_token_begin_norm(const void* embed, const void* tok, const void* rope_tab, const int* pos, void* h, void* rope_row,

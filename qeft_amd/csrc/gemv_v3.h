@@ -151,8 +151,8 @@ __host__ __device__ constexpr size_t v3_red_bytes(int rs_cap, int m = 1, int nw 
 struct V3Lds {              // byte offsets of the regions inside the block's dynamic LDS
     uint32_t xs, szl, owl, epl, ssql, red, xf, xg, szraw, idsl, xraw, total;
 };
-__host__ __device__ inline V3Lds v3_lds(int K, int ngroups, int n_out, int rs_cap, int m, int nw, bool xn, bool szn, bool gather, bool xg = false) {
-    V3Lds L;
+__host__ __device__ constexpr V3Lds v3_lds(int K, int ngroups, int n_out, int rs_cap, int m, int nw, bool xn, bool szn, bool gather, bool xg = false) {
+    V3Lds L{};
     uint32_t o = 0;
     L.xs = o;   o += xg ? 0u : ((uint32_t)m * v3_x_stride(K, m) + 1023u) / 1024u * 1024u;   // [m][K] fp16 as the MFMAs read it (xg: x stays in global memory)
     L.szl = o;  o += (uint32_t)rs_cap * v3_sz_bytes(ngroups);                               // [rs_cap][groups][16] u32
@@ -168,7 +168,7 @@ __host__ __device__ inline V3Lds v3_lds(int K, int ngroups, int n_out, int rs_ca
     L.total = o;
     return L;
 }
-__host__ __device__ inline size_t v3_smem_bytes(int K, int ngroups, int n_out, int rs_cap, bool xn = false, int m = 1, int nw = V3_NW_MAX,
+__host__ __device__ constexpr size_t v3_smem_bytes(int K, int ngroups, int n_out, int rs_cap, bool xn = false, int m = 1, int nw = V3_NW_MAX,
                                                 bool szn = false, bool gather = false) {
     return v3_lds(K, ngroups, n_out, rs_cap, m, nw, xn, szn, gather).total;
 }
@@ -231,8 +231,9 @@ __host__ __device__ inline void v3_block_sets(int b, int q, int r, int& set0, in
 }
 // Blocks are dealt round-robin over the 8 XCDs (b and b + 8 share an L2); neighbouring sets share scale / outlier lines.
 __host__ __device__ inline int v3_xcd_block(int bid, int nblk) {
+    // the first r XCDs hold q + 1 blocks, the others q: XCD x starts at x q + min(x, r) (no branch: every block runs this)
     const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    return xcd * q + (xcd < r ? xcd : r) + (bid >> 3);
 }
 
 #if defined(__HIPCC__)
@@ -245,6 +246,14 @@ __device__ __forceinline__ void v3_dma16(const void* gsrc, uint32_t lds_dst) {
     uint32_t keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+// The same piece for the compile-time-K instances (KCT != 0): M0 is written once and left behind.  Nothing else in those
+// kernels reads M0 -- the compiler writes it itself in front of any use of its own, and every DMA statement sets it in
+// the statement that reads it -- so the save / restore pair of v3_dma16 bought nothing.  lds_dst must be a value the compiler
+// can prove wave-uniform (no readfirstlane here: on a constant it left a dead compare / select pair per piece); the s_nop
+// is the one wait state between an SALU write of M0 and the LDS-DMA that reads it.
+__device__ __forceinline__ void v3_dma16_lean(const void* gsrc, uint32_t lds_dst) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
 // Lab hooks (tools/gemv_v3_lab.hip defines them before including this file; the product compiles them away): in-kernel time
@@ -278,6 +287,20 @@ template <int I, int N, typename F> __device__ __forceinline__ void v3_static_fo
         v3_static_for<I + 1, N>(f);
     }
 }
+// The staging loop of one region: f(p) for the pieces p = first, first + STRIDE, .. below count (0 <= first < STRIDE).
+// COUNT >= 0: count is the compile-time constant COUNT and the loop is straight-line code -- ceil(COUNT / STRIDE) calls, a
+// compare only in front of the last one and only where a wave can be past the end; COUNT < 0: the run-time loop.
+template <int COUNT, int STRIDE, typename F> __device__ __forceinline__ void v3_for_pieces(int first, int count, F&& f) {
+    if constexpr (COUNT < 0) {
+        for (int p = first; p < count; p += STRIDE) f(p);
+    } else {
+        v3_static_for<0, (COUNT + STRIDE - 1) / STRIDE>([&](auto t) {
+            constexpr int T = decltype(t)::value;
+            const int p = first + T * STRIDE;
+            if ((T + 1) * STRIDE <= COUNT || p < COUNT) f(p);
+        });
+    }
+}
 __host__ __device__ constexpr int v3_gcd(int a, int b) { return b == 0 ? a : v3_gcd(b, a % b); }
 // steps per unrolled round: even (the x fragments alternate between two register sets) and a whole number of ring turns
 __host__ __device__ constexpr int v3_unroll_steps(int D, int RSC) {
@@ -295,7 +318,12 @@ __host__ __device__ constexpr int v3_unroll_steps(int D, int RSC) {
 //      stream their last set twice and drop the copy's results.
 // FL: the run-time flags (V3_F_*: per-channel scales, consumer-side norm, checkpoint-layout operands, gather) are honoured; false
 //     for the plain launches of the decode engine, which then carry no trace of those paths.
-template <int NW, int D, bool OUTL, int MODE, int BITS = 4, int MB = 1, int RSC = 1, bool FL = true, bool XG = false>
+// KCT: 0, or the launch's K as a COMPILE-TIME constant (the decode engine launches each kind with one K for the life of the
+//     model; gemv_v3_plan names the (instance, K) pairs that are built): the LDS carve-up, piece counts, set and step strides
+//     are then literals, the staging loops straight-line code and the DMA pieces of the lean form (v3_dma16_lean) -- the
+//     scalar chain between block entry and the first ring load is what such a launch pays per block.  The
+//     kernel's K_ argument is then ignored.  Loads, MFMAs, fold and epilogue are the run-time path's: the results are its bits.
+template <int NW, int D, bool OUTL, int MODE, int BITS = 4, int MB = 1, int RSC = 1, bool FL = true, bool XG = false, int KCT = 0>
 __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const uint8_t* qw, const f16* x_in, const uint8_t* szp, const uint8_t* ow,
                                                           const f16* xn_gamma, int K_, uint32_t nblk_rscap_flags, uint32_t setsq_setsr,
                                                           V3Tail a) {
@@ -304,6 +332,8 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
     static_assert(RSC >= 1 && RSC <= V3_MAX_RS && D >= 2, "row sets per block 1..4, at least two loads in flight per wave");
     // (MB == 2 && !FL: the decode engine's m-row launches with its fused epilogues, gemv_v3_multi.hip)
     static_assert(!XG || (MB == 2 && D >= 4), "x fragments from global memory: batch-row launches with a deep ring");
+    static_assert(KCT == 0 || (!FL && MB == 1 && BITS == 4 && !XG && KCT % 128 == 0 && KCT >= 256), "compile-time K: the engine's plain one-row 4-bit launches");
+    constexpr bool CT = KCT != 0;
     typedef typename V3Val<MB>::type val_t;
     // the leading parameters arrive in SGPRs (kernarg preload); the tail is one batch of scalar loads issued here and waited
     // for once, behind the ring issue (the pin below) -- argument loads that hipcc leaves next to their first use each cost a
@@ -317,7 +347,8 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
     const int nblk = (int)(nblk_rscap_flags & 0xffffu);
     const int sets_q = (int)(setsq_setsr & 0xffffu), sets_r = (int)(setsq_setsr >> 16);
     // (nsets from the preloaded words: the checkpoint-layout scale pieces need N before the tail has arrived)
-    V3Geom G{K_, a.n_out, a.nsteps, (K_ >> 7) - (OUTL ? 1 : 0), per_channel_f ? 1 : (K_ >> 7), sets_q * nblk + sets_r};
+    const int KK = CT ? KCT : K_;
+    V3Geom G{KK, a.n_out, a.nsteps, (KK >> 7) - (OUTL ? 1 : 0), per_channel_f ? 1 : (KK >> 7), sets_q * nblk + sets_r};
     const int ssq_n = a.n_ssq_in;
     const float eps = a.eps;
     const f16* const bias = a.bias;
@@ -330,12 +361,17 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
     const uint8_t* const residual = (const uint8_t*)a.residual;
     const uint8_t* const gamma_out = (const uint8_t*)a.gamma_out;
     const uint8_t* const idsp = (const uint8_t*)a.ids;
-    asm volatile("" ::"s"(G.K), "s"(G.nfull), "s"(G.ngroups), "s"(nblk), "s"(sets_q), "s"(sets_r), "s"(xptr), "s"(qw),
-                 "s"(szp), "s"(ow), "s"(xn_gamma));
+    if constexpr (!CT)
+        asm volatile("" ::"s"(G.K), "s"(G.nfull), "s"(G.ngroups), "s"(nblk), "s"(sets_q), "s"(sets_r), "s"(xptr), "s"(qw),
+                     "s"(szp), "s"(ow), "s"(xn_gamma));
 
     extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
-    const V3Lds L = v3_lds(G.K, G.ngroups, OUTL ? 128 : 0, RSC, m, NW, XN, SZN, GATHER, XG);
-    const int XB = v3_x_bytes(G.K), SZB = v3_sz_bytes(G.ngroups), XS = v3_x_stride(G.K, m);
+    // (compile-time K: the same functions evaluated by the compiler; KC stands in for K where the instance has none)
+    constexpr int KC = CT ? KCT : 256;
+    constexpr V3Lds LCT = v3_lds(KC, KC >> 7, OUTL ? 128 : 0, RSC, 1, NW, false, false, false, false);
+    const V3Lds L = CT ? LCT : v3_lds(G.K, G.ngroups, OUTL ? 128 : 0, RSC, m, NW, XN, SZN, GATHER, XG);
+    const int XB = CT ? v3_x_bytes(KC) : v3_x_bytes(G.K), SZB = CT ? v3_sz_bytes(KC >> 7) : v3_sz_bytes(G.ngroups), XS = v3_x_stride(G.K, m);
+    constexpr int PXC = CT ? v3_x_bytes(KC) >> 10 : -1, SPSC = CT ? v3_sz_bytes(KC >> 7) >> 10 : -1;   // piece counts of x and of a set's scale words
     uint8_t* const xs = smem + L.xs;                                  // [m][K] fp16 raw (rows XS apart)
     uint8_t* const szl = smem + L.szl;                                // [RSC][SZB / 64][16] u32
     uint8_t* const owl = smem + L.owl;                                // [RSC] 4 KB: 16 plain rows (chunks ^ row) or 8 interleaved rows
@@ -344,7 +380,8 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
     float* const red = (float*)(smem + L.red);                        // [RSC][NW][16], or [RSC][NW][8 or 16][16] (MB == 2)
     uint8_t* const xf32 = smem + L.xf;                                // xn launches: [K] fp32 h, then its gamma [K] fp16
     uint8_t* const xg = smem + L.xg;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
+    // (compile-time K: the address taken in the LDS address space -- through the generic pointer every use carries a null check)
+    const uint32_t lds0 = CT ? (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem : (uint32_t)(uintptr_t)smem;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -360,6 +397,11 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
     //         wait for until the barrier below.  (What only the epilogue reads is requested behind the ring, step 2b.)
     const int PX = XB >> 10, SPS = SZB >> 10;
     const int SRB = v3_szraw_bytes(G.ngroups), SPR = SRB >> 10;
+    // one piece: the lean form with a compile-time K (dst is wave-uniform by construction there: wave, constants)
+    auto dma = [&](const void* gsrc, uint32_t dst) {
+        if constexpr (CT) v3_dma16_lean(gsrc, dst);
+        else v3_dma16(gsrc, __builtin_amdgcn_readfirstlane(dst));
+    };
     auto stage_all = [&]() {
         if (XG) {
             // x fragments come straight from global memory (step 4)
@@ -367,8 +409,9 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
             // (a gathering launch stages the rows as they are into xraw; step 3b writes xs)
             const uint32_t xdst = lds0 + (GATHER ? L.xraw : L.xs), xstr = GATHER ? (uint32_t)XB : (uint32_t)XS;
             for (int i = 0; i < m; ++i)
-                for (int p = wave; p < PX; p += NW)
-                    v3_dma16(xptr + (size_t)i * G.K * 2 + v3_x_off(G, p, lane), __builtin_amdgcn_readfirstlane(xdst + (uint32_t)i * xstr + ((uint32_t)p << 10)));
+                v3_for_pieces<PXC, NW>(wave, PX, [&](int p) {
+                    dma(xptr + (size_t)i * G.K * 2 + v3_x_off(G, p, lane), xdst + (uint32_t)i * xstr + ((uint32_t)p << 10));
+                });
         } else {               // fp32 h (2 PX pieces) and its gamma (PX pieces) go to their own regions; xs is written in step 3b
             const int PF = v3_xf_bytes(G.K) >> 10;
             for (int p = wave; p < PF + PX; p += NW) {
@@ -379,23 +422,40 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
                              __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)xg + ((uint32_t)(p - PF) << 10)));
             }
         }
-        {
+        auto stage_sz = [&](int rs) {
+            const int set = set_of(rs);
+            if (!SZN) {
+                v3_for_pieces<SPSC, NW>(wave, SPS, [&](int j) {
+                    dma(szp + v3_sz_off(G, set, j, lane), lds0 + L.szl + (uint32_t)rs * SZB + ((uint32_t)j << 10));
+                });
+            } else {        // checkpoint layout: scales (array 0, the szp slot) and scaled_zeros (array 1, the xn_gamma slot), packed in step 3b
+                for (int t = wave; t < 2 * SPR; t += NW) {
+                    const int arr = t >= SPR ? 1 : 0, j = t - arr * SPR;
+                    v3_dma16((arr ? (const uint8_t*)xn_gamma : szp) + v3_szn_off(G, set, j, lane),
+                             __builtin_amdgcn_readfirstlane(lds0 + L.szraw + (uint32_t)(arr * RSC + rs) * SRB + ((uint32_t)j << 10)));
+                }
+            }
+        };
+        auto stage_ow = [&](int rs) {
+            dma(ow + (OWIL ? v3_owil_off(set_of(rs), wave - (NW - 4), lane) : v3_ow_off(set_of(rs), wave - (NW - 4), lane)),
+                (CT ? lds0 + L.owl : (uint32_t)(uintptr_t)owl) + (uint32_t)rs * 4096u + ((uint32_t)(wave - (NW - 4)) << 10));
+        };
+        if constexpr (CT) {
+            // the wave's role is tested once, not once per row set: all scale pieces of the wave, then all its outlier pieces
+            // (the same pieces per wave, all of them older than its ring loads -- which is all the counted waits ask for)
+            if (SPSC >= NW || wave < SPSC) {
+    #pragma unroll
+                for (int rs = 0; rs < RSC; ++rs) stage_sz(rs);
+            }
+            if (OUTL && wave >= NW - 4) {
+    #pragma unroll
+                for (int rs = 0; rs < RSC; ++rs) stage_ow(rs);
+            }
+        } else {
     #pragma unroll
             for (int rs = 0; rs < RSC; ++rs) {
-                const int set = set_of(rs);
-                if (!SZN) {
-                    for (int j = wave; j < SPS; j += NW)
-                        v3_dma16(szp + v3_sz_off(G, set, j, lane), __builtin_amdgcn_readfirstlane(lds0 + L.szl + (uint32_t)rs * SZB + ((uint32_t)j << 10)));
-                } else {        // checkpoint layout: scales (array 0, the szp slot) and scaled_zeros (array 1, the xn_gamma slot), packed in step 3b
-                    for (int t = wave; t < 2 * SPR; t += NW) {
-                        const int arr = t >= SPR ? 1 : 0, j = t - arr * SPR;
-                        v3_dma16((arr ? (const uint8_t*)xn_gamma : szp) + v3_szn_off(G, set, j, lane),
-                                 __builtin_amdgcn_readfirstlane(lds0 + L.szraw + (uint32_t)(arr * RSC + rs) * SRB + ((uint32_t)j << 10)));
-                    }
-                }
-                if (OUTL && wave >= NW - 4)
-                    v3_dma16(ow + (OWIL ? v3_owil_off(set, wave - (NW - 4), lane) : v3_ow_off(set, wave - (NW - 4), lane)),
-                             __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)owl + (uint32_t)rs * 4096u + ((uint32_t)(wave - (NW - 4)) << 10)));
+                stage_sz(rs);
+                if (OUTL && wave >= NW - 4) stage_ow(rs);
             }
         }
     };
@@ -407,7 +467,10 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
     //         issues past the end re-read the wave's last step (a valid address).
     const int nsw = (G.nfull - wave + NW - 1) / NW;
     constexpr uint32_t STEPB = BITS == 3 ? 768u : 256u;              // bytes from one 128-k step of a row (group) to the next
-    const uint32_t set_bytes = BITS == 3 ? (uint32_t)G.nfull * 768u : (uint32_t)G.K * 8u;   // one 16-row set
+    uint32_t set_bytes = BITS == 3 ? (uint32_t)G.nfull * 768u : (uint32_t)G.K * 8u;   // one 16-row set
+    // (compile-time K: kept in a scalar register like the run-time value -- as a literal it does not fit the loads' offset
+    //  field, and hipcc then forms the ring addresses with 64-bit vector adds)
+    if constexpr (CT) asm volatile("" : "+s"(set_bytes));
     const uint8_t* const wbase = qw + (BITS == 3 ? v3w3_set_off(G, set0) : v3_w_set_off(G, set0));         // wave-uniform
     const uint32_t lane_off = BITS == 3 ? (uint32_t)lane * 12u : v3_w_lane_off(G, nl, kc);
     const uint32_t step0 = min((uint32_t)wave * STEPB, BITS == 3 ? v3w3_last_step_off(G) : v3_last_step_off(G));
@@ -445,12 +508,11 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
     //          complete before the vmcnt(0) every wave executes in front of the final barrier.
     if (MB == 1 && MODE == V3_MODE_PLAIN && residual && wave == 1) {
         const bool g_lane = lane >= 16 && gamma_out != nullptr;
-        v3_dma16((g_lane ? gamma_out : residual) + v3_epi_off(set0, RS, g_lane ? lane : (lane < 16 ? lane : 0)),
-                 __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)epl));
+        dma((g_lane ? gamma_out : residual) + v3_epi_off(set0, RS, g_lane ? lane : (lane < 16 ? lane : 0)), CT ? lds0 + L.epl : (uint32_t)(uintptr_t)epl);
     }
     if (MB == 1 && ssq_in && (wave == 2 || wave == 3) && (wave - 2) * 256 < ssq_n) {       // <= 2 pieces of 256 floats
         const int v = min((wave - 2) * 64 + lane, (ssq_n - 1) >> 2);             // clamped 16-byte vector of the array
-        v3_dma16(ssq_in + (size_t)v * 16, __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ssql + (uint32_t)(wave - 2) * 1024u));
+        dma(ssq_in + (size_t)v * 16, (CT ? lds0 + L.ssql : (uint32_t)(uintptr_t)ssql) + (uint32_t)(wave - 2) * 1024u);
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -873,12 +935,13 @@ __global__ __launch_bounds__(V3_LAUNCH_THREADS(NW)) void gemv_v3_kernel(const ui
 int gemv_v3_blocks(int nsets);
 bool gemv_v3_ok(int K, int G, int n_out);
 // What gemv_v3_launch runs: the grid (nblk blocks; the first sets_r of them hold rs_cap row sets, the others sets_q), the instance
-// gemv_v3_kernel<nw, D, outl, mode, bits, mb, rs_cap, fl, xg> and its dynamic LDS.  gemv_v3_plan (gemv_v3.hip) is the one place
+// gemv_v3_kernel<nw, D, outl, mode, bits, mb, rs_cap, fl, xg, kct> and its dynamic LDS.  gemv_v3_plan (gemv_v3.hip) is the one place
 // that decides any of it; the launcher executes the plan and keeps it per thread (gemv_v3_last_plan) beside g_last_variant.
 // flags: the V3_F_* bits of the operands (v3_flags), and V3_PLAN_XG for V3Args::xg (a bit of the plan only, never the kernel's).
 constexpr uint32_t V3_PLAN_XG = 1u << 28;
 struct V3Plan {
     int nblk, rs_cap, sets_q, sets_r, nw, D, outl, mode, bits, fl, mb, xg;
+    int kct;                // the K compiled into the instance (gemv_v3_dispatch.h: V3_CTK), 0: K is the kernel's run-time argument
     size_t smem;
     bool ok;                // false: the launcher refuses (the other fields then say what it would have needed)
 };

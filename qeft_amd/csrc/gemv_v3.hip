@@ -50,6 +50,8 @@ static int env_int(const char* name) {
 //             instantiated with 4 only, 12-wave blocks with 2 only
 //   half      the instances without the flag paths (gemv_v3_plain.hip) for one batch row and no run-time flag, else the flagged ones
 //   MB        2 for several batch rows (8 waves, 4 bits, PLAIN, flagged half)
+//   K         a template argument where (waves, ring, row sets, mode, K) is a row of V3_CTK (gemv_v3_dispatch.h: the engine's
+//             Llama-2-7B / -13B launches), else the kernel's run-time argument; QEFT_GEMV_CTK=0: always the latter
 // ok is false for what the launcher refuses: more than V3_MAX_M batch rows, a block that does not fit the chip's 160 KB of LDS
 // (many batch rows of a long x: the caller splits the batch, gemv_v3_max_rows), 65536 blocks or more, batch rows in PAIR mode /
 // with 3 bits / with the consumer-side norm, xg without batch rows or with a gather, the consumer-side norm on checkpoint-layout
@@ -88,6 +90,10 @@ V3Plan gemv_v3_plan(const V3Geom& g, int m, int mode, int bits, uint32_t flags) 
     p.xg = xg;
     // plain launches (no run-time flag, one batch row): the instantiations without the flag paths (gemv_v3_plain.hip)
     p.fl = !(m <= 1 && (flags & (V3_F_PERCH | V3_F_XN | V3_F_SZN | V3_F_OWIL | V3_F_GATHER)) == 0);
+    // compile-time K: the instances of the engine's 7B / 13B launches exist a second time with their K as a template argument
+    // (gemv_v3_dispatch.h: V3_CTK, v3_ctk_pick); QEFT_GEMV_CTK=0 keeps every launch on the run-time instance (A/B)
+    static const int no_ctk = getenv("QEFT_GEMV_CTK") && atoi(getenv("QEFT_GEMV_CTK")) == 0;
+    p.kct = v3_ctk_pick(p, g.K, !no_ctk);
     p.ok = m <= V3_MAX_M && p.smem <= 160 * 1024 && p.nblk < 65536 &&        // (nblk, sets_r share dwords with rs_cap, sets_q)
            (mode == V3_MODE_PLAIN || mode == V3_MODE_PAIR) && p.rs_cap <= V3_MAX_RS &&
            !(m > 1 && (mode != V3_MODE_PLAIN || p.bits == 3 || xn)) &&

@@ -15,6 +15,48 @@ hipError_t gemv_v3_dispatch_plain(const V3Args& a, const V3Plan& p, hipStream_t 
 // depth 2, for one-set launches with a long K (round 4: down_proj 7.44 -> 7.31 us, profiles/r04_gemv_lab.txt).
 // Nothing is decided here: each function maps fields of the plan (gemv_v3_plan) to template arguments, and a plan that names an
 // instance the build does not hold is an error.
+
+// Compile-time K (gemv_v3.h: KCT).  The decode engine launches each kind of linear with one K for the life of the model, so the
+// instances its Llama-2-7B and -13B launches run are built a second time with that K as a template argument: flag-free half, one
+// batch row, 4 bits, with the outlier step.  The table is the whole choice: v3_ctk_pick (called by gemv_v3_plan, and by nobody
+// else) looks a plan up in it, and launch_dmr instantiates exactly its rows.  Any other shape -- another K, another grid and so
+// another (waves, ring, row sets) -- runs the run-time instance; QEFT_GEMV_CTK=0 sends every launch there (A/B).
+struct V3CtkRow {
+    int nw, D, rs_cap, mode, K;
+};
+constexpr V3CtkRow V3_CTK[] = {
+    {8, 6, 3, V3_MODE_PLAIN, 4096},     // 7B  q|k|v     12288 x 4096: 256 blocks of three sets
+    {4, 4, 3, V3_MODE_PAIR, 4096},      //     gate|up   22016 x 4096: 459 blocks of three
+    {8, 2, 1, V3_MODE_PLAIN, 4096},     //     o_proj     4096 x 4096: 256 blocks of one
+    {12, 2, 1, V3_MODE_PLAIN, 11008},   //     down       4096 x 11008
+    {8, 6, 4, V3_MODE_PLAIN, 5120},     // 13B q|k|v     15360 x 5120: 240 blocks of four
+    {4, 4, 4, V3_MODE_PAIR, 5120},      //     gate|up   27648 x 5120: 432 blocks of four
+    {8, 4, 2, V3_MODE_PLAIN, 5120},     //     o_proj     5120 x 5120: 160 blocks of two
+    {8, 4, 2, V3_MODE_PLAIN, 13824},    //     down       5120 x 13824
+};
+constexpr int V3_CTK_ROWS = (int)(sizeof(V3_CTK) / sizeof(V3_CTK[0]));
+// the K to compile in for this plan and this K, or 0 (the run-time instance)
+inline int v3_ctk_pick(const V3Plan& p, int K, bool enabled) {
+    if (!enabled || p.fl || p.mb != 1 || p.bits != 4 || !p.outl || p.xg) return 0;
+    for (const V3CtkRow& r : V3_CTK)
+        if (r.nw == p.nw && r.D == p.D && r.rs_cap == p.rs_cap && r.mode == p.mode && r.K == K) return K;
+    return 0;
+}
+
+// launch_dmr's search of the table: row I and the rest
+template <int NW, int D, int RSC, int I, typename GO>
+static hipError_t launch_ctk(const V3Plan& p, GO&& go) {
+    if constexpr (I < V3_CTK_ROWS) {
+        constexpr V3CtkRow R = V3_CTK[I];
+        if constexpr (R.nw == NW && R.D == D && R.rs_cap == RSC) {
+            if (p.kct == R.K && p.mode == R.mode) return go(gemv_v3_kernel<NW, D, true, R.mode, 4, 1, RSC, false, false, R.K>);
+        }
+        return launch_ctk<NW, D, RSC, I + 1>(p, go);
+    } else {
+        return hipErrorInvalidValue;        // a plan that names an instance the build does not hold
+    }
+}
+
 template <int NW, int D, bool OUTL, int BITS, int RSC, bool FL>
 static hipError_t launch_dmr(const V3Args& a, const V3Plan& p, hipStream_t st) {
     auto go = [&](auto kern) -> hipError_t {
@@ -25,6 +67,10 @@ static hipError_t launch_dmr(const V3Args& a, const V3Plan& p, hipStream_t st) {
         hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(NW * 64), p.smem, st, V3_KERNEL_ARGS(a));
         return hipGetLastError();
     };
+    if (p.kct != 0) {
+        if constexpr (!FL && BITS == 4 && OUTL) return launch_ctk<NW, D, RSC, 0>(p, go);
+        return hipErrorInvalidValue;
+    }
     if constexpr (NW == 8 && BITS == 4 && FL) {       // several batch rows (the reference's gemv entries, m = 2..7; 8..16 from the GEMM entries): plain launches
         if constexpr (D >= 4) {
             if (p.mb > 1 && p.xg) return go(gemv_v3_kernel<8, D, OUTL, V3_MODE_PLAIN, 4, 2, RSC, true, true>);     // x read from global memory

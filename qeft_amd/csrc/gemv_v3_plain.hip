@@ -1,5 +1,6 @@
 // The v3 decode GEMV's instantiations WITHOUT the run-time flag paths (FL = false): the decode engine's plain launches.
-// A translation unit of its own so that the two halves of the instantiation set compile in parallel (gemv_v3_dispatch.h).
+// Also the home of the compile-time-K instances of the engine's Llama-2 launches (gemv_v3_dispatch.h: V3_CTK), which exist in this
+// half only.  A translation unit of its own so that the two halves of the instantiation set compile in parallel (gemv_v3_dispatch.h).
 #include "gemv_v3_dispatch.h"
 
 namespace qeft {

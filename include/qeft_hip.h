@@ -297,15 +297,18 @@ long long qeft_gemv_v3_check_extents_ckpt(int n, int k, int group_size, int n_ou
  *   would set (per-channel follows from group_size == k and need not be given).  Returns QEFT_OK, QEFT_ERR_NULL without `out`,
  *   and -1 for what the launcher refuses: a shape outside the requirements above, m > 16, a block that does not fit the LDS,
  *   several rows in PAIR mode / with 3 bits / with XN, XG with one row or with GATHER, XN with SZN, an unknown or contradictory flag.
+ *   With QEFT_V3_F_ENGINE_M it answers for qeft_decode_linear_m's m-row launches (flag-free half, MB 2, PLAIN or PAIR) and refuses
+ *   m outside 2..8, 3 bits and every flag but XG; that entry asks without XG and, where the x rows do not fit the LDS, with it.
  *   The lab overrides QEFT_GEMV_BLOCKS / _NW / _NW12 / _DEPTH of the process's environment act on it as on the launcher.
- * qeft_gemv_v3_last_plan: what the calling thread's last v3 launch through qeft_decode_linear / _w3 / _hnorm, the gemv entries
- *   or the GEMM entries' few-row route ran (all zero before the first); qeft_decode_linear_m's m-row launches do not set it. */
+ * qeft_gemv_v3_last_plan: what the calling thread's last v3 launch through qeft_decode_linear / _w3 / _hnorm / _m, the gemv
+ *   entries or the GEMM entries' few-row route ran (all zero before the first). */
 #define QEFT_GEMV_V3_PLAN_INTS 13
 #define QEFT_V3_F_PERCH (1u << 24)  /* one group per row (group_size == k) */
 #define QEFT_V3_F_XN (1u << 25)     /* qeft_decode_linear_hnorm: the whole RMSNorm in the launch */
 #define QEFT_V3_F_SZN (1u << 26)    /* scales / scaled_zeros in the checkpoint layout (the gemv and GEMM entries without sz_packed) */
 #define QEFT_V3_F_OWIL (1u << 27)   /* outlier slice from oweight_interleaved (the gemv entries) */
 #define QEFT_V3_F_XG (1u << 28)     /* several rows whose x does not fit the LDS: fragments from global memory */
+#define QEFT_V3_F_ENGINE_M (1u << 29) /* qeft_gemv_v3_plan only: the plan of qeft_decode_linear_m's m-row launches (m = 2..8) */
 #define QEFT_V3_F_GATHER (1u << 31) /* reorder_ids gathered inside the launch */
 int qeft_gemv_v3_plan(int n, int k, int group_size, int n_out, int m, int mode, int bits, int flags, int* out);
 int qeft_gemv_v3_last_plan(int* out);

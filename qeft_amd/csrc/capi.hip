@@ -765,7 +765,8 @@ long long qeft_gemv_v3_check_extents_ckpt(int n, int k, int group_size, int n_ou
 
 // ---- the v3 launcher's plan as integers: what it would run (no HIP call, no GPU needed), what it last ran
 static_assert(QEFT_V3_F_PERCH == qeft::V3_F_PERCH && QEFT_V3_F_XN == qeft::V3_F_XN && QEFT_V3_F_SZN == qeft::V3_F_SZN &&
-              QEFT_V3_F_OWIL == qeft::V3_F_OWIL && QEFT_V3_F_GATHER == qeft::V3_F_GATHER && QEFT_V3_F_XG == qeft::V3_PLAN_XG,
+              QEFT_V3_F_OWIL == qeft::V3_F_OWIL && QEFT_V3_F_GATHER == qeft::V3_F_GATHER && QEFT_V3_F_XG == qeft::V3_PLAN_XG &&
+              QEFT_V3_F_ENGINE_M == qeft::V3_PLAN_ENGINE_M,
               "the header's flag values are the kernel's");
 static void v3_plan_out(const qeft::V3Plan& p, int* out) {
     const int v[QEFT_GEMV_V3_PLAN_INTS] = {p.nblk, p.rs_cap, p.sets_q, p.sets_r, p.nw, p.D, p.outl, p.mode, p.bits, p.fl, p.mb, p.xg, (int)p.smem};
@@ -776,7 +777,8 @@ int qeft_gemv_v3_plan(int n, int k, int group_size, int n_out, int m, int mode, 
     qeft::V3Geom G{};
     if (!out) return QEFT_ERR_NULL;
     if (v3_geom(G, n, k, group_size, n_out, mode) != QEFT_OK || m < 1 || (bits != 4 && bits != 3)) return -1;
-    const uint32_t known = QEFT_V3_F_PERCH | QEFT_V3_F_XN | QEFT_V3_F_SZN | QEFT_V3_F_OWIL | QEFT_V3_F_GATHER | QEFT_V3_F_XG;
+    const uint32_t known = QEFT_V3_F_PERCH | QEFT_V3_F_XN | QEFT_V3_F_SZN | QEFT_V3_F_OWIL | QEFT_V3_F_GATHER | QEFT_V3_F_XG |
+                           QEFT_V3_F_ENGINE_M;
     if (((uint32_t)flags & ~known) != 0) return -1;
     // (flags that contradict the shape: per-channel without group_size == k, an interleaved outlier slice without outliers)
     if ((((uint32_t)flags & QEFT_V3_F_PERCH) && !(G.ngroups == 1 && k > 128)) || (((uint32_t)flags & QEFT_V3_F_OWIL) && n_out == 0)) return -1;

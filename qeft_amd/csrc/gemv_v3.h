@@ -936,9 +936,15 @@ int gemv_v3_blocks(int nsets);
 bool gemv_v3_ok(int K, int G, int n_out);
 // What gemv_v3_launch runs: the grid (nblk blocks; the first sets_r of them hold rs_cap row sets, the others sets_q), the instance
 // gemv_v3_kernel<nw, D, outl, mode, bits, mb, rs_cap, fl, xg, kct> and its dynamic LDS.  gemv_v3_plan (gemv_v3.hip) is the one place
-// that decides any of it; the launcher executes the plan and keeps it per thread (gemv_v3_last_plan) beside g_last_variant.
-// flags: the V3_F_* bits of the operands (v3_flags), and V3_PLAN_XG for V3Args::xg (a bit of the plan only, never the kernel's).
+// that decides any of it; both launchers execute the plan and keep it per thread (gemv_v3_last_plan) beside g_last_variant.
+// flags: the V3_F_* bits of the operands (v3_flags), and two bits of the plan only, never the kernel's: V3_PLAN_XG for V3Args::xg,
+// V3_PLAN_ENGINE_M for the engine's m-row launches (gemv_v3_multi_launch: m = 2..8, fl = 0, mb = 2, PLAIN or PAIR).
 constexpr uint32_t V3_PLAN_XG = 1u << 28;
+constexpr uint32_t V3_PLAN_ENGINE_M = 1u << 29;
+// The flags of the plan for a pack: the run-time flags the kernel will see, and xg
+inline uint32_t v3_plan_flags(const V3Args& a) {
+    return (v3_flags(a) & (V3_F_PERCH | V3_F_XN | V3_F_SZN | V3_F_OWIL | V3_F_GATHER)) | (a.xg ? V3_PLAN_XG : 0u);
+}
 struct V3Plan {
     int nblk, rs_cap, sets_q, sets_r, nw, D, outl, mode, bits, fl, mb, xg;
     int kct;                // the K compiled into the instance (gemv_v3_dispatch.h: V3_CTK), 0: K is the kernel's run-time argument
@@ -946,7 +952,8 @@ struct V3Plan {
     bool ok;                // false: the launcher refuses (the other fields then say what it would have needed)
 };
 V3Plan gemv_v3_plan(const V3Geom& g, int m, int mode, int bits, uint32_t flags);
-const V3Plan& gemv_v3_last_plan();
+extern thread_local V3Plan g_last_plan;
+inline const V3Plan& gemv_v3_last_plan() { return g_last_plan; }
 int gemv_v3_max_rows(V3Args a, int m_want);
 hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st);
 hipError_t gemv_v3_multi_launch(V3Args a, int mode, hipStream_t st);

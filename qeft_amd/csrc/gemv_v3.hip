@@ -50,17 +50,22 @@ static int env_int(const char* name) {
 //             instantiated with 4 only, 12-wave blocks with 2 only
 //   half      the instances without the flag paths (gemv_v3_plain.hip) for one batch row and no run-time flag, else the flagged ones
 //   MB        2 for several batch rows (8 waves, 4 bits, PLAIN, flagged half)
+//   engine-m  V3_PLAN_ENGINE_M, the decode engine's m-row launches (gemv_v3_multi.hip): m = 2..8 packed rows with its fused
+//             epilogues, PLAIN or PAIR, on MB = 2 instances of their own without the flag paths (fl = 0); grid, 8 waves, ring
+//             and LDS as the batch rows above
 //   K         a template argument where (waves, ring, row sets, mode, K) is a row of V3_CTK (gemv_v3_dispatch.h: the engine's
 //             Llama-2-7B / -13B launches), else the kernel's run-time argument; QEFT_GEMV_CTK=0: always the latter
 // ok is false for what the launcher refuses: more than V3_MAX_M batch rows, a block that does not fit the chip's 160 KB of LDS
-// (many batch rows of a long x: the caller splits the batch, gemv_v3_max_rows), 65536 blocks or more, batch rows in PAIR mode /
-// with 3 bits / with the consumer-side norm, xg without batch rows or with a gather, the consumer-side norm on checkpoint-layout
-// scales.  The lab overrides (QEFT_GEMV_BLOCKS, _NW, _NW12, _DEPTH; read once per process) act here and nowhere else.
+// (many batch rows of a long x: the caller splits the batch, gemv_v3_max_rows), 65536 blocks or more, batch rows in PAIR mode
+// (but the engine's) / with 3 bits / with the consumer-side norm, xg without batch rows or with a gather, the consumer-side norm on
+// checkpoint-layout scales, an engine-m launch of other than 2..8 rows or with any run-time flag.  The lab overrides
+// (QEFT_GEMV_BLOCKS, _NW, _NW12, _DEPTH; read once per process) act here and nowhere else.
 V3Plan gemv_v3_plan(const V3Geom& g, int m, int mode, int bits, uint32_t flags) {
     V3Plan p{};
     if (m < 1) m = 1;
     if (g.ngroups == 1 && g.K > 128) flags |= V3_F_PERCH;
     const bool xn = (flags & V3_F_XN) != 0, szn = (flags & V3_F_SZN) != 0, gather = (flags & V3_F_GATHER) != 0, xg = (flags & V3_PLAN_XG) != 0;
+    const bool em = (flags & V3_PLAN_ENGINE_M) != 0, flagged = (flags & (V3_F_PERCH | V3_F_XN | V3_F_SZN | V3_F_OWIL | V3_F_GATHER)) != 0;
     p.nblk = gemv_v3_blocks(g.nsets);
     p.rs_cap = ceil_div(g.nsets, p.nblk);
     p.sets_q = g.nsets / p.nblk;
@@ -89,22 +94,18 @@ V3Plan gemv_v3_plan(const V3Geom& g, int m, int mode, int bits, uint32_t flags) 
     p.mb = m > 1 ? 2 : 1;
     p.xg = xg;
     // plain launches (no run-time flag, one batch row): the instantiations without the flag paths (gemv_v3_plain.hip)
-    p.fl = !(m <= 1 && (flags & (V3_F_PERCH | V3_F_XN | V3_F_SZN | V3_F_OWIL | V3_F_GATHER)) == 0);
+    p.fl = !em && (m > 1 || flagged);
     // compile-time K: the instances of the engine's 7B / 13B launches exist a second time with their K as a template argument
     // (gemv_v3_dispatch.h: V3_CTK, v3_ctk_pick); QEFT_GEMV_CTK=0 keeps every launch on the run-time instance (A/B)
     static const int no_ctk = getenv("QEFT_GEMV_CTK") && atoi(getenv("QEFT_GEMV_CTK")) == 0;
     p.kct = v3_ctk_pick(p, g.K, !no_ctk);
     p.ok = m <= V3_MAX_M && p.smem <= 160 * 1024 && p.nblk < 65536 &&        // (nblk, sets_r share dwords with rs_cap, sets_q)
            (mode == V3_MODE_PLAIN || mode == V3_MODE_PAIR) && p.rs_cap <= V3_MAX_RS &&
-           !(m > 1 && (mode != V3_MODE_PLAIN || p.bits == 3 || xn)) &&
+           !(m > 1 && ((mode != V3_MODE_PLAIN && !em) || p.bits == 3 || xn)) &&
+           !(em && (m < 2 || m > 8 || flagged)) &&        // the engine's m-row launches carry no run-time flag
            !(xg && (m <= 1 || gather)) &&          // x from global memory: batch-row launches without a gather
            !(szn && xn);                           // (the zeros pointer uses xn_gamma's slot)
     return p;
-}
-
-// The flags of the plan for a pack: the run-time flags the kernel will see, and xg
-static uint32_t v3_plan_flags(const V3Args& a) {
-    return (v3_flags(a) & (V3_F_PERCH | V3_F_XN | V3_F_SZN | V3_F_OWIL | V3_F_GATHER)) | (a.xg ? V3_PLAN_XG : 0u);
 }
 
 // Batch rows one launch of this configuration can take (0: not even one): LDS holds m rows of x (twice with a gather)
@@ -114,8 +115,7 @@ int gemv_v3_max_rows(V3Args a, int m_want) {
     return 0;
 }
 
-static thread_local V3Plan g_last_plan{};
-const V3Plan& gemv_v3_last_plan() { return g_last_plan; }
+thread_local V3Plan g_last_plan{};
 
 hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st) {
     if (a.m < 1) a.m = 1;
@@ -128,7 +128,7 @@ hipError_t gemv_v3_launch(V3Args a, int mode, hipStream_t st) {
     g_last_variant = p.mb > 1 ? (p.xg ? "gemv_v3_mb_xg" : "gemv_v3_mb") : mode == V3_MODE_PAIR ? (w3 ? "gemv_v3_w3_pair" : "gemv_v3_pair") : (w3 ? "gemv_v3_w3" : "gemv_v3");
     g_last_plan = p;
     if (!p.fl) return gemv_v3_dispatch_plain(a, p, st);
-    return w3 ? launch_b<3, true>(a, p, st) : launch_b<4, true>(a, p, st);
+    return w3 ? launch_b<3, V3_FAM_FLAGGED>(a, p, st) : launch_b<4, V3_FAM_FLAGGED>(a, p, st);
 }
 
 // ---- host-side enumeration of every address the kernel can form for a configuration (no GPU involved).

@@ -1,6 +1,8 @@
-// Kernel instantiation and dispatch of the v3 decode GEMV, shared by its two translation units: gemv_v3.hip (FL = true: launches
-// that carry run-time flags -- the reference's entry points, the consumer-side norm, per-channel scales, several batch rows) and
-// gemv_v3_plain.hip (FL = false: the decode engine's plain launches).  Two files so that hipcc builds the two halves in parallel.
+// Kernel instantiation and dispatch of the v3 decode GEMV, shared by its three translation units, one per family of instances:
+// gemv_v3.hip (V3_FAM_FLAGGED, FL = true: launches that carry run-time flags -- the reference's entry points, the consumer-side
+// norm, per-channel scales, several batch rows), gemv_v3_plain.hip (V3_FAM_PLAIN, FL = false: the decode engine's one-row launches)
+// and gemv_v3_multi.hip (V3_FAM_ENGINE_M: the engine's m-row launches, MB = 2 without the flag paths).  Three files so that hipcc
+// builds the families in parallel; each instantiates launch_b with its own family only.
 #pragma once
 #include "gemv_v3.h"
 
@@ -9,10 +11,13 @@ namespace qeft {
 // the FL = false half (gemv_v3_plain.hip), called by gemv_v3_launch
 hipError_t gemv_v3_dispatch_plain(const V3Args& a, const V3Plan& p, hipStream_t st);
 
+enum V3Family { V3_FAM_PLAIN, V3_FAM_FLAGGED, V3_FAM_ENGINE_M };
+
 // Instantiations.  8 waves per block (the 16-wave form of round 2 lost to it on every launch kind once the step loop had its row
 // sets at compile time, profiles/r03_gemv_lab.txt): ring depth 2 for every RSC, 4 for RSC <= 2, 6 for RSC >= 3.  4 waves per
 // block with ring depth 4 for launches of more than 256 blocks (several blocks per CU: gate|up 10.47 vs 10.76 us).  12 waves, ring
-// depth 2, for one-set launches with a long K (round 4: down_proj 7.44 -> 7.31 us, profiles/r04_gemv_lab.txt).
+// depth 2, for one-set launches with a long K (round 4: down_proj 7.44 -> 7.31 us, profiles/r04_gemv_lab.txt).  The engine's m-row
+// family holds the 8-wave forms only: ring 2 and the deep ring x outliers x PLAIN / PAIR x RSC 1..4, xg on the deep ring (48).
 // Nothing is decided here: each function maps fields of the plan (gemv_v3_plan) to template arguments, and a plan that names an
 // instance the build does not hold is an error.
 
@@ -57,8 +62,24 @@ static hipError_t launch_ctk(const V3Plan& p, GO&& go) {
     }
 }
 
-template <int NW, int D, bool OUTL, int BITS, int RSC, bool FL>
+// launch_dmr's engine-m family: m = 2..8 rows with the engine's epilogues, PLAIN or PAIR; no flag path, no compile-time K
+template <int NW, int D, bool OUTL, int BITS, int RSC, typename GO>
+static hipError_t launch_em(const V3Plan& p, GO&& go) {
+    if constexpr (NW == 8 && BITS == 4) {
+        if (p.mb != 2 || p.fl || p.kct != 0) return hipErrorInvalidValue;
+        if constexpr (D >= 4) {
+            if (p.xg)       // x read from global memory
+                return p.mode == V3_MODE_PAIR ? go(gemv_v3_kernel<8, D, OUTL, V3_MODE_PAIR, 4, 2, RSC, false, true>) : go(gemv_v3_kernel<8, D, OUTL, V3_MODE_PLAIN, 4, 2, RSC, false, true>);
+        }
+        if (p.xg) return hipErrorInvalidValue;
+        return p.mode == V3_MODE_PAIR ? go(gemv_v3_kernel<8, D, OUTL, V3_MODE_PAIR, 4, 2, RSC, false>) : go(gemv_v3_kernel<8, D, OUTL, V3_MODE_PLAIN, 4, 2, RSC, false>);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <int NW, int D, bool OUTL, int BITS, int RSC, V3Family FAM>
 static hipError_t launch_dmr(const V3Args& a, const V3Plan& p, hipStream_t st) {
+    constexpr bool FL = FAM == V3_FAM_FLAGGED;
     auto go = [&](auto kern) -> hipError_t {
         if (p.smem > 64 * 1024) {
             hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.smem);
@@ -67,51 +88,55 @@ static hipError_t launch_dmr(const V3Args& a, const V3Plan& p, hipStream_t st) {
         hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(NW * 64), p.smem, st, V3_KERNEL_ARGS(a));
         return hipGetLastError();
     };
-    if (p.kct != 0) {
-        if constexpr (!FL && BITS == 4 && OUTL) return launch_ctk<NW, D, RSC, 0>(p, go);
-        return hipErrorInvalidValue;
-    }
-    if constexpr (NW == 8 && BITS == 4 && FL) {       // several batch rows (the reference's gemv entries, m = 2..7; 8..16 from the GEMM entries): plain launches
-        if constexpr (D >= 4) {
-            if (p.mb > 1 && p.xg) return go(gemv_v3_kernel<8, D, OUTL, V3_MODE_PLAIN, 4, 2, RSC, true, true>);     // x read from global memory
+    if constexpr (FAM == V3_FAM_ENGINE_M) {
+        return launch_em<NW, D, OUTL, BITS, RSC>(p, go);
+    } else {
+        if (p.kct != 0) {
+            if constexpr (!FL && BITS == 4 && OUTL) return launch_ctk<NW, D, RSC, 0>(p, go);
+            return hipErrorInvalidValue;
         }
-        if (p.mb > 1 && p.xg) return hipErrorInvalidValue;
-        if (p.mb > 1) return go(gemv_v3_kernel<8, D, OUTL, V3_MODE_PLAIN, 4, 2, RSC, true>);
+        if constexpr (NW == 8 && BITS == 4 && FL) {       // several batch rows (the reference's gemv entries, m = 2..7; 8..16 from the GEMM entries): plain launches
+            if constexpr (D >= 4) {
+                if (p.mb > 1 && p.xg) return go(gemv_v3_kernel<8, D, OUTL, V3_MODE_PLAIN, 4, 2, RSC, true, true>);     // x read from global memory
+            }
+            if (p.mb > 1 && p.xg) return hipErrorInvalidValue;
+            if (p.mb > 1) return go(gemv_v3_kernel<8, D, OUTL, V3_MODE_PLAIN, 4, 2, RSC, true>);
+        }
+        if (p.mb > 1) return hipErrorInvalidValue;
+        return p.mode == V3_MODE_PAIR ? go(gemv_v3_kernel<NW, D, OUTL, V3_MODE_PAIR, BITS, 1, RSC, FL>) : go(gemv_v3_kernel<NW, D, OUTL, V3_MODE_PLAIN, BITS, 1, RSC, FL>);
     }
-    if (p.mb > 1) return hipErrorInvalidValue;
-    return p.mode == V3_MODE_PAIR ? go(gemv_v3_kernel<NW, D, OUTL, V3_MODE_PAIR, BITS, 1, RSC, FL>) : go(gemv_v3_kernel<NW, D, OUTL, V3_MODE_PLAIN, BITS, 1, RSC, FL>);
 }
 
-template <bool OUTL, int BITS, bool FL>
+template <bool OUTL, int BITS, V3Family FAM>
 static hipError_t launch_d(const V3Args& a, const V3Plan& p, hipStream_t st) {
     if (p.nw == 4) {
         if (p.D != 4) return hipErrorInvalidValue;
         switch (p.rs_cap) {
-            case 1: return launch_dmr<4, 4, OUTL, BITS, 1, FL>(a, p, st);
-            case 2: return launch_dmr<4, 4, OUTL, BITS, 2, FL>(a, p, st);
-            case 3: return launch_dmr<4, 4, OUTL, BITS, 3, FL>(a, p, st);
-            case 4: return launch_dmr<4, 4, OUTL, BITS, 4, FL>(a, p, st);
+            case 1: return launch_dmr<4, 4, OUTL, BITS, 1, FAM>(a, p, st);
+            case 2: return launch_dmr<4, 4, OUTL, BITS, 2, FAM>(a, p, st);
+            case 3: return launch_dmr<4, 4, OUTL, BITS, 3, FAM>(a, p, st);
+            case 4: return launch_dmr<4, 4, OUTL, BITS, 4, FAM>(a, p, st);
         }
         return hipErrorInvalidValue;
     }
     if (p.nw == 12) {             // long one-set launches (down_proj: 85 full steps = 8 / 7 per wave instead of 11 / 10)
-        if (p.rs_cap == 1 && p.D == 2) return launch_dmr<12, 2, OUTL, BITS, 1, FL>(a, p, st);
+        if (p.rs_cap == 1 && p.D == 2) return launch_dmr<12, 2, OUTL, BITS, 1, FAM>(a, p, st);
         return hipErrorInvalidValue;
     }
     const bool deep = p.D != 2;       // the deep ring of the block's RSC: 4 loads, 6 with three or four row sets
     if (p.nw != 8 || (deep && p.D != (p.rs_cap >= 3 ? 6 : 4))) return hipErrorInvalidValue;
     switch (p.rs_cap) {           // row sets per block: a compile-time constant of the kernel
-        case 1: return deep ? launch_dmr<8, 4, OUTL, BITS, 1, FL>(a, p, st) : launch_dmr<8, 2, OUTL, BITS, 1, FL>(a, p, st);
-        case 2: return deep ? launch_dmr<8, 4, OUTL, BITS, 2, FL>(a, p, st) : launch_dmr<8, 2, OUTL, BITS, 2, FL>(a, p, st);
-        case 3: return deep ? launch_dmr<8, 6, OUTL, BITS, 3, FL>(a, p, st) : launch_dmr<8, 2, OUTL, BITS, 3, FL>(a, p, st);
-        case 4: return deep ? launch_dmr<8, 6, OUTL, BITS, 4, FL>(a, p, st) : launch_dmr<8, 2, OUTL, BITS, 4, FL>(a, p, st);
+        case 1: return deep ? launch_dmr<8, 4, OUTL, BITS, 1, FAM>(a, p, st) : launch_dmr<8, 2, OUTL, BITS, 1, FAM>(a, p, st);
+        case 2: return deep ? launch_dmr<8, 4, OUTL, BITS, 2, FAM>(a, p, st) : launch_dmr<8, 2, OUTL, BITS, 2, FAM>(a, p, st);
+        case 3: return deep ? launch_dmr<8, 6, OUTL, BITS, 3, FAM>(a, p, st) : launch_dmr<8, 2, OUTL, BITS, 3, FAM>(a, p, st);
+        case 4: return deep ? launch_dmr<8, 6, OUTL, BITS, 4, FAM>(a, p, st) : launch_dmr<8, 2, OUTL, BITS, 4, FAM>(a, p, st);
     }
     return hipErrorInvalidValue;
 }
 
-template <int BITS, bool FL>
+template <int BITS, V3Family FAM>
 static hipError_t launch_b(const V3Args& a, const V3Plan& p, hipStream_t st) {
-    return p.outl ? launch_d<true, BITS, FL>(a, p, st) : launch_d<false, BITS, FL>(a, p, st);
+    return p.outl ? launch_d<true, BITS, FAM>(a, p, st) : launch_d<false, BITS, FAM>(a, p, st);
 }
 
 }  // namespace qeft

@@ -5,72 +5,26 @@
 // fits, and come from global memory (the XG form) where it does not: K = 11008 at m >= 5.
 // Row layouts: x [m][K], y [m][N] (PAIR: [m][N/2]), residual / y32 [m][N], ssq_in [m][n_ssq_in], ynorm [m][N],
 // ssq_out [m][blocks of the launch] (qeft_decode_linear_blocks(N): the same count as the one-row launch).
-#include "gemv_v3.h"
+// What a launch runs is gemv_v3_plan's answer under V3_PLAN_ENGINE_M (gemv_v3.hip), and gemv_v3_dispatch.h launches it: this file
+// holds the family's 48 instances gemv_v3_kernel<8, D, OUTL, MODE, 4, 2, RSC, false, XG> and nothing that decides.
+#include "gemv_v3_dispatch.h"
 
 namespace qeft {
 
-static int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-// Geometry of an m-row engine launch: the one-row launch's blocks and row sets, 8 waves, x in LDS unless it does not fit.
-bool gemv_v3_multi_plan(V3Args& a, size_t& smem) {
-    const int nblk = gemv_v3_blocks(a.g.nsets);
-    a.nblk = nblk;
-    a.rs_cap = cdiv(a.g.nsets, nblk);
-    a.sets_q = a.g.nsets / nblk;
-    a.sets_r = a.g.nsets % nblk;
-    a.nw = V3_NW;
-    a.xg = false;
-    smem = v3_lds(a.g.K, a.g.ngroups, a.g.n_out, a.rs_cap, a.m, V3_NW, false, false, false, false).total;
-    if (smem > 160 * 1024) {
-        a.xg = true;
-        smem = v3_lds(a.g.K, a.g.ngroups, a.g.n_out, a.rs_cap, a.m, V3_NW, false, false, false, true).total;
-    }
-    return smem <= 160 * 1024 && nblk < 65536;
-}
-
-template <int D, bool OUTL, int MODE, int RSC, bool XG>
-static hipError_t go_multi(const V3Args& a, size_t smem, hipStream_t st) {
-    auto kern = gemv_v3_kernel<8, D, OUTL, MODE, 4, 2, RSC, false, XG>;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.nblk), dim3(8 * 64), smem, st, V3_KERNEL_ARGS(a));
-    return hipGetLastError();
-}
-
-template <bool OUTL, int MODE, int RSC>
-static hipError_t launch_multi_r(const V3Args& a, size_t smem, int depth, hipStream_t st) {
-    constexpr int DD = RSC >= 3 ? 6 : 4;        // the deep ring of gemv_v3_dispatch.h
-    if (a.xg) return go_multi<DD, OUTL, MODE, RSC, true>(a, smem, st);
-    return depth >= 4 ? go_multi<DD, OUTL, MODE, RSC, false>(a, smem, st) : go_multi<2, OUTL, MODE, RSC, false>(a, smem, st);
-}
-
-template <bool OUTL, int MODE>
-static hipError_t launch_multi_m(const V3Args& a, size_t smem, int depth, hipStream_t st) {
-    switch (a.rs_cap) {
-        case 1: return launch_multi_r<OUTL, MODE, 1>(a, smem, depth, st);
-        case 2: return launch_multi_r<OUTL, MODE, 2>(a, smem, depth, st);
-        case 3: return launch_multi_r<OUTL, MODE, 3>(a, smem, depth, st);
-        case 4: return launch_multi_r<OUTL, MODE, 4>(a, smem, depth, st);
-    }
-    return hipErrorInvalidValue;
+// The plan of an m-row engine launch: x in LDS unless it does not fit
+static V3Plan engine_m_plan(const V3Geom& g, int m, int mode, int bits, uint32_t flags) {
+    const V3Plan p = gemv_v3_plan(g, m, mode, bits, flags | V3_PLAN_ENGINE_M);
+    return p.ok ? p : gemv_v3_plan(g, m, mode, bits, flags | V3_PLAN_ENGINE_M | V3_PLAN_XG);
 }
 
 // a: packed operands (szp, plain oweight), m = 2..8, no per-channel scales / xn / gather (the launch carries no run-time flag)
 hipError_t gemv_v3_multi_launch(V3Args a, int mode, hipStream_t st) {
-    if (a.m < 2 || a.m > 8 || !a.szp || a.xn_gamma || a.ids || a.bits == 3) return hipErrorInvalidValue;
-    if (a.g.ngroups == 1 && a.g.K > 128) return hipErrorInvalidValue;        // per-channel scales: a flag path
-    if (a.g.n_out > 0 && !a.ow) return hipErrorInvalidValue;
-    size_t smem;
-    if (!gemv_v3_multi_plan(a, smem)) return hipErrorInvalidValue;
-    // ring depth as the batch-row launches of gemv_v3_launch: 4 / 6 loads per wave where a CU holds one block with >= 8 loads
-    const int loads_per_wave = cdiv(a.g.nfull, V3_NW) * a.rs_cap;
-    const int depth = a.xg ? 4 : (a.nblk <= 256 && loads_per_wave >= 8 ? 4 : 2);
-    g_last_variant = a.xg ? "gemv_v3_multi_xg" : mode == V3_MODE_PAIR ? "gemv_v3_multi_pair" : "gemv_v3_multi";
-    if (mode == V3_MODE_PAIR)
-        return a.g.n_out > 0 ? launch_multi_m<true, V3_MODE_PAIR>(a, smem, depth, st) : launch_multi_m<false, V3_MODE_PAIR>(a, smem, depth, st);
-    return a.g.n_out > 0 ? launch_multi_m<true, V3_MODE_PLAIN>(a, smem, depth, st) : launch_multi_m<false, V3_MODE_PLAIN>(a, smem, depth, st);
+    const V3Plan p = engine_m_plan(a.g, a.m, mode, a.bits, v3_plan_flags(a) & ~V3_PLAN_XG);
+    if (!p.ok) return hipErrorInvalidValue;
+    a.nblk = p.nblk, a.rs_cap = p.rs_cap, a.sets_q = p.sets_q, a.sets_r = p.sets_r, a.nw = p.nw, a.xg = p.xg;
+    g_last_variant = p.xg ? "gemv_v3_multi_xg" : mode == V3_MODE_PAIR ? "gemv_v3_multi_pair" : "gemv_v3_multi";
+    g_last_plan = p;
+    return launch_b<4, V3_FAM_ENGINE_M>(a, p, st);
 }
 
 // Host-side enumeration of every address an m-row engine launch forms beyond those of the one-row launch (which
@@ -79,18 +33,15 @@ hipError_t gemv_v3_multi_launch(V3Args a, int mode, hipStream_t st) {
 // y [m][N] or [m][N/2].  n_rows_have: rows the operands really hold (< N: the negative control).
 long long gemv_v3_count_out_of_range_multi(const V3Geom& G, int n_rows_have, int m, int mode, int n_ssq_in) {
     long long bad = 0;
-    V3Args a{};
-    a.g = G;
-    a.m = m;
-    size_t smem;
-    if (!gemv_v3_multi_plan(a, smem)) return 1;
-    const int N = G.nsets * 16, nblk = a.nblk;
+    const V3Plan pl = engine_m_plan(G, m, mode, 4, 0);
+    if (!pl.ok) return 1;
+    const int N = G.nsets * 16, nblk = pl.nblk;
     const size_t x_bytes = (size_t)m * G.K * 2, rows_f32 = (size_t)m * n_rows_have * 4, rows_f16 = (size_t)m * n_rows_have * 2;
-    const V3Lds L = v3_lds(G.K, G.ngroups, G.n_out, a.rs_cap, m, V3_NW, false, false, false, a.xg);
+    const V3Lds L = v3_lds(G.K, G.ngroups, G.n_out, pl.rs_cap, m, V3_NW, false, false, false, pl.xg);
     const int XB = v3_x_bytes(G.K), XS = v3_x_stride(G.K, m);
     for (int lane = 0; lane < 64; ++lane) {
         const int nl = lane & 15, kc = lane >> 4, row = nl < m - 1 ? nl : m - 1;
-        if (a.xg) {
+        if (pl.xg) {
             for (int step = 0; step < G.nsteps; ++step) bad += (size_t)row * G.K * 2 + (size_t)step * 256 + kc * 64 + 64 > x_bytes;
         } else {
             for (int i = 0; i < m; ++i)
@@ -103,7 +54,7 @@ long long gemv_v3_count_out_of_range_multi(const V3Geom& G, int n_rows_have, int
         }
     }
     // the partial sums of every (row set, wave, batch row) inside the red region
-    bad += (size_t)((a.rs_cap - 1) * V3_NW + V3_NW - 1) * 8 * 16 * 4 + (size_t)7 * 16 * 4 + 16 * 4 > v3_red_bytes(a.rs_cap, m, V3_NW);
+    bad += (size_t)((pl.rs_cap - 1) * V3_NW + V3_NW - 1) * 8 * 16 * 4 + (size_t)7 * 16 * 4 + 16 * 4 > v3_red_bytes(pl.rs_cap, m, V3_NW);
     for (int b = 0; b < nblk; ++b) {
         int set0, RS;
         v3_block_sets(v3_xcd_block(b, nblk), G.nsets / nblk, G.nsets % nblk, set0, RS);

@@ -6,7 +6,7 @@
 namespace qeft {
 
 hipError_t gemv_v3_dispatch_plain(const V3Args& a, const V3Plan& p, hipStream_t st) {
-    return p.bits == 3 ? launch_b<3, false>(a, p, st) : launch_b<4, false>(a, p, st);
+    return p.bits == 3 ? launch_b<3, V3_FAM_PLAIN>(a, p, st) : launch_b<4, V3_FAM_PLAIN>(a, p, st);
 }
 
 }  // namespace qeft

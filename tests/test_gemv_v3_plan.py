@@ -1,8 +1,9 @@
 """The plan of the v3 decode GEMV launcher (csrc/gemv_v3.hip gemv_v3_plan) against an independent
 restatement, and the census of its instances against the pinned GPU cases.
 
-gemv_v3_launch chooses between the 232 instantiations of one kernel template that it and gemv_v3_plain.hip build, and qeft_last_variant calls all of them
-"gemv_v3".  qeft_gemv_v3_plan says which one a launch would run: host arithmetic, no GPU.  Below, the rules are written down a
+gemv_v3_launch chooses between the 232 instantiations of one kernel template that it and gemv_v3_plain.hip build (and the 8 with a
+compile-time K, tests/test_gemv_v3_ctk_plan.py), gemv_v3_multi_launch between the 48 of the engine's m-row family
+(gemv_v3_multi.hip), and qeft_last_variant calls all of the former "gemv_v3" and the latter "gemv_v3_multi".  qeft_gemv_v3_plan says which one a launch would run: host arithmetic, no GPU.  Below, the rules are written down a
 second time in plain Python -- blocks, waves, ring depth, the template's D, the half, the LDS bytes, the refusals -- and compared
 with the library over a sweep; then the set of instances the sweep reaches must be exactly the set that
 tests/test_gpu_gemv_v3_tiers.py pins to a shape, and the instances that are built but that no shape reaches must be exactly
@@ -15,7 +16,9 @@ enter the half, the LDS bytes and the refusals.  So
   * m, mode, bits and the flags are crossed with each other, with both n_out, with the K next to every value of nfull at which
     ceil(nfull / waves) * RSC can pass 8 or nfull passes 64 (K_EDGE), and with the nsets next to every threshold of the blocks rule
     plus every 16th one and the six large ones (NSETS_EDGE);
-  * per-channel scales (group_size == K) are crossed with NSETS_EDGE, every K, both n_out and m of 1 and 2.
+  * per-channel scales (group_size == K) are crossed with NSETS_EDGE, every K, both n_out and m of 1 and 2;
+  * the engine's m-row family (ENGINE_M, with and without XG) is crossed with m of 2, 5, 8 and the refused 1 and 9, both modes, both
+    n_out, NSETS_EDGE and K_EDGE, and at m = 2 with 3 bits, each run-time flag and per-channel scales (all refused).
 The full product of all axes would be some 10^8 queries."""
 import ctypes
 import functools
@@ -23,12 +26,13 @@ import functools
 import pytest
 
 PLAN = ("nblk", "rs_cap", "sets_q", "sets_r", "nw", "D", "outl", "mode", "bits", "fl", "mb", "xg", "smem")
-PERCH, XN, SZN, OWIL, XG, GATHER = 1 << 24, 1 << 25, 1 << 26, 1 << 27, 1 << 28, 1 << 31
+PERCH, XN, SZN, OWIL, XG, ENGINE_M, GATHER = 1 << 24, 1 << 25, 1 << 26, 1 << 27, 1 << 28, 1 << 29, 1 << 31
 PLAIN, PAIR = 0, 1
 
 NSETS = list(range(1, 1301)) + [1376, 1536, 1792, 2048, 3001, 3584]
 KS = list(range(128, 16384 + 1, 128))
 MS = (1, 2, 7, 8, 9, 16)
+MS_ENGINE = (1, 2, 5, 8, 9)       # the engine's m-row launches take 2..8
 NSETS_EDGE = sorted({t + d for t in (256, 512, 1024, 1152) for d in (-2, -1, 0, 1, 2)} | set(NSETS[::16]) | set(NSETS[-6:]) | {1300})
 NFULL_EDGE = (1, 7, 8, 9, 16, 17, 24, 25, 32, 33, 56, 57, 63, 64, 65, 84, 85, 96, 127)
 K_EDGE = sorted({(f + d) * 128 for f in NFULL_EDGE for d in (0, 1)})
@@ -94,8 +98,11 @@ def restated_plan(nsets, k, g, n_out, m, mode, bits, flags):
     perch = g == k and k > 128
     if (flags & PERCH and not perch) or (flags & OWIL and not n_out):
         return None
-    xn, szn, gather, xg = bool(flags & XN), bool(flags & SZN), bool(flags & GATHER), bool(flags & XG)
-    if m > 16 or (m > 1 and (mode == PAIR or bits == 3 or xn)) or (xg and (m == 1 or gather)) or (szn and xn):
+    xn, szn, gather, xg, em = bool(flags & XN), bool(flags & SZN), bool(flags & GATHER), bool(flags & XG), bool(flags & ENGINE_M)
+    if m > 16 or (m > 1 and ((mode == PAIR and not em) or bits == 3 or xn)) or (xg and (m == 1 or gather)) or (szn and xn):
+        return None
+    # the engine's m-row launches: 2..8 rows, 4 bits, no run-time flag; PLAIN or PAIR on the flag-free MB = 2 instances
+    if em and (not 2 <= m <= 8 or bits == 3 or perch or flags & (XN | SZN | OWIL | GATHER)):
         return None
     nfull, ngroups = (k - n_out) // 128, 1 if g == k else k // 128
     nblk = blocks(nsets)
@@ -105,7 +112,7 @@ def restated_plan(nsets, k, g, n_out, m, mode, bits, flags):
         nw = 12
     deep = xg or (nblk <= 256 and _cd(nfull, nw) * rs >= 8)
     d = 4 if nw == 4 else 2 if nw == 12 else (6 if rs >= 3 else 4) if deep else 2
-    fl = int(m > 1 or perch or (flags & (XN | SZN | OWIL | GATHER)) != 0)
+    fl = int(not em and (m > 1 or perch or (flags & (XN | SZN | OWIL | GATHER)) != 0))
     smem = lds_bytes(k, ngroups, n_out, rs, m, nw, xn, szn, gather, xg)
     if smem > 160 * 1024 or nblk >= 65536:
         return None
@@ -143,6 +150,16 @@ def sweep():
                     yield nsets, k, k, n_out, m, PLAIN, 4, 0
                 for mode, bits in ((PAIR, 4), (PLAIN, 3), (PAIR, 3)):
                     yield nsets, k, k, n_out, 1, mode, bits, 0
+        for k in K_EDGE:
+            for n_out in (0, 128):
+                for mode in (PLAIN, PAIR):
+                    for flags in (ENGINE_M, ENGINE_M | XG):
+                        for m in MS_ENGINE:
+                            yield nsets, k, 128, n_out, m, mode, 4, flags
+                        yield nsets, k, 128, n_out, 2, mode, 3, flags
+                        yield nsets, k, k, n_out, 2, mode, 4, flags
+                        for f in (XN, SZN, OWIL, GATHER):
+                            yield nsets, k, 128, n_out, 2, mode, 4, flags | f
 
 
 @pytest.fixture(scope="module")
@@ -203,6 +220,8 @@ def test_every_pinned_case_is_what_the_plan_says(lib):
     for c in cases:
         p = query(lib, c.n // 16, c.k, c.g, c.r, c.m, c.mode, c.bits, c.flags)
         assert p is not None and instance(p) == c.want and p[0] == tiers.blocks_of(c) and restated_plan(c.n // 16, c.k, c.g, c.r, c.m, c.mode, c.bits, c.flags) == p, (c, p)
+        if c.entry == "engine_m":       # qeft_decode_linear_m asks without XG first: an xg case is one that this refuses, and no other
+            assert (query(lib, c.n // 16, c.k, c.g, c.r, c.m, c.mode, c.bits, ENGINE_M) is None) == bool(c.flags & XG), c
 
 
 def test_the_unreachable_list_is_exact(reached):
@@ -215,9 +234,13 @@ def test_the_unreachable_list_is_exact(reached):
     for t in got:
         assert {i[3:] for i in reached if i[:3] == t and i[7] == 1} == {(o, md, b, f, 1, 0) for o in (0, 1) for md in (0, 1) for b in (4, 3) for f in (0, 1)}, t
     # several batch rows: 8 waves, 4 bits, PLAIN, the flagged half; xg on the deep rings only
-    mb = {i for i in reached if i[7] == 2}
+    mb = {i for i in reached if i[7] == 2 and i[6] == 1}
     assert mb == {(8, rs, d, o, 0, 4, 1, 2, x) for rs in (1, 2, 3, 4) for d in (2, 6 if rs >= 3 else 4) for o in (0, 1) for x in (0, 1)
                   if not (x and d == 2)}
+    # the engine's m-row family: the same geometries on the flag-free half, PLAIN and PAIR: the 48 instances of gemv_v3_multi.hip
+    em = {i for i in reached if i[7] == 2 and i[6] == 0}
+    assert em == {(8, rs, d, o, md, 4, 0, 2, x) for rs in (1, 2, 3, 4) for d in (2, 6 if rs >= 3 else 4) for o in (0, 1) for md in (0, 1)
+                  for x in (0, 1) if not (x and d == 2)} and len(em) == 48
 
 
 def test_the_query_refuses_what_the_launcher_refuses(lib):
@@ -233,6 +256,15 @@ def test_the_query_refuses_what_the_launcher_refuses(lib):
                 (16 * 4 * 65536, 256, 128, 0, 1, 0, 4, 0)):
         assert q(*bad, out) == -1, bad
     assert q(16, 16384, 128, 0, 16, 0, 4, XG, out) == 0 and out[11] == 1 and out[5] == 4      # the x rows leave the LDS: it fits
+    # the engine's m-row launches: two PAIR rows on the flag-free half; refused: 1 and 9 rows, 3 bits, per-channel scales, every
+    # run-time flag, a bit that is neither flag nor plan bit, x rows that do not fit the LDS (taken with XG)
+    assert q(16, 256, 128, 128, 2, 1, 4, ENGINE_M, out) == 0 and tuple(out) == (1, 1, 1, 0, 8, 2, 1, 1, 4, 0, 2, 0, lds_bytes(256, 2, 128, 1, 2, 8, 0, 0, 0, 0))
+    for bad in ((16, 256, 128, 128, 1, 0, 4, ENGINE_M), (16, 256, 128, 128, 9, 0, 4, ENGINE_M), (16, 256, 128, 128, 2, 0, 3, ENGINE_M),
+                (16, 256, 256, 128, 2, 0, 4, ENGINE_M), (16, 256, 128, 128, 2, 0, 4, ENGINE_M | XN), (16, 256, 128, 128, 2, 0, 4, ENGINE_M | SZN),
+                (16, 256, 128, 128, 2, 0, 4, ENGINE_M | OWIL), (16, 256, 128, 128, 2, 0, 4, (ENGINE_M | GATHER) - (1 << 32)),
+                (16, 256, 128, 128, 1, 0, 4, ENGINE_M | XG), (16, 256, 128, 128, 2, 0, 4, ENGINE_M | 1 << 30), (16, 11008, 128, 128, 8, 0, 4, ENGINE_M)):
+        assert q(*bad, out) == -1, bad
+    assert q(16, 11008, 128, 128, 8, 0, 4, ENGINE_M | XG, out) == 0 and out[11] == 1 and out[5] == 4 and out[9] == 0
 
 
 def test_the_last_plan_query_needs_no_gpu(lib):

@@ -9,6 +9,7 @@ admits it (the reason says which), with nfull varied so that the outlier step fa
 where nfull < nw leaves waves without a step -- where the row's range of nfull allows it: (8, 1, 4) lives on nfull 57 .. 63 and
 (12, 1, 2) on nfull >= 64, so neither has nfull < nw, and no nfull of 57 .. 63 is a multiple of 8.  The first shape of a row (a
 ragged one: some blocks hold rs_cap sets, the others one fewer) is crossed with outl x mode x bits on both halves.
+EM / EM_XG hold the engine's m-row family (qeft_decode_linear_m, "gemv_v3_multi"): 2..8 rows with the engine's fused epilogues.
 tests/test_gemv_v3_plan.py (no GPU) checks that these tables name exactly the instances a launch can reach.
 
 Every launch goes through the C ABI with each output all-NaN between two NaN bands: the bands must stay NaN, the middle must become
@@ -40,7 +41,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 BAND = 4096                      # NaN elements in front of and behind a banded buffer
 PLAIN, PAIR = 0, 1
-PERCH, XN, SZN, OWIL, XG, GATHER = 1 << 24, 1 << 25, 1 << 26, 1 << 27, 1 << 28, 1 << 31
+PERCH, XN, SZN, OWIL, XG, ENGINE_M, GATHER = 1 << 24, 1 << 25, 1 << 26, 1 << 27, 1 << 28, 1 << 29, 1 << 31
 PLAN_INTS = 13
 EPS = 1e-5
 
@@ -102,8 +103,16 @@ MB = {(1, 2): (48, 1152), (1, 4): (16, 7424), (2, 2): (4112, 1152), (2, 4): (411
 # n_out = 128, K with n_out = 0): without the 4 KB outlier slabs more of x fits, so the two K differ.
 MB_XG = {(1, 4): ("gemv", 7, 16, 11776, 11776), (2, 4): ("gemm", 16, 4112, 4352, 4224), (3, 6): ("gemm", 16, 8224, 3200, 3840),
          (4, 6): ("gemm", 16, 12304, 2688, 3200)}
+# The engine's m-row launches (qeft_decode_linear_m: MB = 2 on the flag-free half, PLAIN and PAIR, 8 waves): (rs_cap, D) -> (n, K at
+# n_out = 128), the smallest shape of each at m = 2.  x from global memory: the entry asks for it where the m rows of x do not fit the
+# LDS (and only there: test_every_pinned_case_is_what_the_plan_says); (rs_cap, D) -> (n, K with n_out = 128, K with n_out = 0), the
+# smallest K at m = 8.  One ragged m (5) on a row of each table: EM_M5 (n, K at n_out = 128, xg).
+EM = {(1, 2): (16, 256), (1, 4): (16, 7424), (2, 2): (4112, 256), (2, 4): (4112, 3328), (3, 2): (8208, 256), (3, 6): (8208, 2304),
+      (4, 2): (12304, 256), (4, 6): (12304, 1280)}
+EM_XG = {(1, 4): (16, 8832, 9344), (2, 4): (4112, 8320, 8832), (3, 6): (8208, 7808, 8320), (4, 6): (12304, 6784, 7808)}
+EM_M5 = {(2, 4): (4112, 3328, False), (1, 4): (16, 14464, True)}
 
-ENTRY_FLAGS = {"decode": lambda r: 0, "hnorm": lambda r: XN, "ckpt": lambda r: SZN | GATHER | (OWIL if r else 0),
+ENTRY_FLAGS = {"engine_m": lambda r: ENGINE_M, "decode": lambda r: 0, "hnorm": lambda r: XN, "ckpt": lambda r: SZN | GATHER | (OWIL if r else 0),
                "gemv": lambda r: SZN | (OWIL if r else 0), "gemm": lambda r: SZN}
 
 
@@ -111,7 +120,7 @@ def _case(n, k128, outl, g_perch, m, mode, bits, entry, triple, reason, xg=False
     r = 128 if outl else 0
     k = k128 if outl else k128 - 128
     flags = ENTRY_FLAGS[entry](r) | (XG if xg else 0)
-    fl = int(m > 1 or g_perch or flags != 0)
+    fl = int(entry != "engine_m" and (m > 1 or g_perch or flags != 0))
     nw, rs, d = triple
     return Case(n, k, r, k if g_perch else 128, m, mode, bits, entry, flags, (nw, rs, d, int(outl), mode, bits, fl, 2 if m > 1 else 1, int(xg)), reason)
 
@@ -144,6 +153,15 @@ def _build_cases():
     for (rs, d), (entry, m, n, k_on, k_off) in MB_XG.items():
         cases.append(_case(n, k_on, True, False, m, PLAIN, 4, entry, (8, rs, d), "the x rows do not fit the LDS", xg=True))
         cases.append(_case(n, k_off + 128, False, False, m, PLAIN, 4, entry, (8, rs, d), "the x rows do not fit the LDS", xg=True))
+    for mode in (PLAIN, PAIR):
+        for (rs, d), (n, k) in EM.items():
+            for outl in (True, False):
+                cases.append(_case(n, k, outl, False, 2, mode, 4, "engine_m", (8, rs, d), "two rows of the verify pass"))
+        for (rs, d), (n, k_on, k_off) in EM_XG.items():
+            cases.append(_case(n, k_on, True, False, 8, mode, 4, "engine_m", (8, rs, d), "eight x rows do not fit the LDS", xg=True))
+            cases.append(_case(n, k_off + 128, False, False, 8, mode, 4, "engine_m", (8, rs, d), "eight x rows do not fit the LDS", xg=True))
+        for (rs, d), (n, k, xg) in EM_M5.items():
+            cases.append(_case(n, k, True, False, 5, mode, 4, "engine_m", (8, rs, d), "five rows: three waves without a row", xg=xg))
     unique = {c[:-1]: c for c in reversed(cases)}                   # (a crossing that is one of the row's own shapes: once)
     # cases that share a packed layer stand together (the cache below holds a few layers)
     return sorted(unique.values(), key=lambda c: (c.n, c.k, c.r, c.g, c.bits))
@@ -297,7 +315,11 @@ def _tolerance(c):
     return 3e-3 if c.entry == "hnorm" else 2e-3 if c.mode == PAIR else REL_TOL
 
 
-@pytest.mark.parametrize("c", CASES, ids=[_id(c) for c in CASES])
+ONE_ENTRY_CASES = [c for c in CASES if c.entry != "engine_m"]
+ENGINE_M_CASES = [c for c in CASES if c.entry == "engine_m"]
+
+
+@pytest.mark.parametrize("c", ONE_ENTRY_CASES, ids=[_id(c) for c in ONE_ENTRY_CASES])
 def test_instance(c):
     from qeft_amd import _lib
     lib = _lib.lib()
@@ -327,6 +349,81 @@ def test_instance(c):
     assert err < _tolerance(c), (c, err)
     if c.mode == PLAIN and c.entry != "hnorm":
         assert elem_err_ok(got, ref), c
+
+
+# ------------------------------------------------------------------------------------------- the engine's m-row family
+@pytest.mark.parametrize("c", ENGINE_M_CASES, ids=[_id(c) for c in ENGINE_M_CASES])
+def test_engine_m_instance(c):
+    """qeft_decode_linear_m on m rows in the engine's forms: PAIR with ssq_in (gate|up); PLAIN with ssq_in (q|k|v: 300 producer sums,
+    both 256-float pieces) and PLAIN with the fp32 residual, gamma_out -> ynorm and ssq_out [m][blocks] (o_proj, down_proj).  Every
+    launch must have run the instance the case names (qeft_gemv_v3_last_plan ==), under the family's variant name, and every output
+    is compared whole with float64: rel_err < REL_TOL and elem_err_ok for PLAIN, the one-row PAIR bound (2e-3) for PAIR."""
+    from qeft_amd import _lib
+    lib = _lib.lib()
+    n, k, m = c.n, c.k, c.m
+    bufs, t, w64 = _layer(n, k, c.r, c.g)
+    x = O.make_activation(m, k, c.r, seed=m + 2)
+    xt = torch.from_numpy(x).to(DEV)
+    rng = np.random.default_rng(n + k + m)
+    n_ssq = 300
+    ssq = (rng.random((m, n_ssq)) * 10 + 1).astype(np.float32)
+    rs_norm = 1.0 / np.sqrt(ssq.astype(np.float64).sum(1, keepdims=True) / k + EPS)
+    ssq_t = torch.from_numpy(ssq).to(DEV)
+    prod, bias = x.astype(np.float64) @ w64.T, bufs["bias"].astype(np.float64)
+    nblk = lib.qeft_decode_linear_blocks(n)
+    want_plan = _plan(lib, c)
+    want_variant = "gemv_v3_multi_xg" if c.want[8] else "gemv_v3_multi_pair" if c.mode == PAIR else "gemv_v3_multi"
+
+    def launch(y, residual=None, ssq_in=None, gamma_out=None, ynorm=None, ssq_out=None):
+        _lib.check(lib.qeft_decode_linear_m(_p(xt), _p(t["qweight"]), _p(t["sz_packed"]), _p(t["oweight"]) if c.r else None, _p(t["bias"]), y,
+                                            n, k, c.g, c.r, c.mode, residual, ssq_in, n_ssq if ssq_in else 0, EPS, gamma_out, ynorm, ssq_out, m,
+                                            _st()))
+        ran = _last_plan(lib)
+        assert _instance(ran) == c.want and ran == want_plan and ran[0] == nblk, (ran, c.want, c.reason)
+        assert _lib.last_variant() == want_variant
+
+    def worst(err):
+        print(f"[v3 tier] {_id(c)}: rel_err {err:.3e}")
+        if c.want not in _WORST or err > _WORST[c.want][0]:
+            _WORST[c.want] = (err, _id(c))
+
+    n_y = m * (n // 2 if c.mode == PAIR else n)
+    y, y2 = _Banded(n_y, torch.float16), _Banded(n_y, torch.float16)
+    launch(y.ptr(), ssq_in=_p(ssq_t))
+    launch(y2.ptr(), ssq_in=_p(ssq_t))
+    torch.cuda.synchronize()
+    assert y.still_poisoned() and y2.still_poisoned(), c
+    got = y.mid.cpu().numpy().astype(np.float64).reshape(m, -1)
+    assert np.isfinite(got).all(), c
+    assert torch.equal(y.mid, y2.mid), "a second launch of the same plan sums in the same order"
+    ref = prod * rs_norm + bias
+    if c.mode == PAIR:
+        err = rel_err(got, _silu_pair(ref))
+        worst(err)
+        assert err < 2e-3, (c, err)
+        return
+    err = rel_err(got, ref)
+    worst(err)
+    assert err < REL_TOL and elem_err_ok(got, ref), (c, err)
+    # the producer form: y32 = W x + bias + residual (fp32, in place), ynorm = fp16(y32 * gamma), ssq_out[row][block]
+    h0 = rng.standard_normal((m, n)).astype(np.float32)
+    gamma = (1 + 0.1 * rng.standard_normal(n)).astype(np.float16)
+    gt = torch.from_numpy(gamma).to(DEV)
+    y32 = _Banded(m * n, torch.float32, init=torch.from_numpy(h0).to(DEV).reshape(-1))
+    ynorm, so = _Banded(m * n, torch.float16), _Banded(m * nblk, torch.float32)
+    launch(y32.ptr(), residual=y32.ptr(), gamma_out=_p(gt), ynorm=ynorm.ptr(), ssq_out=so.ptr())
+    torch.cuda.synchronize()
+    for b in (y32, ynorm, so):
+        assert b.still_poisoned() and bool(torch.isfinite(b.mid).all()), c
+    href = h0.astype(np.float64) + prod + bias
+    h = y32.mid.cpu().numpy().astype(np.float64).reshape(m, n)
+    err = rel_err(h, href)
+    worst(err)
+    assert err < REL_TOL and elem_err_ok(h, href), (c, err)
+    yn, ynref = ynorm.mid.cpu().numpy().astype(np.float64).reshape(m, n), href * gamma.astype(np.float64)
+    assert rel_err(yn, ynref) < REL_TOL and elem_err_ok(yn, ynref), c
+    sums, sref = so.mid.cpu().numpy().astype(np.float64).reshape(m, nblk).sum(1), (href ** 2).sum(1)
+    assert (np.abs(sums - sref) / sref).max() < REL_TOL, c
 
 
 # ------------------------------------------------------------------------------------ the producer epilogue on ragged blocks

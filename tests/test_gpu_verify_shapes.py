@@ -41,8 +41,9 @@ SHAPES = {
     "70b": [(10240, 8192), (8192, 8192), (57344, 8192), (8192, 28672)],
 }
 KINDS = ["qkv", "o", "gu", "down"]
-# the launch geometry gemv_v3_multi_plan picks for m = 2..8: row sets per block (rs_cap), "X" = x read from global memory
-# (m K does not fit LDS next to the block's scale / outlier slabs).  Asserted launch by launch: a planner change fails here.
+# the launch geometry gemv_v3_plan (its engine-m clause) picks for m = 2..8: row sets per block (rs_cap), "X" = x
+# read from global memory (m K does not fit LDS next to the block's scale / outlier slabs).  Read from qeft_gemv_v3_last_plan
+# launch by launch: a planner change fails here.
 GEOMETRY = {
     ("7b", "qkv"): ["3"] * 7, ("7b", "o"): ["1"] * 7, ("7b", "gu"): ["3"] * 7, ("7b", "down"): ["1"] * 5 + ["X1"] * 2,
     ("13b", "qkv"): ["4"] * 7, ("13b", "o"): ["2"] * 7, ("13b", "gu"): ["4"] * 7, ("13b", "down"): ["2"] * 3 + ["X2"] * 4,
@@ -138,6 +139,14 @@ def _gemv_launch(lib, ck, op, m, x, y, mode=0, residual=None, ssq_in=None, gamma
                                 ssq_in.shape[1] if ssq_in is not None else 0, 1e-5, p(gamma), p(ynorm), p(ssq_out), m, _st()))
 
 
+def _last_plan(lib):
+    """qeft_gemv_v3_last_plan as a dict of the fields this file asserts."""
+    import ctypes
+    out = (ctypes.c_int * 13)()
+    assert lib.qeft_gemv_v3_last_plan(out) == 0
+    return dict(nblk=out[0], rs_cap=out[1], nw=out[4], D=out[5], fl=out[9], mb=out[10], xg=out[11])
+
+
 def _close(got, ref, what):
     got, ref = got.double().cpu().numpy(), ref.double().cpu().numpy()
     assert np.isfinite(got).all(), what
@@ -158,7 +167,6 @@ def test_decode_linear_m_fp64(shape, kind, n_out):
     g = torch.Generator(device=DEV).manual_seed(n + k)
     x = (torch.randn(8, k, generator=g, device=DEV) * 0.5).half()
     nb = lib.qeft_decode_linear_blocks(n)
-    rs_cap = _cdiv(n // 16, nb)
     # the raw products x W^T in fp64, per module (all 8 rows at once: m rows are a prefix), one dense weight alive at a time
     raw = []
     for ql in mods:
@@ -179,7 +187,7 @@ def test_decode_linear_m_fp64(shape, kind, n_out):
             if kind == "qkv":
                 y = torch.zeros(m, n, dtype=torch.float16, device=DEV)
                 _gemv_launch(lib, ck, op, m, xm, y, ssq_in=ssq)
-                variant = L.last_variant()
+                variant, plan = L.last_variant(), _last_plan(lib)
                 ref = torch.cat([r[:m] for r in raw], 1) * rs
                 torch.cuda.synchronize()
                 _close(y, ref, (shape, kind, m))
@@ -191,7 +199,7 @@ def test_decode_linear_m_fp64(shape, kind, n_out):
             else:
                 y = torch.zeros(m, n // 2, dtype=torch.float16, device=DEV)
                 _gemv_launch(lib, ck, op, m, xm, y, mode=1, ssq_in=ssq)
-                variant = L.last_variant()
+                variant, plan = L.last_variant(), _last_plan(lib)
                 gt, up = raw[0][:m] * rs, raw[1][:m] * rs
                 torch.cuda.synchronize()
                 # per tensor: the one-row PAIR launch's bound against fp64 (tests/test_gpu_gemv_v3.py::test_gate_up_pair_silu:
@@ -214,7 +222,7 @@ def test_decode_linear_m_fp64(shape, kind, n_out):
             yn = torch.zeros(m, n, dtype=torch.float16, device=DEV)
             so = torch.full((m, nb), float("nan"), device=DEV)
             _gemv_launch(lib, ck, op, m, xm, h, residual=h, gamma=gamma, ynorm=yn, ssq_out=so)
-            variant = L.last_variant()
+            variant, plan = L.last_variant(), _last_plan(lib)
             prod = raw[0][:m]
             href = h0.double() + prod
             torch.cuda.synchronize()
@@ -228,12 +236,17 @@ def test_decode_linear_m_fp64(shape, kind, n_out):
             for r0 in (0, n - 16):
                 yo = _oracle_rows(mods[0], xm, r0, r0 + 16)
                 assert rel_err((h - h0)[:, r0:r0 + 16].cpu().numpy(), yo) < REL_TOL, (shape, kind, m, r0)
-        xg = variant.endswith("_xg")
+        xg, rs_cap = bool(plan["xg"]), plan["rs_cap"]
+        assert xg == variant.endswith("_xg") and rs_cap == _cdiv(n // 16, nb) and plan["nblk"] == nb, (plan, variant)
         want = "gemv_v3_multi_xg" if xg else ("gemv_v3_multi_pair" if kind == "gu" else "gemv_v3_multi")
         assert variant == want, (variant, want)
+        # the ring: deep (4 loads, 6 with three or four row sets) for every xg launch and where a CU holds one block whose waves
+        # have 8 loads or more to make; 8 waves, MB = 2 on the flag-free half
+        deep = xg or (nb <= 256 and _cdiv((k - n_out) // 128, 8) * rs_cap >= 8)
+        assert plan["D"] == ((6 if rs_cap >= 3 else 4) if deep else 2) and (plan["nw"], plan["fl"], plan["mb"]) == (8, 0, 2), (plan, m)
         code = ("X" if xg else "") + str(rs_cap)
         seen.append(code)
-        print(f"[gemv-m] {shape:>3} {kind:>4} n_out={n_out:<3} m={m} variant={variant:<18} rs_cap={rs_cap} blocks={nb}")
+        print(f"[gemv-m] {shape:>3} {kind:>4} n_out={n_out:<3} m={m} variant={variant:<18} rs_cap={rs_cap} D={plan['D']} blocks={nb}")
     assert seen == table[(shape, kind)], (shape, kind, n_out, seen)
     del mods, op, raw
     torch.cuda.empty_cache()

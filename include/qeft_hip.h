@@ -159,6 +159,25 @@ int qeft_gemm_w4_dx_plan(int m, int n, int k, int group_size, int n_out, int bit
 int qeft_grad_oweight_plan(int n, int k, int n_out, const int* overrides, int* out);
 const char* qeft_gemm_tier_name(int tier);
 
+/* What the round-1 decode GEMV launchers behind qeft_gemv_w4 / _qeft / _fused / qeft_gemv_w3 (kind 0, rows), the few-row route of
+ * qeft_gemm_w4 (kind 1, small-M), qeft_gemv_w4_group / qeft_gemv_w3_group (kind 2) and qeft_gemv_w4_silu / qeft_gemv_w3_silu
+ * (kind 3) would do for a shape: host arithmetic only, no GPU needed.  The entries hand a shape the v3 kernel takes to it before
+ * these launchers are asked; the plan is the launcher's alone.  n_parts[nparts]: the layer's n (nparts 1) or the group's parts
+ * (1..3); m: batch rows (kinds 0 and 1; >= 0); bits 4 or 3; flags: 1 x is gathered through reorder_ids (kind 0), 2 the group's
+ * RMSNorm gamma is given (kind 2).  overrides: NULL for the process's environment, else 2 ints in place of it --
+ * QEFT_GEMV_BLOCKS (0 unset) and the ring depth QEFT_GEMV_DEPTH stands for (0 unset, 4 or 6).
+ * out[QEFT_GEMV_W4_PLAN_INTS] = { hipError_t of a refusal (0: planned; 801 not supported, 1 invalid value: the rest is 0),
+ *   variant id (qeft_gemv_w4_variant_name: what qeft_last_variant reports, "" for 0: nothing launched), 1 MFMA / 0 VALU family,
+ *   the template selectors BITS, D, RGI (0: MFMA), OUTL, XG, XT, threads per block, blk_end[0..2] of the last launch,
+ *   then the body launch { count, batch rows, M (1..7 fixed, 16 run-time), blocks, dynamic LDS bytes, rs_cap (0: VALU) } and
+ *   the tail launch likewise (count 0 or 1) }: the m rows go as `count` body launches and then the tail, on consecutive rows.
+ * Return QEFT_OK, QEFT_ERR_NULL without n_parts or out, QEFT_ERR_SHAPE for another kind, bits or nparts (kinds other than 2: 1),
+ * m < 0, a part that is not a positive multiple of 4, k % 64 != 0, group_size < 1 or not dividing k, n_out < 0 or >= k at 4 bits, an overrides depth other than 0, 4 or 6. */
+#define QEFT_GEMV_W4_PLAN_INTS 25
+int qeft_gemv_w4_plan(int kind, int bits, int m, int nparts, const int* n_parts, int k, int group_size, int n_out, int flags,
+                      const int* overrides, int* out);
+const char* qeft_gemv_w4_variant_name(int variant);
+
 /* Dense dequantisation Wdeq[N,K] fp16 (validation / backward helper; the role of the uncompiled
  * dequantize_weight_4bit_qeft, qeft/kernel/quantization_new/dequantize/dequantize_cuda_qeft.cu:38-118).
  * oweight (plain [N, r]) may be NULL. */

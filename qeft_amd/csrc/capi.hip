@@ -9,6 +9,7 @@
 #include "qeft_common.h"
 #include "host_launch.h"
 #include "gemm_w4.h"
+#include "gemv_w4.h"
 #include "gemv_v3.h"
 #include "decode_rows.h"
 #include "decode_kv8.h"
@@ -169,7 +170,7 @@ static int v3_rows(const void* x, const void* qweight, const void* scales, const
     return QEFT_OK;
 }
 
-// The pack of the round-1 GEMV kernels (gemv_w4.hip, gemv_w3.hip): value-initialised, then the operands every site names.
+// The pack of the round-1 GEMV kernels (gemv_w4.hip): value-initialised, then the operands every site names.
 // What differs between the sites -- where x comes from, the outlier slice as ow_il or ow_plain, ids, residual, xt_aux,
 // sz_blk -- each sets by name (profiles/capi_builders_refactor.log lists every field per site).
 // gshift: log2 of a power-of-two group, 31 for one group per row.  0 for any other group: only gemm_impl's small-M branch
@@ -212,11 +213,8 @@ static int gemv_fused_impl(const void* x, const void* qweight, const void* scale
     a.ids = reorder_ids;
     a.residual = (const qeft::f16*)residual;
     a.sz_blk = (const uint32_t*)sz_packed;
-    if (bits == 3) {
-        if (m < 1 || reorder_ids) return QEFT_ERR_SHAPE;   // the gather is the caller's (qlinear.py:275) for w3
-        return finish(qeft::gemv_w3_dispatch(a, m, (hipStream_t)stream));
-    }
-    return finish(qeft::gemv_w4_dispatch(a, m, (hipStream_t)stream));
+    if (bits == 3 && reorder_ids) return QEFT_ERR_SHAPE;   // the gather is the caller's (qlinear.py:275) for w3
+    return finish(qeft::gemv_w4_launch(qeft::kGemvRows, bits, a, m, (hipStream_t)stream));
 }
 
 int qeft_gemv_w4_fused(const void* x, const void* qweight, const void* scales, const void* scaled_zeros,
@@ -270,7 +268,7 @@ static int gemm_impl(const void* x, const void* qweight, const void* scales, con
         // (gemm_4bit semantics with oweight == NULL and a non-zero slice -- dead nibbles -- stays on the GEMM kernel.)
         qeft::GemvArgs a = gemv_args(x, qweight, scales, scaled_zeros, bias, y, n, k, group_size, n_out);
         a.ow_plain = (const qeft::f16*)oweight;      // (any group that is a multiple of 32 gets here: gshift 0 for one that is no power of two)
-        const hipError_t e = qeft::gemv_w4_smallm_dispatch(a, m, (hipStream_t)stream);
+        const hipError_t e = qeft::gemv_w4_launch(qeft::kGemvSmallM, 4, a, m, (hipStream_t)stream);
         if (e == hipSuccess) return QEFT_OK;
         if (e != hipErrorNotSupported) return finish(e);
     }
@@ -451,6 +449,28 @@ int qeft_grad_oweight_plan(int n, int k, int n_out, const int* overrides, int* o
 
 const char* qeft_gemm_tier_name(int tier) { return qeft::gemm_tier_variant(tier); }
 
+int qeft_gemv_w4_plan(int kind, int bits, int m, int nparts, const int* n_parts, int k, int group_size, int n_out, int flags,
+                      const int* overrides, int* out) {
+    if (!n_parts || !out) return QEFT_ERR_NULL;
+    if (kind < qeft::kGemvRows || kind > qeft::kGemvSilu || (bits != 4 && bits != 3) || m < 0 || nparts < 1 ||
+        nparts > (kind == qeft::kGemvGroup ? 3 : 1) || k < 64 || k % 64 != 0 || group_size < 1 || k % group_size != 0 || n_out < 0 ||
+        (bits == 4 && n_out >= k))
+        return QEFT_ERR_SHAPE;
+    for (int p = 0; p < nparts; ++p)
+        if (n_parts[p] < 4 || n_parts[p] % 4 != 0) return QEFT_ERR_SHAPE;
+    if (overrides && overrides[1] != 0 && overrides[1] != 4 && overrides[1] != 6) return QEFT_ERR_SHAPE;      // depths that have instances
+    const qeft::GemvOverrides ov = overrides ? qeft::GemvOverrides{overrides[0], overrides[1]} : qeft::gemv_w4_overrides();
+    const qeft::GemvPlan p = qeft::gemv_w4_plan(kind, bits, m, nparts, n_parts, k, group_size, n_out, (flags & 1) != 0, (flags & 2) != 0, ov);
+    const qeft::GemvLaunch &b = p.body, &t = p.tail;
+    const int v[QEFT_GEMV_W4_PLAN_INTS] = {(int)p.rc, p.variant, p.mfma, p.rc ? 0 : p.bits, p.D, p.rgi, p.outl, p.xg, p.xt, p.threads,
+                                           p.blk_end[0], p.blk_end[1], p.blk_end[2], b.count, b.rows, b.M, b.grid, b.lds, b.rs_cap,
+                                           t.count, t.rows, t.M, t.grid, t.lds, t.rs_cap};
+    memcpy(out, v, sizeof(v));
+    return QEFT_OK;
+}
+
+const char* qeft_gemv_w4_variant_name(int variant) { return qeft::gemv_w4_variant(variant); }
+
 int qeft_dequant_w4(const void* qweight, const void* scales, const void* scaled_zeros, const void* oweight,
                     void* w_out, int n, int k, int group_size, int n_out, qeft_stream_t stream) {
     if (!oweight) n_out = 0;
@@ -508,8 +528,7 @@ static int gemv_group_impl(const void* x, const void* norm_gamma, float norm_eps
     if (norm_gamma && !aligned16(norm_gamma)) return QEFT_ERR_ALIGN;
     g.xt_aux = (const qeft::f16*)norm_gamma;
     g.xt_eps = norm_eps;
-    if (bits == 3) return finish(qeft::gemv_w3_group_dispatch(g, nparts, (hipStream_t)stream));
-    return finish(qeft::gemv_w4_group_dispatch(g, nparts, (hipStream_t)stream));
+    return finish(qeft::gemv_w4_group_launch(bits, g, nparts, (hipStream_t)stream));
 }
 
 int qeft_gemv_w4_group(const void* x, const void* norm_gamma, float norm_eps, int nparts,
@@ -543,8 +562,7 @@ static int gemv_silu_impl(const void* gate, const void* up, const void* qweight,
     a.ow_il = (const qeft::f16*)oweight_il;
     a.residual = (const qeft::f16*)residual;
     a.sz_blk = (const uint32_t*)sz_packed;
-    if (bits == 3) return finish(qeft::gemv_w3_silu_dispatch(a, (hipStream_t)stream));
-    return finish(qeft::gemv_w4_silu_dispatch(a, (hipStream_t)stream));
+    return finish(qeft::gemv_w4_launch(qeft::kGemvSilu, bits, a, 1, (hipStream_t)stream));
 }
 
 int qeft_gemv_w4_silu(const void* gate, const void* up, const void* qweight, const void* scales,

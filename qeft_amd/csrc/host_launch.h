@@ -1,9 +1,10 @@
 // Host-side launchers of the families that have no header of their own, declared once: the file that defines a launcher and
 // every file that calls it include this header, so a definition whose parameters drift from its callers no longer links as an
 // overload of its own.  The other families declare theirs beside their geometry: gemv_v3.h,
-// gemv_v3_dispatch.h, decode_rows.h, decode_kv8.h, prefill_attn.h, attn_train.h, train_glue.h, gemm_w4.h.  Host only.
+// gemv_v3_dispatch.h, decode_rows.h, decode_kv8.h, prefill_attn.h, attn_train.h, train_glue.h, gemm_w4.h, and the round-1 decode
+// GEMV with its plan: gemv_w4.h.  Host only.
 #pragma once
-#include "qeft_common.h"      // GemvArgs, GemvGroupArgs
+#include "qeft_common.h"      // hipError_t, hipStream_t
 
 namespace qeft {
 
@@ -42,16 +43,6 @@ hipError_t verify_sample_launch(const void* logits, const void* tokens, int m, i
 hipError_t token_end_sample_b_launch(const void* logits, const int* slot_tab, void* tok, int* pos_tab, const int* limit, const int* eos,
                                      int* done, void* out, int* ctr, const int* params, int vocab, int out_cap, int n_slots, int m,
                                      hipStream_t st);
-
-// ---- gemv_w4.hip, gemv_w3.hip
-hipError_t gemv_w4_dispatch(const GemvArgs& a, int m, hipStream_t st);
-hipError_t gemv_w4_group_dispatch(GemvGroupArgs g, int nparts, hipStream_t st);
-hipError_t gemv_w4_silu_dispatch(const GemvArgs& a, hipStream_t st);
-hipError_t gemv_w4_smallm_dispatch(const GemvArgs& a, int m, hipStream_t st);
-hipError_t gemv_w3_dispatch(const GemvArgs& a, int m, hipStream_t st);
-hipError_t gemv_w3_group_dispatch(GemvGroupArgs g, int nparts, hipStream_t st);
-hipError_t gemv_w3_silu_dispatch(const GemvArgs& a, hipStream_t st);
-hipError_t expand_w3_launch(const void* q3, void* q4, int N, int K, int n_out, hipStream_t st);
 
 // ---- aux_w4.hip
 hipError_t dequant_w4_launch(const void* qw, const void* scales, const void* zeros, const void* ow, void* out, int N,

@@ -12,7 +12,7 @@ a whole, eager and captured, against a float64 dense pass (tests/dense_ref.py).
     v2_w4      hidden 256, inter 512, g 128, n_out 128          QEFT_ENGINE_V2=1       gemv_mfma_group    gemv_mfma   gemv_mfma_silu
     v2_w3      the same, bits 3                                 QEFT_ENGINE_V2=1       gemv_w3_group      gemv_w3     gemv_w3_silu
 
-(the variants are gemv_w4.hip's and gemv_w3.hip's: mfma_ok() wants n_out % 128 == 0 and a group of 128 or K.)  The first three
+(the variants are gemv_w4.hip's, at both bit widths: mfma_ok() wants n_out % 128 == 0 and a group of 128 or K.)  The first three
 cases are built WITHOUT the environment variable, so that the refusal of the v3 path is the shape's own.
 
 Bounds: own error from fp64 <= 2 x the fp16 torch pass's + one fp16 ulp of the largest logit (the factor is the project's margin

@@ -227,7 +227,13 @@ GEMV = [(3, 24, 384, 0, 128, False, "gemv_valu", "N % 16 != 0"),
         (1, 128, 640, 96, 32, False, "gemv_valu", "group 32, r = 96, K % 128 == 0 yet n_out % 128 != 0"),
         (2, 40, 576, 32, 64, False, "gemv_valu", "K % 128 != 0"),
         (2, 64, 512, 128, 128, True, "gemv_mfma", "a residual keeps the launch off the v3 kernel; mfma_ok holds"),
-        (7, 48, 2048, 0, 2048, True, "gemv_mfma", "per-channel, residual, seven rows")]
+        (7, 48, 2048, 0, 2048, True, "gemv_mfma", "per-channel, residual, seven rows"),
+        # the launch site's selectors no other GPU test reaches (qeft_gemv_w4_plan names them): the deep ring, RGI 4 and 2
+        (1, 24, 6272, 0, 128, False, "gemv_valu", "K > 6144 on the VALU form: ring depth 4"),
+        (1, 16, 6272, 0, 128, True, "gemv_mfma", "K > 6144 on the MFMA form: ring depth 6, one row set"),
+        (1, 4096, 128, 0, 64, False, "gemv_valu", "group 64; 256 blocks of four row-groups: RGI 4"),
+        (1, 2048, 128, 0, 64, False, "gemv_valu", "group 64; 256 blocks of two row-groups: RGI 2"),
+        (7, 40, 576, 32, 64, False, "gemv_valu", "seven rows on the VALU form")]
 
 
 @pytest.mark.parametrize("m,n,k,r,g,residual,want,reason", GEMV, ids=[f"{c[6]}-{c[0]}x{c[1]}x{c[2]}-r{c[3]}-g{c[4]}" for c in GEMV])
@@ -249,13 +255,35 @@ def test_gemv_entry_form(m, n, k, r, g, residual, want, reason):
     _check(y.cpu().numpy(), ref, variant, (m, n, k, r, g))
 
 
+GEMV_GATHER = [(3, 24, 384, 32, 128, "gemv_valu", "N % 16 != 0, n_out = 32: x gathered through reorder_ids on the VALU form")]
+
+
+@pytest.mark.parametrize("m,n,k,r,g,want,reason", GEMV_GATHER, ids=[f"{c[5]}-{c[0]}x{c[1]}x{c[2]}-r{c[3]}-g{c[4]}" for c in GEMV_GATHER])
+def test_gemv_entry_form_with_gather(m, n, k, r, g, want, reason):
+    """The o_proj launch (x through reorder_ids while it is staged) where only the VALU form takes the shape."""
+    from qeft_amd import _lib, qeft_cuda
+    bufs, t, w64 = _layer(n, k, r, g)
+    x = O.make_activation(m, k, r, seed=m)
+    ids = O.sparse_to_dense_ids(np.sort(np.random.default_rng(n).choice(k, size=r, replace=False)), k)
+    y = qeft_cuda.gemv_4bit_fused(torch.from_numpy(x).to(DEV), t["qweight"], t["scales"], t["scaled_zeros"], t["oweight_interleaved"],
+                                  t["bias"], torch.from_numpy(ids.astype(np.int32)).to(DEV), None, m, n, k, g)
+    variant = _lib.last_variant()
+    torch.cuda.synchronize()
+    assert variant == want, (variant, reason)
+    ref = np.take(x, ids, axis=-1).astype(np.float64) @ w64.T + bufs["bias"].astype(np.float64)      # unrounded, as above
+    _check(y.cpu().numpy(), ref, variant, (m, n, k, r, g, "gather"))
+
+
 # grouped (q|k|v, gate|up) and SiLU-staging launches of the decode engine's older GEMV: both forms
 VALU, MFMA = ("gemv_valu_group", "gemv_valu_silu"), ("gemv_mfma_group", "gemv_mfma_silu")
 GROUPED = [((264, 72), 576, 32, 64, VALU, "K % 128 != 0"),
            ((40, 24, 24), 384, 0, 128, VALU, "N % 16 != 0"),
            ((128, 64), 640, 96, 32, VALU, "n_out % 128 != 0, group 32"),
            ((256, 64, 64), 512, 128, 128, MFMA, "three parts, one block per row set"),
-           ((64, 32), 1024, 0, 1024, MFMA, "per-channel, no outlier slice")]
+           ((64, 32), 1024, 0, 1024, MFMA, "per-channel, no outlier slice"),
+           ((24, 24), 6272, 0, 128, VALU, "K > 6144 on the VALU form: ring depth 4"),
+           ((4096, 64), 128, 0, 64, VALU, "group 64; 260 and 256 blocks of four row-groups: RGI 4"),
+           ((2048, 8), 128, 0, 64, VALU, "group 64; 257 and 256 blocks of two row-groups: RGI 2")]
 
 
 def _ptrs(ts):

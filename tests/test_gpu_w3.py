@@ -84,7 +84,8 @@ def test_expand_w3_is_the_4bit_layout_bit_for_bit(n, k, r):
     assert got.dtype == torch.int16 and np.array_equal(got.cpu().numpy(), O.pack_intweight(full))
 
 
-@pytest.mark.parametrize("ns,k", [((512, 256, 256), 512), ((11008, 11008), 4096)])
+@pytest.mark.parametrize("ns,k", [((512, 256, 256), 512), ((11008, 11008), 4096),
+                                  ((32, 16), 6272)])      # K > 6144: the depth-6 instances of both launches (qeft_gemv_w4_plan says so)
 def test_w3_group_norm_and_silu_variants(ns, k):
     from qeft_amd import _lib, qeft_cuda
     lib, r, g = _lib.lib(), 128, 128

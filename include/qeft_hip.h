@@ -788,6 +788,29 @@ int qeft_lm_head_nll_grad(const void* x, int x_stride, const void* weight, const
                           int t, int hidden, int vocab, qeft_stream_t stream);
 long long qeft_lm_head_nll_grad_check_extents(int x_stride, int dx_stride, int t, int hidden, int vocab);
 
+/* Calibration (csrc/calib.hip, csrc/calib.h; qeft_amd/calibrate.py).
+ * qeft_hessian_accum: H <- beta * H + alpha * X^T X.  x fp16 [t][k] row-major, h fp32 [k][k], both 16-byte aligned, k % 64 == 0,
+ *   64 <= k <= 32768, 1 <= t <= 2^24 (QEFT_ERR_SHAPE otherwise).  MFMA on the fp16 operands (their products are exact in fp32),
+ *   fp32 accumulation over the rows in ONE fixed ascending order that depends on neither the grid nor the device; no atomics.
+ *   Epilogue with S the fp32 sum: fl(fl(beta * H[i][j]) + fl(alpha * S)), nothing contracted.  H[i][j] is read for i <= j only
+ *   (not at all with beta == 0: the term is +0) and the result is stored to H[i][j] AND H[j][i]: the triangles agree bit for bit.
+ * qeft_hessian_accum_check_extents: CPU-only -- walks every address a launch forms and returns how many leave x or h, plus the
+ *   elements of h not written exactly once (0 = none; -1 for arguments the entry refuses and for k > 4096: the walk keeps a
+ *   byte per element of h and visits every thread).
+ * qeft_gptq_block: `count` (1..128) columns of the GPTQ error-feedback loop for n rows in one launch, fp32 throughout.
+ *   w1 [n][ld_w] (the block's columns in place inside the working matrix; updated), hinv1 [count][ld_h] (the diagonal block of
+ *   the upper Cholesky factor of the inverse Hessian, in place; the upper triangle is read), scale / zero fp32 [n], maxq 7 or 15,
+ *   q1 / err1 fp32 [n][count] (written).  Per row, for i = 0 .. count - 1, every operation rounded once, nothing contracted,
+ *   IEEE division, rint = round half to even:
+ *     x = w_i / scale;  c = min(max(rint(x) + zero, 0), maxq);  q1_i = scale * (c - zero);  err1_i = (w_i - q1_i) / hinv1[i][i];
+ *     w_j = w_j - fl(err1_i * hinv1[i][j])  for j = i .. count - 1.
+ *   A row's results do not depend on n, the row's index or the grid.  QEFT_ERR_SHAPE: n < 1, count outside 1..128, ld_w or ld_h
+ *   below count, another maxq.  Pointers 4-byte aligned. */
+int qeft_hessian_accum(const void* x, void* h, int t, int k, float alpha, float beta, qeft_stream_t stream);
+long long qeft_hessian_accum_check_extents(int t, int k);
+int qeft_gptq_block(void* w1, int ld_w, const void* hinv1, int ld_h, const void* scale, const void* zero, void* q1, void* err1, int n,
+                    int count, int maxq, qeft_stream_t stream);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py). A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

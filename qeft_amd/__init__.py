@@ -1,6 +1,7 @@
-"""QEFT on AMD: packed QuantLinear, the decode engines, prefill, scoring and the training loss over hand-written gfx950 kernels.
+"""QEFT on AMD: packed QuantLinear, the decode engines, prefill, scoring, the training loss and the per-linear calibration over
+hand-written gfx950 kernels.
 
-The scoring and fine-tuning entry points are exported here; they resolve on first use, so that `import qeft_amd` (and
+The scoring, fine-tuning and calibration entry points are exported here; they resolve on first use, so that `import qeft_amd` (and
 `qeft_amd.build`, which runs before the library exists) stays free of torch and of the HIP library.
 """
 _SCORING = ("score", "eval_nll", "lm_head_nll", "lm_head_nll_loss")
@@ -8,7 +9,8 @@ _FINETUNE = ("causal_lm_loss", "shift_labels", "pack_sequences", "train_step", "
 _ATTENTION = ("causal_attention", "causal_attention_packed")
 _GLUE = ("add_rmsnorm", "swiglu", "rope_qk")
 _OPTIM = ("OWeightAdamW",)
-__all__ = [*_SCORING, *_FINETUNE, *_ATTENTION, *_GLUE, *_OPTIM]
+_CALIBRATE = ("HessianAccumulator", "frob_norm_error", "select_outliers", "gptq_reorder", "calibrate_linear")
+__all__ = [*_SCORING, *_FINETUNE, *_ATTENTION, *_GLUE, *_OPTIM, *_CALIBRATE]
 
 
 def __getattr__(name):
@@ -27,4 +29,7 @@ def __getattr__(name):
     if name in _OPTIM:
         from . import optim
         return getattr(optim, name)
+    if name in _CALIBRATE:
+        from . import calibrate
+        return getattr(calibrate, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libqeft_hip.so")
-SOURCES = ["capi.hip", "gemv_w4.hip", "gemv_v3.hip", "gemv_v3_plain.hip", "gemv_v3_multi.hip", "gemm_w4.hip", "gemm_ws.hip", "aux_w4.hip", "decode_aux.hip", "decode_verify.hip", "decode_batch.hip", "decode_attn_kv8.hip", "decode_verify_kv8.hip", "decode_sample.hip", "prefill_attn.hip", "prefill_attn_kv8.hip", "attn_train.hip", "train_glue.hip", "oweight_optim.hip", "lm_head_nll.hip", "lm_head_nll_grad.hip", "oneshot.hip"]
+SOURCES = ["capi.hip", "gemv_w4.hip", "gemv_v3.hip", "gemv_v3_plain.hip", "gemv_v3_multi.hip", "gemm_w4.hip", "gemm_ws.hip", "aux_w4.hip", "decode_aux.hip", "decode_verify.hip", "decode_batch.hip", "decode_attn_kv8.hip", "decode_verify_kv8.hip", "decode_sample.hip", "prefill_attn.hip", "prefill_attn_kv8.hip", "attn_train.hip", "train_glue.hip", "oweight_optim.hip", "calib.hip", "lm_head_nll.hip", "lm_head_nll_grad.hip", "oneshot.hip"]
 # every header a source may include: an edit to any of them rebuilds (SOURCES stays explicit: a stray .hip must not enter the library)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "qeft_hip.h")]
 ARCH = "gfx950"

@@ -17,6 +17,7 @@
 #include "attn_train.h"
 #include "train_glue.h"
 #include "oweight_optim.h"
+#include "calib.h"
 
 static thread_local int g_last_hip_error = 0;
 thread_local const char* qeft::g_last_variant = "";
@@ -1463,6 +1464,37 @@ int qeft_oweight_adamw(void* p, const void* g, void* m, void* v, long long n, co
         return QEFT_ERR_ALIGN;
     const qeft::OoHyper H{lr, beta1, beta2, eps, weight_decay, max_norm, growth_factor, backoff_factor, growth_interval, dynamic};
     return finish(qeft::oweight_adamw_launch(p, g, m, v, G, state_in, state_out, partials, H, g_oo_nt != 0, (hipStream_t)stream));
+}
+
+// ---- calibration (calib.hip)
+static int ha_geom(qeft::HaGeom& G, int t, int k) {
+    if (t < 1 || t > qeft::HA_MAX_T || k < 64 || k % 64 != 0 || k > qeft::HA_MAX_K) return QEFT_ERR_SHAPE;
+    G = qeft::HaGeom{t, k};
+    return QEFT_OK;
+}
+
+int qeft_hessian_accum(const void* x, void* h, int t, int k, float alpha, float beta, qeft_stream_t stream) {
+    qeft::HaGeom G{};
+    if (int e = ha_geom(G, t, k)) return e;
+    if (!x || !h) return QEFT_ERR_NULL;
+    if (!aligned16(x) || !aligned16(h)) return QEFT_ERR_ALIGN;
+    return finish(qeft::hessian_accum_launch(x, h, G, alpha, beta, (hipStream_t)stream));
+}
+
+long long qeft_hessian_accum_check_extents(int t, int k) {
+    qeft::HaGeom G{};
+    if (ha_geom(G, t, k) != QEFT_OK || k > qeft::HA_MAX_K_ENUM) return -1;
+    return qeft::hessian_accum_count_out_of_range(G);
+}
+
+int qeft_gptq_block(void* w1, int ld_w, const void* hinv1, int ld_h, const void* scale, const void* zero, void* q1, void* err1, int n,
+                    int count, int maxq, qeft_stream_t stream) {
+    if (n < 1 || count < 1 || count > qeft::GB_MAX_COUNT || ld_w < count || ld_h < count || (maxq != 7 && maxq != 15))
+        return QEFT_ERR_SHAPE;
+    if (!w1 || !hinv1 || !scale || !zero || !q1 || !err1) return QEFT_ERR_NULL;
+    if (((uintptr_t)w1 | (uintptr_t)hinv1 | (uintptr_t)scale | (uintptr_t)zero | (uintptr_t)q1 | (uintptr_t)err1) & 3) return QEFT_ERR_ALIGN;
+    const qeft::GbGeom G{n, count, ld_w, ld_h};
+    return finish(qeft::gptq_block_launch(w1, hinv1, scale, zero, q1, err1, G, (float)maxq, (hipStream_t)stream));
 }
 
 // ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)

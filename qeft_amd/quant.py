@@ -1,8 +1,9 @@
 """Host-side quantisation helpers that install and feed QuantLinear (reference qeft/quant.py).
 
-Only the pieces on or next to the hot path are restated: the fake-quant formula (:8-10), the asymmetric
+The pieces on or next to the hot path are restated here: the fake-quant formula (:8-10), the asymmetric
 min-max parameters of `Quantizer.find_params(mse=False)` (:142-158), `make_quant` (:194-214) and `lm_pack`
-(:216-234).  The MSE grid search and the GPTQ/OWQ reconstruction are offline calibration and out of scope.
+(:216-234).  The GPTQ/OWQ reconstruction of one linear, which calls `minmax_params` per 128-column group and whose
+results `lm_pack` consumes, is qeft_amd/calibrate.py; the MSE grid search exists there as a torch restatement only.
 """
 import torch
 import torch.nn as nn

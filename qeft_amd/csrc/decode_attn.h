@@ -33,17 +33,21 @@ __host__ __device__ constexpr size_t attn_ctr_floats(int n_heads) { return ((siz
 
 // Single-token attention for one sequence.  grid = n_heads * S, block = 256 (4 waves), head_dim = 128.
 //   q,k,v  : this token's projections [n_heads*128], [n_kv*128], [n_kv*128] (fp16)
-//   cos/sin: fp32 rotary values; ROW: [64], the row of THIS position, selected by the caller (the engine's form);
-//            !ROW: the whole table [>= max_seq][64], row *pos_ptr is used.  The launcher picks the instantiation (tab_rows == 1)
+//   cos/sin: fp32 rotary values; ROW != 0: [64], the row of THIS position, selected by the caller (the engine's form);
+//            ROW == 0: the whole table [>= max_seq][64], row *pos_ptr is used.  The launcher picks the instantiation (tab_rows == 1)
 //   kc, vc : caches [n_kv][max_seq][128] fp16;  *pos_ptr = index of this token (0-based)
 //   out    : [n_heads*128] fp16, element i stored at out_pos[i] when out_pos is given
 //   ws     : S > 1 only: [attn_ctr_floats(n_heads)] uint32 arrival counters (zero before first use), then [n_heads*S][kAttnRec] floats
 // 32 blocks pulling a whole head's K and V each are bound by what ONE CU can load (~100 KB took ~4 us), so a head is
 // split over S blocks and the kernel is organised around latency:
 //   * requests go out in the order in which their consumers run, because a wave's vector loads retire in order through one
-//     counter: q/k/v and the rotary values first (ROW: before `pos` is back), the output map, then -- `pos` gives the context
-//     length -- the K quarter-rows and V pieces of the first PRE runs of each wave (a run past the context re-reads row 0, so
-//     the count is fixed).  The rotary waits for what is older than that prefetch (vmcnt(PRE * (4 + 4 / DH))), run i's scores
+//     counter: q/k/v and the rotary values first (ROW != 0: before `pos` is back), the output map, then the K quarter-rows and
+//     V pieces of the first PRE runs of each wave.  The first EARLY of those runs do not wait for `pos` either (ROW != 0): their
+//     addresses come from the preloaded arguments alone -- the run's rows if it lies inside the cache, else run 0 -- and `pos`,
+//     a scalar round trip behind the kernel arguments, arrives while they go out; what they fetch at or beyond `pos` is masked
+//     by the selects that already mask the tail of the last run.  Runs EARLY .. PRE - 1 (and all of them in the whole-table
+//     form, whose rotary row needs `pos` first) fetch rows inside the context only; a run past it re-reads row 0, so the count
+//     is fixed.  The rotary waits for what is older than that prefetch (vmcnt(PRE * (4 + 4 / DH))), run i's scores
 //     for the K loads up to run i's, P.V for the V loads; rotary, scores and P.V of the prefetched runs are straight-line
 //     code (values and addresses selected, nothing branched on), so that no wait covers a load its consumer does not read;
 //   * positions are dealt in runs of 16 to the 4*S waves of a head (run r belongs to wave r % (4*S)); each wave
@@ -63,25 +67,33 @@ __device__ __forceinline__ size_t kcache_off(int p, int chunk, int max_seq) {
     return KFT ? ((size_t)chunk * max_seq + p) * 8 : (size_t)p * 128 + chunk * 8;
 }
 
-// Parameter order: what the first loads need comes first -- the leading 13 dwords of the kernel-argument segment are
-// preloaded into SGPRs at wave launch (build flag -amdgpu-kernarg-preload-count), the rest arrives by scalar loads that
-// overlap those first vector loads.  DBG (lab only, tools/attn_timeline.py): per-wave phase stamps.
+// Parameter order: what the loads in front of `pos` need comes first -- the leading 14 dwords of the kernel-argument segment
+// (all that 16 user SGPRs leave behind the segment's own address) are preloaded into SGPRs at wave launch (build flag
+// -amdgpu-kernarg-preload-count): q, k, v, cs, out_pos, kc, the geometry word and n_heads.  The geometry word (rope_attn_geom,
+// below) carries heads per kv head, its shift when a power of two, log2 S and max_seq / 16: the cache stride of a head and the
+// clamp of the early runs need no scalar load, and no division stands ahead of the first load.  vc is the first argument behind
+// them: its scalar load returns while the K requests go out.  ROW: 0 = cs / sn are whole tables; 1 = this position's rows;
+// 2 = this position's rows with sn == cs + 64 (the engine's buffer), which takes both from the preloaded cs.
+// DBG (lab only, tools/attn_timeline.py): per-wave phase stamps.
 // The kernel's BODY is a device function so that the lab's fused attention + o_proj launch can run it too:
 // `bid` = the block's index among the attention blocks, `smem_raw` = its dynamic LDS, and -- S == 1 only -- `pub` != NULL sends
 // every output element to pub[opos] by an agent-scope (write-through) store instead of a plain store to out[opos]: readers on
 // other XCDs of the SAME launch can then be released by a flag (lab only; the product passes NULL).
-template <int PRE, int DH = 1, bool KFT = false, bool DBG = false, bool ALIBI = false, bool ROW = true>
-__device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const int bid, const int* __restrict__ pos_ptr,
-                                                      const int* __restrict__ out_pos, const f16* __restrict__ q,
+template <int PRE, int DH = 1, bool KFT = false, bool DBG = false, bool ALIBI = false, int ROW = 1, int EARLY_ = 0>
+__device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const int bid, const f16* __restrict__ q,
                                                       const f16* __restrict__ k, const f16* __restrict__ v,
-                                                      const float* __restrict__ cs, uint32_t heads_kv_s_tab,
-                                                      const float* __restrict__ sn, f16* __restrict__ kc, f16* __restrict__ vc,
-                                                      f16* __restrict__ out, float* __restrict__ ws, int max_seq,
+                                                      const float* __restrict__ cs, const int* __restrict__ out_pos,
+                                                      f16* __restrict__ kc, uint32_t geom, int n_heads, f16* __restrict__ vc,
+                                                      const float* __restrict__ sn, const int* __restrict__ pos_ptr,
+                                                      f16* __restrict__ out, float* __restrict__ ws,
                                                       unsigned long long* dbg_ptr, const float* __restrict__ alibi,
                                                       f16* __restrict__ pub = nullptr) {
     constexpr int HD = 128;
-    const int n_heads = (int)(heads_kv_s_tab & 0xfffu), n_kv = (int)((heads_kv_s_tab >> 12) & 0xfffu);
-    const int S = (int)((heads_kv_s_tab >> 24) & 0xfu);
+    // prefetched runs requested before `pos` is known; none in the whole-table form, whose rotary row needs `pos` and is requested first
+    constexpr int EARLY = ROW == 0 ? 0 : EARLY_ < PRE ? EARLY_ : PRE;
+    const int grp = (int)(geom & 0xfffu), gsh = (int)((geom >> 12) & 0xfu);
+    const int lgS = DH > 1 ? 0 : (int)((geom >> 16) & 3u), S = 1 << lgS;      // DH > 1 is launched with one split only
+    const int max_seq = (int)((geom >> 18) & 0xfffu) * 16;
     unsigned long long* const dbg = DBG ? dbg_ptr : nullptr;
     unsigned long long stamp[10];
     auto mark = [&](int i) {
@@ -102,15 +114,16 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
     constexpr int NDG = 16 / DH;             // 8-dim groups of this block
     constexpr int NPC = 64 / NDG;            // position classes of a 16-position run
     constexpr int PPC = 16 / NPC;            // positions per class
-    const int dhi = (int)(bid % DH);
-    const int hs_idx = bid / DH;
-    const int h = hs_idx / S, sp = hs_idx % S, t = threadIdx.x, lane = t & 63;
+    // No division stands in front of the first load: DH is a power of two, S = 1 << lgS, and the launcher sends the shift of a
+    // power-of-two group size (gsh - 1; gsh = 0: any other size, divided here).
+    const int dhi = (int)((unsigned)bid % DH);
+    const int hs_idx = (int)((unsigned)bid / DH);
+    const int h = hs_idx >> lgS, sp = hs_idx & (S - 1), t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int gw = sp * 4 + w, NW = 4 * S;   // this wave among the head's waves
-    const int grp = n_heads / n_kv, hk = h / grp;
+    const int hk = gsh ? h >> (gsh - 1) : h / grp;
     f16* kch = kc + (size_t)hk * max_seq * HD;
-    f16* vch = vc + (size_t)hk * max_seq * HD;
-    const bool appender = (sp == 0) && (dhi == 0) && (h % grp == 0);
+    const bool appender = (sp == 0) && (dhi == 0) && (h == hk * grp);
     // ALIBI (the reference's single_query_attention boundary only): the head's linear position bias, slope * (key - query position)
     // added to the scaled score (decoder_masked_multihead_attention_template.hpp:1335-1345, no padding tokens)
     const float slope = ALIBI ? alibi[h] : 0.f;
@@ -126,29 +139,18 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
     // counter of outstanding vector loads retires in order, so the rotary's wait for them then leaves the whole prefetch
     // in flight.  (Loaded behind the prefetch in one form only, they made the compiler drain it -- vmcnt(0) -- in both.)
     float rc, rsn;
-    if constexpr (ROW) {                      // the caller already selected this position's rotary row: no wait for pos
+    if constexpr (ROW != 0) {                 // the caller already selected this position's rotary row: no wait for pos
         rc = cs[t & 63];
-        rsn = sn[t & 63];
+        rsn = ROW == 2 ? cs[64 + (t & 63)] : sn[t & 63];     // 2: the sine row stands behind the cosine row (the engine's buffer)
     }
     // The output map is the one load taken under a (kernel-uniform, scalar) branch, and it stands HERE on purpose: loads
     // whose values are used only behind the `pos` check below are otherwise sunk behind that check -- issued one scalar
     // round trip late -- and a load is not sunk past a join of two paths.
     int opos_raw = 0;
     if (out_pos) opos_raw = out_pos[h * HD + ti];
-    // `pos` is a scalar load: it arrives while the vector loads above are in flight, and nothing above waits for it
-    mark(1);
-    const int pos = *pos_ptr, L = pos + 1;
-    if (pos < 0 || pos >= max_seq) return;   // never index the cache / rotary table out of range (grid-uniform)
-    if (dbg) { asm volatile("" :: "s"(pos)); }
-    if constexpr (!ROW) {                     // the whole table: row pos; `pos` is awaited for the prefetch (L) anyway
-        rc = cs[(size_t)pos * 64 + (t & 63)];
-        rsn = sn[(size_t)pos * 64 + (t & 63)];
-    }
-    mark(2);
-    // ---- K/V of the first PRE runs of this wave.  One CU pulls ~50 GB/s, so only rows inside the context are
-    // fetched; the load COUNT stays fixed (runs past the context re-read row 0, an L1 hit), which keeps the compiler's
-    // vmcnt bookkeeping exact: the rotary waits for q/k/v and the table values only, run i's scores for the K loads up to
-    // run i's, and P.V for the V loads -- all of it straight-line code, so no wait covers a load its consumer does not read.
+    // ---- K/V of the first PRE runs of this wave: PRE * (4 + 4 / DH) loads whatever the context, so that the compiler's vmcnt
+    // bookkeeping is exact: the rotary waits for q/k/v and the table values only, run i's scores for the K loads up to run i's,
+    // and P.V for the V loads -- all of it straight-line code, so no wait covers a load its consumer does not read.
     // score role: position pj of the run, dims qd*8 + 32*j .. +8 (j = 0..3): the 4 lanes of a position read 64
     // contiguous bytes per load instruction
     const int qd = lane & 3, pj = lane >> 2;
@@ -156,20 +158,64 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
     const int dg = lane & (NDG - 1), pc = lane / NDG;
     const int dim0 = dhi * HDB + dg * 8;
     h8 kpre[PRE][4], vpre[PRE][PPC];
-#pragma unroll
-    for (int i = 0; i < PRE; ++i) {
-        const int r0 = (i * NW + gw) * 16;                      // max_seq % 16 == 0: a run never straddles the cache end
-        const int krow = r0 < L ? r0 + pj : 0;
+    // Run i of this wave starts at row r0 = (i * NW + gw) * 16 (max_seq % 16 == 0: a run never straddles the cache end).  The
+    // first EARLY runs are requested WITHOUT `pos`: rows r0 .. r0 + 15 if the run lies inside the cache (r0 < max_seq), else run
+    // 0 -- every such row is inside the allocation whatever `pos` is, and what lies at or beyond `pos` is masked by the selects
+    // of score_run / pv_run below (the tests poison those rows).  Runs EARLY .. PRE - 1 wait for `pos` and fetch rows inside the
+    // context only (a run past it re-reads row 0, an L1 hit).
+    auto k_run = [&](int i, int krow) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) kpre[i][j] = *(const h8*)(kch + kcache_off<KFT>(krow, qd + 4 * j, max_seq));
-    }
-#pragma unroll
-    for (int i = 0; i < PRE; ++i) {
-        const int r0 = (i * NW + gw) * 16;
-        const int vrow = r0 < L ? r0 + pc * PPC : 0;
+    };
+    f16* vch;
+    auto v_run = [&](int i, int vrow) {
         const h8* row = (const h8*)(vch + (size_t)vrow * HD + dim0);
 #pragma unroll
         for (int j = 0; j < PPC; ++j) vpre[i][j] = row[j * (HD / 8)];
+    };
+    auto early_r0 = [&](int i) {
+        const int r0 = (i * NW + gw) * 16;
+        return r0 < max_seq ? r0 : 0;
+    };
+#pragma unroll
+    for (int i = 0; i < EARLY; ++i) k_run(i, early_r0(i) + pj);
+    // vc is the first kernel argument behind the preloaded ones.  Its first use is pinned HERE: behind the early K requests, and
+    // in front of the `pos` check -- left to the compiler, its scalar load is either awaited in front of those requests or sunk
+    // behind the check, where it is one more round trip in series with pos_ptr and `pos` ahead of the rest of the prefetch.
+    if constexpr (EARLY > 0) __builtin_amdgcn_sched_barrier(0);
+    vch = vc + (size_t)hk * max_seq * HD;
+    if constexpr (EARLY > 0) asm volatile("" ::"s"(vch));
+    if constexpr (EARLY == PRE) {             // the whole prefetch is out before `pos` is looked at
+#pragma unroll
+        for (int i = 0; i < EARLY; ++i) v_run(i, early_r0(i) + pc * PPC);
+    }
+    // `pos` is a scalar load: it arrives while the vector loads above are in flight, and nothing above waits for it.  With an
+    // early prefetch it is taken under a kernel-uniform branch for the reason given at the output map: the prefetch's values are
+    // used behind the `pos` check only, and without a join between the two the compiler sinks all its loads behind that check.
+    mark(1);
+    int pos_raw = -1;
+    if (EARLY == 0 || pos_ptr) pos_raw = *pos_ptr;
+    const int pos = pos_raw, L = pos + 1;
+    if (pos < 0 || pos >= max_seq) return;   // never index the cache / rotary table out of range (grid-uniform)
+    if (dbg) { asm volatile("" :: "s"(pos)); }
+    if constexpr (ROW == 0) {                 // the whole table: row pos, requested ahead of the prefetch (EARLY is 0 in this form)
+        rc = cs[(size_t)pos * 64 + (t & 63)];
+        rsn = sn[(size_t)pos * 64 + (t & 63)];
+    }
+    mark(2);
+#pragma unroll
+    for (int i = EARLY; i < PRE; ++i) {
+        const int r0 = (i * NW + gw) * 16;
+        k_run(i, r0 < L ? r0 + pj : 0);
+    }
+    if constexpr (EARLY < PRE) {
+#pragma unroll
+        for (int i = 0; i < EARLY; ++i) v_run(i, early_r0(i) + pc * PPC);
+    }
+#pragma unroll
+    for (int i = EARLY; i < PRE; ++i) {
+        const int r0 = (i * NW + gw) * 16;
+        v_run(i, r0 < L ? r0 + pc * PPC : 0);
     }
     const int opos = out_pos ? opos_raw : h * HD + ti;
     // ---- rotary and staging, one straight line for the four waves: every thread rotates (the v threads' result is not used)
@@ -365,17 +411,28 @@ __device__ __forceinline__ void rope_attn_decode_body(uint8_t* smem_raw, const i
     }
 }
 
-template <int PRE, int DH = 1, bool KFT = false, bool DBG = false, bool ALIBI = false, bool ROW = true>
-__global__ __launch_bounds__(256) void rope_attn_decode_kernel(const int* __restrict__ pos_ptr, const int* __restrict__ out_pos,
-                                                               const f16* __restrict__ q, const f16* __restrict__ k,
+template <int PRE, int DH = 1, bool KFT = false, bool DBG = false, bool ALIBI = false, int ROW = 1, int EARLY = 0>
+__global__ __launch_bounds__(256) void rope_attn_decode_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
                                                                const f16* __restrict__ v, const float* __restrict__ cs,
-                                                               uint32_t heads_kv_s_tab, const float* __restrict__ sn,
-                                                               f16* __restrict__ kc, f16* __restrict__ vc, f16* __restrict__ out,
-                                                               float* __restrict__ ws, int max_seq, unsigned long long* dbg_ptr,
+                                                               const int* __restrict__ out_pos, f16* __restrict__ kc, uint32_t geom,
+                                                               int n_heads, f16* __restrict__ vc, const float* __restrict__ sn,
+                                                               const int* __restrict__ pos_ptr, f16* __restrict__ out,
+                                                               float* __restrict__ ws, unsigned long long* dbg_ptr,
                                                                const float* __restrict__ alibi) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
-    rope_attn_decode_body<PRE, DH, KFT, DBG, ALIBI, ROW>(smem_raw, (int)blockIdx.x, pos_ptr, out_pos, q, k, v, cs, heads_kv_s_tab, sn, kc, vc, out, ws,
-                                                    max_seq, dbg_ptr, alibi);
+    rope_attn_decode_body<PRE, DH, KFT, DBG, ALIBI, ROW, EARLY>(smem_raw, (int)blockIdx.x, q, k, v, cs, out_pos, kc, geom, n_heads, vc, sn,
+                                                                pos_ptr, out, ws, dbg_ptr, alibi);
+}
+
+// The geometry word of the kernel (host side: the launcher).  0 where a field does not fit.
+inline uint32_t rope_attn_geom(int n_heads, int n_kv, int S, int max_seq) {
+    const int grp = n_kv > 0 ? n_heads / n_kv : 0;
+    if (grp < 1 || grp > 4095 || (S != 1 && S != 2 && S != 4 && S != 8) || max_seq < 16 || max_seq % 16 || max_seq > 32768) return 0;
+    uint32_t gsh = 0, lgS = 0;
+    if ((grp & (grp - 1)) == 0)
+        while ((1 << gsh++) != grp) {}
+    while ((1 << lgS) != S) ++lgS;
+    return (uint32_t)grp | (gsh << 12) | (lgS << 16) | ((uint32_t)(max_seq / 16) << 18);
 }
 
 // LDS bytes of the body for a cache of max_seq positions

@@ -366,13 +366,20 @@ unsigned long long* g_attn_dbg = nullptr;   // lab only: per-wave phase stamps
 #ifndef QEFT_ATTN_PRE1
 #define QEFT_ATTN_PRE1 4
 #endif
+// Of those runs (of every instantiation: at most its PRE), how many are requested before `pos` is back (decode_attn.h).  0 is the
+// kernel that waits for `pos` first; A/B like the depth: -DQEFT_ATTN_EARLY=0 / 2 / 4 (profiles/attn_early_prefetch_bench.txt: 2
+// separates from the build before it at contexts 64..128 and 128..256, 4 -- every prefetched row fetched whatever the context,
+// `pos` requested behind all 24 loads -- does not separate from 0).
+#ifndef QEFT_ATTN_EARLY
+#define QEFT_ATTN_EARLY 2
+#endif
 size_t attn_workspace_bytes(int n_heads, int S) { return S > 1 ? (attn_ctr_floats(n_heads) + (size_t)n_heads * S * kAttnRec) * 4 : 0; }
 
 hipError_t rope_attn_decode_launch(const void* q, const void* k, const void* v, const void* cs, const void* sn, void* kc,
                                    void* vc, const int* pos, const int* out_pos, void* out, void* ws, int n_heads,
                                    int n_kv, int max_seq, int S, int tab_rows, hipStream_t st, bool k_ft_layout,
                                    const float* alibi_slopes) {
-    const size_t smem = (size_t)(max_seq + 16) * 4 + 16 * 128 * 4 + 64 * 4 + 4 * 4 + 3 * 128 * 2;
+    const size_t smem = rope_attn_smem_bytes(max_seq);
     // prefetch 256 positions per head whatever the split: PRE runs of 16 on each of the 4*S waves
     int dh = 1;
     auto launch = [&](auto kern) -> hipError_t {
@@ -380,20 +387,25 @@ hipError_t rope_attn_decode_launch(const void* q, const void* k, const void* v, 
             hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
             if (e != hipSuccess) return e;
         }
-        if (n_heads > 4095 || n_kv > 4095 || S > 15) return hipErrorInvalidValue;
-        const uint32_t packed = (uint32_t)n_heads | ((uint32_t)n_kv << 12) | ((uint32_t)S << 24);
-        hipLaunchKernelGGL(kern, dim3(n_heads * S * dh), dim3(256), smem, st, pos, out_pos, (const f16*)q, (const f16*)k,
-                           (const f16*)v, (const float*)cs, packed, (const float*)sn, (f16*)kc, (f16*)vc, (f16*)out, (float*)ws,
-                           max_seq, g_attn_dbg, alibi_slopes);
+        const uint32_t geom = rope_attn_geom(n_heads, n_kv, S, max_seq);
+        if (n_heads > 4095 || !geom || (dh > 1 && S != 1)) return hipErrorInvalidValue;
+        // the leading 14 dwords (q .. n_heads) are what the kernel's first loads and its early prefetch need (decode_attn.h)
+        hipLaunchKernelGGL(kern, dim3(n_heads * S * dh), dim3(256), smem, st, (const f16*)q, (const f16*)k, (const f16*)v,
+                           (const float*)cs, out_pos, (f16*)kc, geom, n_heads, (f16*)vc, (const float*)sn, pos, (f16*)out,
+                           (float*)ws, g_attn_dbg, alibi_slopes);
         return hipGetLastError();
     };
     // measured on the 7B decode step (contexts 64..192): 682 / 689 / 688 tokens/s with 1 / 2 / 4 blocks per head
     static const int dh_env = getenv("QEFT_ATTN_DH") ? atoi(getenv("QEFT_ATTN_DH")) : 2;   // A/B switch: 1, 2 or 4 (4: 797 vs 799 tokens/s)
     // with the K/V prefetch left in flight across the rotary (decode_attn.h): 841 / 851 / 846-850 with 1 / 2 / 4
-    // The rotary-table form is a template parameter (ROW: the caller selected this position's row): either form then has
-    // its table loads in one place ahead of the K/V prefetch (decode_attn.h).
-    const bool row = tab_rows == 1;
-#define QEFT_ATTN_FORM(...) (row ? launch(rope_attn_decode_kernel<__VA_ARGS__, true>) : launch(rope_attn_decode_kernel<__VA_ARGS__, false>))
+    // The rotary-table form is a template parameter: 0 the whole table (row *pos), 1 the caller selected this position's rows,
+    // 2 the same with the sine row directly behind the cosine row (the engine's buffer: one pointer, and that one preloaded).
+    // Either form then has its table loads in one place ahead of the K/V prefetch (decode_attn.h).
+    const int form = tab_rows != 1 ? 0 : (const float*)sn == (const float*)cs + 64 ? 2 : 1;
+#define QEFT_ATTN_FORM(...)                                                          \
+    (form == 2   ? launch(rope_attn_decode_kernel<__VA_ARGS__, 2, QEFT_ATTN_EARLY>)  \
+     : form == 1 ? launch(rope_attn_decode_kernel<__VA_ARGS__, 1, QEFT_ATTN_EARLY>)  \
+                 : launch(rope_attn_decode_kernel<__VA_ARGS__, 0, QEFT_ATTN_EARLY>))
     if (k_ft_layout) {     // the reference's single_query_attention boundary: one block per head
         if (S != 1) return hipErrorInvalidValue;
         if (alibi_slopes) return QEFT_ATTN_FORM(4, 1, true, false, true);

@@ -73,7 +73,7 @@ int main(int argc, char** argv) {
     auto args = [&](int l, bool stamps) {
         AoArgs a{};
         a.pos = pos; a.out_pos = nullptr; a.q = (const f16*)q; a.k = (const f16*)k; a.v = (const f16*)v; a.cs = (const float*)cs; a.sn = (const float*)sn;
-        a.heads_kv_s_tab = (uint32_t)n_heads | ((uint32_t)n_kv << 12) | (1u << 24) | (1u << 28);
+        a.heads_kv_s_tab = rope_attn_geom(n_heads, n_kv, 1, max_seq);
         a.kc = (f16*)kc; a.vc = (f16*)vc; a.max_seq = max_seq; a.n_attn_blocks = n_heads * 2;
         a.qw = (const uint8_t*)qw[l]; a.szp = (const uint8_t*)szp[l]; a.ow = (const uint8_t*)ow[l];
         a.h32 = (float*)h32; a.gamma_out = (const f16*)gamma; a.ynorm = (f16*)ynorm; a.ssq_out = (float*)ssq;
@@ -83,9 +83,9 @@ int main(int argc, char** argv) {
     };
     auto fused = [&](int l) { hipLaunchKernelGGL(kern, dim3(nblk), dim3(AO_NW * 64), smem, 0, args(l, false)); };
     auto attn = [&](int) {
-        hipLaunchKernelGGL((rope_attn_decode_kernel<4, 2>), dim3(n_heads * 2), dim3(256), rope_attn_smem_bytes(max_seq), 0, (const int*)pos, (const int*)nullptr,
-                           (const f16*)q, (const f16*)k, (const f16*)v, (const float*)cs, (uint32_t)n_heads | ((uint32_t)n_kv << 12) | (1u << 24) | (1u << 28),
-                           (const float*)sn, (f16*)kc, (f16*)vc, (f16*)att_out, (float*)nullptr, max_seq, (unsigned long long*)nullptr, (const float*)nullptr);
+        hipLaunchKernelGGL((rope_attn_decode_kernel<4, 2>), dim3(n_heads * 2), dim3(256), rope_attn_smem_bytes(max_seq), 0, (const f16*)q, (const f16*)k,
+                           (const f16*)v, (const float*)cs, (const int*)nullptr, (f16*)kc, rope_attn_geom(n_heads, n_kv, 1, max_seq), n_heads, (f16*)vc,
+                           (const float*)sn, (const int*)pos, (f16*)att_out, (float*)nullptr, (unsigned long long*)nullptr, (const float*)nullptr);
     };
     printf("heads %d  hidden %d  position %d  lds %zu\n", n_heads, hidden, position, smem);
     for (int rep = 0; rep < 3; ++rep) {

@@ -158,8 +158,8 @@ __global__ __launch_bounds__(AO_NW * 64) void attn_oproj_kernel(AoArgs a) {
     AO_STAMP(1);
     if (is_attn && pos_ok) {
         if (wave < 4) {
-            rope_attn_decode_body<PRE, DH>(smem + L.attn, (int)blockIdx.x, a.pos, a.out_pos, a.q, a.k, a.v, a.cs, a.heads_kv_s_tab, a.sn, a.kc,
-                                           a.vc, nullptr, nullptr, a.max_seq, nullptr, nullptr, a.xatt);
+            rope_attn_decode_body<PRE, DH>(smem + L.attn, (int)blockIdx.x, a.q, a.k, a.v, a.cs, a.out_pos, a.kc, a.heads_kv_s_tab,
+                                           a.n_attn_blocks / DH, a.vc, a.sn, a.pos, nullptr, nullptr, nullptr, nullptr, a.xatt);
         } else {
             __builtin_amdgcn_s_barrier();       // the body's two block barriers (rotary staged; partials written)
             __builtin_amdgcn_s_barrier();
@@ -375,7 +375,7 @@ hipError_t attn_oproj_launch(const void* q, const void* k, const void* v, const 
     AoArgs a{};
     a.pos = pos; a.out_pos = out_pos; a.q = (const f16*)q; a.k = (const f16*)k; a.v = (const f16*)v;
     a.cs = (const float*)cs; a.sn = (const float*)sn;
-    a.heads_kv_s_tab = (uint32_t)n_heads | ((uint32_t)n_kv << 12) | (1u << 24);
+    a.heads_kv_s_tab = rope_attn_geom(n_heads, n_kv, 1, max_seq);      // the body's geometry word
     a.kc = (f16*)kc; a.vc = (f16*)vc; a.max_seq = max_seq; a.n_attn_blocks = n_heads * 2;
     a.qw = (const uint8_t*)qweight; a.szp = (const uint8_t*)sz_packed; a.ow = (const uint8_t*)oweight;
     a.h32 = (float*)h32; a.gamma_out = (const f16*)gamma_out; a.ynorm = (f16*)ynorm; a.ssq_out = ssq_out;

@@ -30,11 +30,13 @@ d = d[d[:, 0, 1] > 0]                      # blocks that ran
 rt = (d[..., 1] - d[..., 0]) * 10.0      # ns (100 MHz)
 cyc = (d[..., 9] if S == 1 else d[..., 10]) - d[..., 2]
 print("ns per wave (realtime) mean %.0f  max %.0f ; cycles mean %.0f -> %.2f GHz" % (rt.mean(), rt.max(), cyc.mean(), cyc.mean() / rt.mean()))
-names = ["issue loads", "pos arrives", "rope+append+sync (cos/sin, q/k/v arrive)", "scores (K arrives)", "PV (V arrives)", "sync"] + (["merge+store"] if S == 1 else ["block merge + publish + vmcnt(0) + barrier", "ticket + barrier"])
+# stamp 1 stands behind the loads requested without `pos` (q/k/v, rotary row, output map and the first QEFT_ATTN_EARLY prefetch runs),
+# stamp 2 behind the arrival of `pos`; the prefetch runs that wait for `pos` are requested at the start of the third phase
+names = ["issue loads (+ early prefetch runs)", "pos arrives", "rest of prefetch + rope+append+sync (cos/sin, q/k/v arrive)", "scores (K arrives)", "PV (V arrives)", "sync"] + (["merge+store"] if S == 1 else ["block merge + publish + vmcnt(0) + barrier", "ticket + barrier"])
 ghz = cyc.mean() / rt.mean()
 for i, n in enumerate(names):
     seg = (d[..., 3 + i] - d[..., 2 + i]) / ghz
-    print("%-45s mean %7.0f ns   max %7.0f ns" % (n, seg.mean(), seg.max()))
+    print("%-62s mean %7.0f ns   max %7.0f ns" % (n, seg.mean(), seg.max()))
 span = (d[..., 1].max() - d[..., 0].min()) * 10
 print("first entry -> last exit over the grid: %.0f ns" % span)
 print("entry skew over blocks: %.0f ns" % ((d[..., 0].max() - d[..., 0].min()) * 10))

@@ -805,11 +805,21 @@ long long qeft_lm_head_nll_grad_check_extents(int x_stride, int dx_stride, int t
  *     x = w_i / scale;  c = min(max(rint(x) + zero, 0), maxq);  q1_i = scale * (c - zero);  err1_i = (w_i - q1_i) / hinv1[i][i];
  *     w_j = w_j - fl(err1_i * hinv1[i][j])  for j = i .. count - 1.
  *   A row's results do not depend on n, the row's index or the grid.  QEFT_ERR_SHAPE: n < 1, count outside 1..128, ld_w or ld_h
- *   below count, another maxq.  Pointers 4-byte aligned. */
+ *   below count, another maxq.  Pointers 4-byte aligned.
+ * qeft_mse_search (csrc/calib_mse.hip, csrc/calib_mse.h): the reference's Quantizer.find_params(mse=True) on the asymmetric grid,
+ *   per row of x fp32 [n][g] with row stride ld >= g (read in place): num ranges i = 1 .. num of fl(fl((xmax - xmin) / num) * i)
+ *   times maxq + 1 zero points, scored by sum_j |x_j - q_j|^2.4 in fp32 in ascending j; the first minimum in the order (i, zp)
+ *   ascending wins and scale / zero fp32 [n] receive the pair it leads to.  Every operation but the score is the reference's fp32
+ *   sequence (calib_mse.h), rounded once, nothing contracted, IEEE division, rint = half to even, eps = 1e-8f: each candidate's
+ *   residuals and the returned pair of a winner carry the bits torch gives on the CPU.  The score uses the hardware log2 / exp2
+ *   (exactly 0 for a zero residual), so a runner-up within ~1e-6 relative of the best may win instead.  Non-finite input, and
+ *   scores at or above the reference's initial 1e10, are outside the contract.  A row's result depends on that row alone.
+ *   QEFT_ERR_SHAPE: n < 1, g outside 1..32768, ld < g, maxq other than 7 or 15, num outside 1..40.  Pointers 4-byte aligned. */
 int qeft_hessian_accum(const void* x, void* h, int t, int k, float alpha, float beta, qeft_stream_t stream);
 long long qeft_hessian_accum_check_extents(int t, int k);
 int qeft_gptq_block(void* w1, int ld_w, const void* hinv1, int ld_h, const void* scale, const void* zero, void* q1, void* err1, int n,
                     int count, int maxq, qeft_stream_t stream);
+int qeft_mse_search(const void* x, int ld, int n, int g, int maxq, int num, void* scale, void* zero, qeft_stream_t stream);
 
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py). A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:

@@ -3,13 +3,14 @@ GPTQ_OWQ.add_batch / hessian_sorting / fasterquant_reorder; main.py:130-171 for 
 
     acc = HessianAccumulator(K, device);  acc.add_batch(x) per calibration batch        (qeft_hessian_accum)
     module, info = calibrate_linear(linear, acc.H, n_out, name)                         (qeft_gptq_block per 128 columns)
+    scale, zero = mse_search(x, bits)       the reference's MSE parameter search, what tuning="mse" runs    (qeft_mse_search)
 
-GPU tensors only: the two kernels have no CPU path and no torch fallback.  Around them the reference's own torch expressions
+GPU tensors only: the three kernels have no CPU path and no torch fallback.  Around them the reference's own torch expressions
 remain: dead columns, damping, the three Cholesky calls, the trailing update `W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]` and the
 group parameters, which are computed between launches (group size == block size == 128, so a group starts where a block does).
 
 Out of scope, still: whole-model calibration (layer-by-layer activation capture, the shared outlier index, make_reorder's folding
-of the permutation into norms and embeddings), act_order, sym=True, and a kernel for the MSE parameter search.
+of the permutation into norms and embeddings), act_order and sym=True.
 """
 import types
 
@@ -103,13 +104,39 @@ def mse_params(x, bits=4, num=40, norm=2.4):
     return scale.reshape(-1, 1), zero.reshape(-1, 1)
 
 
+def mse_search(x, bits=4, num=40):
+    """The same search as mse_params in one launch of qeft_mse_search (csrc/calib_mse.hip): x fp32 [N, g] on the GPU, g <= 32768,
+    bits 3 or 4, 1 <= num <= 40; returns (scale, zero) fp32 [N, 1].  A view with stride(1) == 1 is read where it lies (the
+    reorder loop passes columns of its working matrix); anything else is copied first.  No CPU path and no torch fallback.
+
+    Every candidate's residuals x - q, and the pair a winning candidate leads to, are the fp32 bits mse_params gives on the CPU.
+    The score sum |x - q|^2.4 is the kernel's own (hardware log2 / exp2, ascending columns, the sum and not the mean): relative
+    error near 1e-6, so among candidates closer than that another one than torch's may win; exact ties go to the first in the
+    reference's order.  Non-finite input, and scores at or above the reference's initial 1e10, are outside the contract."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError(f"x is {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}: qeft_mse_search reads fp32 [N, g]")
+    if bits not in (3, 4):
+        raise ValueError(f"bits = {bits}: only 3 and 4 are supported")
+    _need_gpu(x, "x")
+    if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    n, g = x.shape
+    scale = torch.empty((n, 1), dtype=torch.float32, device=x.device)
+    zero = torch.empty((n, 1), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().qeft_mse_search(x.data_ptr(), x.stride(0), n, g, 2 ** bits - 1, num, scale.data_ptr(), zero.data_ptr(),
+                                          _stream(x.device)))
+    return scale, zero
+
+
 def _params(x, bits, tuning):
     """(scale, zero) fp32 [N, 1] of ONE group holding every column of x."""
     if tuning == "minmax":
         return minmax_params(x, x.shape[1], bits)
     if tuning == "mse":
+        return mse_search(x, bits)
+    if tuning == "mse_torch":
         return mse_params(x, bits)
-    raise ValueError(f"tuning = {tuning!r}: 'minmax' or 'mse'")
+    raise ValueError(f"tuning = {tuning!r}: 'minmax', 'mse' or 'mse_torch'")
 
 
 def frob_norm_error(W, bits=4, group_size=128, tuning="minmax"):
@@ -152,8 +179,8 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
                    (recon.py:560-563); K - n_out need not be a multiple of 128 -- the last block and group are short
       out_ids (int32), ids, bits, group_size, n_out
       proxy_loss   tr((W - Q) H (W - Q)^T) on the undamped H in fp64, Q the fp32 values before the rounding to fp16
-    tuning: 'minmax' (quant.minmax_params on the block's current columns) or 'mse' (mse_params, the reference's default; ours
-    stays 'minmax' until the search has a kernel).  hinv: the upper Cholesky factor of the inverse damped Hessian in `ids` order,
+    tuning: 'minmax' (quant.minmax_params on the block's current columns), 'mse' (mse_search: the reference's default search in
+    one launch per block) or 'mse_torch' (mse_params, the same search as 640 torch passes: the comparison route).  hinv: the upper Cholesky factor of the inverse damped Hessian in `ids` order,
     for a caller that has one (it replaces the three factorisation calls)."""
     if group_size != BLOCK:
         raise ValueError(f"group_size = {group_size}: only {BLOCK} is supported (a group must start where a block does)")

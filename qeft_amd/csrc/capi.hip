@@ -18,6 +18,7 @@
 #include "train_glue.h"
 #include "oweight_optim.h"
 #include "calib.h"
+#include "calib_mse.h"
 
 static thread_local int g_last_hip_error = 0;
 thread_local const char* qeft::g_last_variant = "";
@@ -1495,6 +1496,15 @@ int qeft_gptq_block(void* w1, int ld_w, const void* hinv1, int ld_h, const void*
     if (((uintptr_t)w1 | (uintptr_t)hinv1 | (uintptr_t)scale | (uintptr_t)zero | (uintptr_t)q1 | (uintptr_t)err1) & 3) return QEFT_ERR_ALIGN;
     const qeft::GbGeom G{n, count, ld_w, ld_h};
     return finish(qeft::gptq_block_launch(w1, hinv1, scale, zero, q1, err1, G, (float)maxq, (hipStream_t)stream));
+}
+
+int qeft_mse_search(const void* x, int ld, int n, int g, int maxq, int num, void* scale, void* zero, qeft_stream_t stream) {
+    if (n < 1 || g < 1 || g > qeft::MS_MAX_G || ld < g || (maxq != 7 && maxq != 15) || num < 1 || num > qeft::MS_MAX_NUM)
+        return QEFT_ERR_SHAPE;
+    if (!x || !scale || !zero) return QEFT_ERR_NULL;
+    if (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)zero) & 3) return QEFT_ERR_ALIGN;
+    const qeft::MsGeom G{n, g, ld, maxq == 15 ? 4 : 3, num};
+    return finish(qeft::mse_search_launch(x, scale, zero, G, (hipStream_t)stream));
 }
 
 // ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)

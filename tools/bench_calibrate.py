@@ -12,6 +12,10 @@ of every side before any measurement, the sides alternating (medians of --reps r
                  reference's own expressions, one python iteration per column -- at N x K = 4096 x 4096, 11008 x 4096 and
                  4096 x 11008 with 128 outlier columns; then the own side's parts, each timed alone over the same tensors:
                  the factorisation (damping + three Cholesky calls), the block launches, the trailing GEMMs, the parameter search
+  --only-mse     (> profiles/calib_mse_bench.json.log) the MSE parameter search: mse_search (one launch of qeft_mse_search)
+                 against calibrate.mse_params (640 torch passes) at [4096, 128], [11008, 128] and [4096, 4096] (the whole-row
+                 search of frob_norm_error), with the rows on which the two return another pair; then the 4096 x 4096
+                 reconstruction with tuning = "minmax", "mse" and "mse_torch", the three sides alternating
 One JSON line per part; no threshold.  Every part runs under its own time limit."""
 import argparse
 import faulthandler
@@ -158,13 +162,74 @@ def recon_bench(n, k, r, reps):
     print(json.dumps(res), flush=True)
 
 
+def mse_search_bench(n, g, reps):
+    """The search alone: one launch of qeft_mse_search against calibrate.mse_params (640 torch passes) on the same rows."""
+    from qeft_amd.calibrate import mse_params, mse_search
+    gen = torch.Generator(device=DEV).manual_seed(4)
+    x = (torch.randn(n, g, generator=gen, device=DEV) * 0.02).half().float()
+    out = {}
+
+    def own():
+        out["own"] = mse_search(x, 4)
+
+    def ref():
+        out["ref"] = mse_params(x, 4)
+
+    us, spread = medians_ms([own, ref], reps)
+    differ = ((out["own"][0] != out["ref"][0]) | (out["own"][1] != out["ref"][1])).sum().item()
+    res = dict(bench="calibrate", op="mse_search", n=n, g=g, bits=4, reps=reps, own_ms=round(us[0], 4),
+               own_ms_min_max=[round(v, 4) for v in spread[0]], torch_ms=round(us[1], 2),
+               torch_ms_min_max=[round(v, 2) for v in spread[1]], own_over_torch=round(us[0] / us[1], 6),
+               candidate_elements_per_s=round(n * g * 640.0 / (us[0] * 1e-3), 0), rows_with_another_pair=differ)
+    print(json.dumps(res), flush=True)
+
+
+def mse_recon_bench(n, k, r, reps):
+    """One reconstruction with each parameter search: min-max, the search kernel, the torch search."""
+    import calib_ref as R
+    from qeft_amd.calibrate import HessianAccumulator, gptq_reorder
+    g = torch.Generator(device=DEV).manual_seed(2)
+    W = (torch.randn(n, k, generator=g, device=DEV) * 0.02).half()
+    acc = HessianAccumulator(k, DEV)
+    acc.add_batch(rows(2048, k, 3))
+    H = acc.H
+    ids = torch.arange(k, device=DEV)
+    tunings = ("minmax", "mse", "mse_torch")
+    out = {}
+
+    def side(tuning):
+        def run():
+            out[tuning] = gptq_reorder(W, H, ids, r, tuning=tuning)
+        return run
+
+    us, spread = medians_ms([side(t) for t in tunings], reps)
+    Wf = W.float()
+    res = dict(bench="calibrate", op="reconstruction_by_tuning", n=n, k=k, n_out=r, reps=reps, blocks=(k - r + 127) // 128)
+    for t, ms, sp in zip(tunings, us, spread):
+        res[f"{t}_ms"] = round(ms, 2)
+        res[f"{t}_ms_min_max"] = [round(v, 2) for v in sp]
+        res[f"proxy_loss_{t}"] = out[t].proxy_loss
+    res["mse_over_mse_torch"] = round(us[1] / us[2], 5)
+    res["mse_over_minmax"] = round(us[1] / us[0], 4)
+    res["proxy_loss_rtn"] = R.proxy_loss(Wf, R.rtn(Wf, k - r), H)
+    print(json.dumps(res), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--small", action="store_true", help="toy sizes: a rehearsal of the script, not a measurement")
     ap.add_argument("--only-add-batch", action="store_true")
+    ap.add_argument("--only-mse", action="store_true", help="the MSE search parts alone (profiles/calib_mse_bench.json.log)")
     a = ap.parse_args()
     print(json.dumps(dict(bench="calibrate", device=torch.cuda.get_device_name(0), torch=torch.__version__)), flush=True)
+    if a.only_mse:
+        for n, g in ([(67, 129)] if a.small else [(4096, 128), (11008, 128), (4096, 4096)]):
+            with limit(240):
+                mse_search_bench(n, g, a.reps)
+        with limit(400):
+            mse_recon_bench(*((64, 384) if a.small else (4096, 4096)), 128, a.reps)
+        sys.exit(0)
     for t, k, inner in ([(128, 256, 8)] if a.small else [(2048, 4096, 1000), (2048, 11008, 200)]):
         with limit(240):
             add_batch_bench(t, k, a.reps, inner)

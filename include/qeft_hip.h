@@ -821,6 +821,24 @@ int qeft_gptq_block(void* w1, int ld_w, const void* hinv1, int ld_h, const void*
                     int count, int maxq, qeft_stream_t stream);
 int qeft_mse_search(const void* x, int ld, int n, int g, int maxq, int num, void* scale, void* zero, qeft_stream_t stream);
 
+/* The factor of the inverse Hessian the error-feedback loop runs on (csrc/calib_factor.hip, csrc/calib_factor.h;
+ * qeft_amd/calibrate.py: hinv_factor, gptq_reorder(factor="own")).
+ * a: fp32 [k][k], rows ld elements apart, symmetric positive definite -- the permuted, dead-column-fixed, damped Hessian; only
+ *   its upper triangle is read, and the entry DESTROYS it (V of a = V V^T overwrites the upper block triangle).
+ * u: fp32 [k][k] contiguous, written in full: the upper triangle holds U with a^-1 = U^T U, the strict lower triangle exact
+ *   zeros, the diagonal positive -- what cholesky(cholesky_inverse(cholesky(a)), upper=True) returns, from one factorisation
+ *   (a = V V^T, V upper-triangular, from the bottom-right corner up) and one triangular inverse (U = V^-1); no k x k inverse
+ *   is formed.  fp32 throughout, no atomics, every sum in one fixed order: the same input gives the same bits on every run.
+ * info: one int32 in device memory, written by the entry (it needs no initialisation): 0 = success, otherwise 1 + the index of
+ *   the first column, in the order of the sweep (block columns descending, columns descending inside a block), whose pivot was
+ *   not a positive finite number; u is unspecified then, and every access still stays inside the operands.
+ * 128-column blocks, ordered by kernel boundaries alone: qeft_hinv_factor_launches(k) = 3 k / 128 - 1 launches (1 at k == 128;
+ *   0 for a k the entry refuses).  No workspace, no host synchronisation.
+ * QEFT_ERR_SHAPE: k < 128, k % 128 != 0, k > 32768, ld < k, ld % 4 != 0 -- before any pointer is looked at; then QEFT_ERR_NULL
+ *   (a, u, info required, a != u), then QEFT_ERR_ALIGN (a, u 16-byte aligned, info 4-byte aligned). */
+int qeft_hinv_factor_launches(int k);
+int qeft_hinv_factor(void* a, int ld, void* u, int* info, int k, qeft_stream_t stream);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py). A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

@@ -5,8 +5,10 @@ GPTQ_OWQ.add_batch / hessian_sorting / fasterquant_reorder; main.py:130-171 for 
     module, info = calibrate_linear(linear, acc.H, n_out, name)                         (qeft_gptq_block per 128 columns)
     scale, zero = mse_search(x, bits)       the reference's MSE parameter search, what tuning="mse" runs    (qeft_mse_search)
 
-GPU tensors only: the three kernels have no CPU path and no torch fallback.  Around them the reference's own torch expressions
-remain: dead columns, damping, the three Cholesky calls, the trailing update `W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]` and the
+    U = hinv_factor(Hd)                     the upper factor of Hd^-1 the loop runs on, what factor="own" calls    (qeft_hinv_factor)
+
+GPU tensors only: the kernels have no CPU path and no torch fallback.  Around them the reference's own torch expressions
+remain: dead columns, damping, the three Cholesky calls (factor="torch", the default), the trailing update `W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]` and the
 group parameters, which are computed between launches (group size == block size == 128, so a group starts where a block does).
 
 Out of scope, still: whole-model calibration (layer-by-layer activation capture, the shared outlier index, make_reorder's folding
@@ -168,7 +170,33 @@ def select_outliers(H, n_out, frob_norm=None, outidx=None):
     return out_ids, sparse_to_dense_ids(out_ids, K)
 
 
-def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning="minmax", hinv=None, sym=False):
+def hinv_factor(Hd):
+    """The upper-triangular U with Hd^-1 = U^T U -- what cholesky(cholesky_inverse(cholesky(Hd)), upper=True) returns -- by
+    qeft_hinv_factor (csrc/calib_factor.hip): ONE blocked factorisation Hd = V V^T from the bottom-right
+    corner up and the triangular inverse U = V^-1 riding on the same sweep, 3 K / 128 - 1 launches, fp32, bit-reproducible.
+    Hd fp32 [K, K] on the GPU, symmetric positive definite (already permuted and damped), K % 128 == 0; it is not modified (the
+    entry works on a copy).  No CPU path and no torch fallback.  Reads the status once (one synchronisation, as the torch route
+    has) and raises torch.linalg.LinAlgError naming the column whose pivot was not positive (its .info holds the entry's status)."""
+    if not isinstance(Hd, torch.Tensor) or Hd.dtype != torch.float32 or Hd.dim() != 2 or Hd.shape[0] != Hd.shape[1]:
+        raise ValueError(f"Hd is {getattr(Hd, 'dtype', type(Hd))} {tuple(getattr(Hd, 'shape', ()))}: qeft_hinv_factor reads fp32 [K, K]")
+    K = Hd.shape[0]
+    if K < BLOCK or K % BLOCK != 0:
+        raise ValueError(f"K = {K}: qeft_hinv_factor needs a multiple of {BLOCK}")
+    _need_gpu(Hd, "Hd")
+    a = Hd.clone(memory_format=torch.contiguous_format)             # the entry destroys its input
+    u = torch.empty_like(a)
+    info = torch.empty(1, dtype=torch.int32, device=Hd.device)
+    _lib.check(_lib.lib().qeft_hinv_factor(a.data_ptr(), K, u.data_ptr(), info.data_ptr(), K, _stream(Hd.device)))
+    code = info.item()
+    if code != 0:
+        err = torch.linalg.LinAlgError(f"hinv_factor: the pivot of column {code - 1} is not a positive finite number "
+                                       f"(info = {code}): the matrix is not positive definite")
+        err.info = code
+        raise err
+    return u
+
+
+def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning="minmax", hinv=None, sym=False, factor="torch"):
     """The reference's fasterquant_reorder (recon.py:488-573) of one weight matrix on the GPU, 128 columns per launch.
 
     W [N, K] (any float dtype), H fp32 [K, K] as accumulated, ids the column order (select_outliers), the last n_out columns of
@@ -181,7 +209,8 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
       proxy_loss   tr((W - Q) H (W - Q)^T) on the undamped H in fp64, Q the fp32 values before the rounding to fp16
     tuning: 'minmax' (quant.minmax_params on the block's current columns), 'mse' (mse_search: the reference's default search in
     one launch per block) or 'mse_torch' (mse_params, the same search as 640 torch passes: the comparison route).  hinv: the upper Cholesky factor of the inverse damped Hessian in `ids` order,
-    for a caller that has one (it replaces the three factorisation calls)."""
+    for a caller that has one (it replaces the factorisation).  factor: how that matrix is computed otherwise -- 'torch' (the
+    reference's three Cholesky calls) or 'own' (hinv_factor: one blocked factorisation in HIP)."""
     if group_size != BLOCK:
         raise ValueError(f"group_size = {group_size}: only {BLOCK} is supported (a group must start where a block does)")
     if sym:
@@ -193,6 +222,8 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
     N, K = W.shape
     if K % BLOCK != 0:
         raise ValueError(f"K = {K}: must be a multiple of {BLOCK} (scale_group / zero_group hold K / {BLOCK} groups)")
+    if factor not in ("torch", "own"):
+        raise ValueError(f"factor = {factor!r}: 'torch' or 'own'")
     _need_gpu(W, "W")
     _need_gpu(H, "H")
     if H.shape != (K, K) or not 0 <= n_out < K:
@@ -213,9 +244,12 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
         damp = percdamp * torch.mean(torch.diag(Hp))
         diag = torch.arange(K, device=dev)
         Hp[diag, diag] += damp
-        Hp = torch.linalg.cholesky(Hp)
-        Hp = torch.cholesky_inverse(Hp)
-        hinv = torch.linalg.cholesky(Hp, upper=True)
+        if factor == "own":
+            hinv = hinv_factor(Hp)
+        else:
+            Hp = torch.linalg.cholesky(Hp)
+            Hp = torch.cholesky_inverse(Hp)
+            hinv = torch.linalg.cholesky(Hp, upper=True)
     hinv = hinv.to(device=dev, dtype=torch.float32).contiguous()
     if hinv.shape != (K, K):
         raise ValueError(f"hinv {tuple(hinv.shape)}: want [{K}, {K}]")
@@ -254,7 +288,7 @@ def calibrate_linear(linear, H, n_out, name, bits=4, group_size=128, frob_norm=T
 
     frob_norm: True = weigh diag(H) by frob_norm_error(W) as the reference does by default, False/None = diag(H) alone, or the
     tensor to use.  outidx: fixed outlier columns instead of a selection.  Other keywords go to gptq_reorder (percdamp, tuning,
-    hinv).  The quantinfo namespace carries what checkpoint.save_packed / quant.lm_pack read (bits, sym, group_size, n_out,
+    hinv, factor).  The quantinfo namespace carries what checkpoint.save_packed / quant.lm_pack read (bits, sym, group_size, n_out,
     reorder, scale_group, zero_group, out_ids) plus ids and proxy_loss, so the layer saves and loads like any other.
 
     The packed columns are in `ids` order.  A module whose name contains 'o_proj' or 'out_proj' gathers its own input

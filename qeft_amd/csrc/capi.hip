@@ -19,6 +19,7 @@
 #include "oweight_optim.h"
 #include "calib.h"
 #include "calib_mse.h"
+#include "calib_factor.h"
 
 static thread_local int g_last_hip_error = 0;
 thread_local const char* qeft::g_last_variant = "";
@@ -1505,6 +1506,18 @@ int qeft_mse_search(const void* x, int ld, int n, int g, int maxq, int num, void
     if (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)zero) & 3) return QEFT_ERR_ALIGN;
     const qeft::MsGeom G{n, g, ld, maxq == 15 ? 4 : 3, num};
     return finish(qeft::mse_search_launch(x, scale, zero, G, (hipStream_t)stream));
+}
+
+// ---- the factor of the inverse Hessian (calib_factor.hip)
+static bool hf_shape_ok(int k, int ld) { return k >= qeft::HF_B && k % qeft::HF_B == 0 && k <= qeft::HF_MAX_K && ld >= k && ld % 4 == 0; }
+
+int qeft_hinv_factor_launches(int k) { return hf_shape_ok(k, k) ? qeft::hf_launches(qeft::HfGeom{k, k}) : 0; }
+
+int qeft_hinv_factor(void* a, int ld, void* u, int* info, int k, qeft_stream_t stream) {
+    if (!hf_shape_ok(k, ld)) return QEFT_ERR_SHAPE;
+    if (!a || !u || !info || a == u) return QEFT_ERR_NULL;
+    if (!aligned16(a) || !aligned16(u) || ((uintptr_t)info & 3)) return QEFT_ERR_ALIGN;
+    return finish(qeft::hinv_factor_launch(a, u, info, qeft::HfGeom{k, ld}, (hipStream_t)stream));
 }
 
 // ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)

@@ -16,6 +16,9 @@ of every side before any measurement, the sides alternating (medians of --reps r
                  against calibrate.mse_params (640 torch passes) at [4096, 128], [11008, 128] and [4096, 4096] (the whole-row
                  search of frob_norm_error), with the rows on which the two return another pair; then the 4096 x 4096
                  reconstruction with tuning = "minmax", "mse" and "mse_torch", the three sides alternating
+  --only-factor  (> profiles/calib_factor_bench.json.log) the factor of the inverse Hessian at K = 4096 and 11008: the three torch
+                 calls against hinv_factor (qeft_hinv_factor, 3 K / 128 - 1 launches) on the same damped matrix, then a whole
+                 4096 x K reconstruction with factor = "torch" and factor = "own" 
 One JSON line per part; no threshold.  Every part runs under its own time limit."""
 import argparse
 import faulthandler
@@ -215,14 +218,62 @@ def mse_recon_bench(n, k, r, reps):
     print(json.dumps(res), flush=True)
 
 
+def factor_bench(n, k, r, reps):
+    """The factor of the inverse Hessian alone (the three torch calls against hinv_factor on the same damped matrix), then one
+    n x k reconstruction with factor = "torch" and "own", the sides alternating."""
+    from qeft_amd import _lib
+    from qeft_amd.calibrate import HessianAccumulator, gptq_reorder, hinv_factor
+    g = torch.Generator(device=DEV).manual_seed(2)
+    W = (torch.randn(n, k, generator=g, device=DEV) * 0.02).half()
+    acc = HessianAccumulator(k, DEV)
+    acc.add_batch(rows(2048, k, 3))
+    H = acc.H
+    Hd = H.clone()
+    Hd.diagonal().add_(0.01 * torch.mean(torch.diag(H)))
+    ids = torch.arange(k, device=DEV)
+    out = {}
+
+    def three_calls():
+        out["torch"] = torch.linalg.cholesky(torch.cholesky_inverse(torch.linalg.cholesky(Hd)), upper=True)
+
+    def own():
+        out["own"] = hinv_factor(Hd)
+
+    us, spread = medians_ms([three_calls, own], reps)
+    diff = ((out["own"] - out["torch"]).norm() / out["torch"].norm()).item()
+    del out["torch"], out["own"]
+
+    def side(factor):
+        def run():
+            out[factor] = gptq_reorder(W, H, ids, r, factor=factor).proxy_loss
+        return run
+
+    rec, rspread = medians_ms([side("torch"), side("own")], reps)
+    res = dict(bench="calibrate", op="hinv_factor", k=k, n=n, n_out=r, reps=reps, launches=_lib.lib().qeft_hinv_factor_launches(k),
+               factor_torch_ms=round(us[0], 3), factor_torch_ms_min_max=[round(v, 3) for v in spread[0]],
+               factor_own_ms=round(us[1], 3), factor_own_ms_min_max=[round(v, 3) for v in spread[1]],
+               factor_own_over_torch=round(us[1] / us[0], 4), own_useful_tflops=round(2.0 / 3.0 * k ** 3 / (us[1] * 1e-3) / 1e12, 2),
+               factor_own_vs_torch_frobenius=diff,
+               reconstruction_torch_ms=round(rec[0], 2), reconstruction_torch_ms_min_max=[round(v, 2) for v in rspread[0]],
+               reconstruction_own_ms=round(rec[1], 2), reconstruction_own_ms_min_max=[round(v, 2) for v in rspread[1]],
+               reconstruction_own_over_torch=round(rec[1] / rec[0], 4), proxy_loss_torch=out["torch"], proxy_loss_own=out["own"])
+    print(json.dumps(res), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--small", action="store_true", help="toy sizes: a rehearsal of the script, not a measurement")
     ap.add_argument("--only-add-batch", action="store_true")
     ap.add_argument("--only-mse", action="store_true", help="the MSE search parts alone (profiles/calib_mse_bench.json.log)")
+    ap.add_argument("--only-factor", action="store_true", help="the inverse-Hessian factor alone (profiles/calib_factor_bench.json.log)")
     a = ap.parse_args()
     print(json.dumps(dict(bench="calibrate", device=torch.cuda.get_device_name(0), torch=torch.__version__)), flush=True)
+    if a.only_factor:
+        for n, k in ([(64, 384)] if a.small else [(4096, 4096), (4096, 11008)]):
+            with limit(400):
+                factor_bench(n, k, 128, a.reps)
+        sys.exit(0)
     if a.only_mse:
         for n, g in ([(67, 129)] if a.small else [(4096, 128), (11008, 128), (4096, 4096)]):
             with limit(240):

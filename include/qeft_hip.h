@@ -839,6 +839,31 @@ int qeft_mse_search(const void* x, int ld, int n, int g, int maxq, int num, void
 int qeft_hinv_factor_launches(int k);
 int qeft_hinv_factor(void* a, int ld, void* u, int* info, int k, qeft_stream_t stream);
 
+/* Quantise and pack a weight matrix on the device, one launch (csrc/quant_pack.hip, csrc/quant_pack.h; qeft_cuda.quant_pack,
+ * QuantLinear.pack_device, calibrate.rtn_linear).  The spec is QuantLinear.pack in qeft_amd/qlinear.py.
+ * w: fp16 [n][k], rows ld_w elements apart.  col_ids: int32 [k] or NULL; with it column j of the operand is w[.][col_ids[j]]
+ *   (an index outside 0 .. k - 1 is clamped into the row, never followed).  The last n_out columns of the operand are the fp16
+ *   outlier columns: not quantised here.
+ * scale_in, zero_in: fp32 [n][k / 128], both or neither.
+ *   Given: code = clamp(rint((float(w) + fl(z s)) / s), 0, maxq) -- the host pack's sequence in fp32, IEEE division.  The host
+ *     does NOT clamp (a code outside 0..maxq spills into the neighbouring nibbles there); the device does, so the two differ only
+ *     where the host's result is already corrupt.
+ *   Neither (round to nearest): per row and group, over the group's live columns, quant.minmax_params -- xmin = min(min, 0),
+ *     xmax = max(max, 0), (-1, 1) for an all-zero group, s = (xmax - xmin) / maxq, z = rint(-xmin / s) -- then
+ *     code = clamp(rint(x / s) + z, 0, maxq).  A group without a live column repeats the last live group's pair.
+ * qweight: bits == 4: int16 [n / 4][k], the checkpoint layout, the nibbles of the last n_out columns holding their group's z;
+ *   bits == 3: int32 [n / 16][(k - n_out) / 128 * 192], the extension layout.  scales, scaled_zeros: fp16 [k / 128][n], s and
+ *   -(z s) rounded once.  scale_out, zero_out: fp32 [n][k / 128] or NULL, the pair used.  Every output is written in full.
+ * No workspace, no atomics, no host synchronisation; the same input gives the same bits on every run.
+ * QEFT_ERR_SHAPE first: bits other than 3 or 4, n < 16, n % 16 != 0, k < 128, k % 128 != 0, n or k above 2^20, ld_w < k, ld_w % 8
+ *   != 0 without col_ids (the rows are then read 16 bytes at a time), n_out negative, odd or >= k, bits == 3 with n_out % 128
+ *   != 0; then QEFT_ERR_GROUP for a group_size other than 128; then QEFT_ERR_NULL (w, qweight, scales, scaled_zeros required;
+ *   scale_in without zero_in or the reverse); then QEFT_ERR_ALIGN (qweight and, without col_ids, w 16-byte aligned; otherwise
+ *   w and the fp16 outputs 2-byte, every fp32 / int32 operand 4-byte). */
+int qeft_quant_pack(const void* w, int ld_w, const void* col_ids, const void* scale_in, const void* zero_in, void* qweight,
+                    void* scales, void* scaled_zeros, void* scale_out, void* zero_out, int n, int k, int n_out, int bits,
+                    int group_size, qeft_stream_t stream);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py). A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

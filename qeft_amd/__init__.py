@@ -9,7 +9,7 @@ _FINETUNE = ("causal_lm_loss", "shift_labels", "pack_sequences", "train_step", "
 _ATTENTION = ("causal_attention", "causal_attention_packed")
 _GLUE = ("add_rmsnorm", "swiglu", "rope_qk")
 _OPTIM = ("OWeightAdamW",)
-_CALIBRATE = ("HessianAccumulator", "frob_norm_error", "select_outliers", "gptq_reorder", "calibrate_linear", "mse_search", "hinv_factor")
+_CALIBRATE = ("HessianAccumulator", "frob_norm_error", "select_outliers", "gptq_reorder", "calibrate_linear", "mse_search", "hinv_factor", "rtn_linear")
 __all__ = [*_SCORING, *_FINETUNE, *_ATTENTION, *_GLUE, *_OPTIM, *_CALIBRATE]
 
 

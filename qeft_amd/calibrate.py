@@ -6,6 +6,8 @@ GPTQ_OWQ.add_batch / hessian_sorting / fasterquant_reorder; main.py:130-171 for 
     scale, zero = mse_search(x, bits)       the reference's MSE parameter search, what tuning="mse" runs    (qeft_mse_search)
 
     U = hinv_factor(Hd)                     the upper factor of Hd^-1 the loop runs on, what factor="own" calls    (qeft_hinv_factor)
+    module, info = calibrate_linear(..., pack="device")     the packing step on the GPU as well, DESIGN.md section 4.22  (qeft_quant_pack)
+    module, info = rtn_linear(linear, n_out, name, H)       round to nearest, the reference's --nearest / --nearest_owq  (qeft_quant_pack)
 
 GPU tensors only: the kernels have no CPU path and no torch fallback.  Around them the reference's own torch expressions
 remain: dead columns, damping, the three Cholesky calls (factor="torch", the default), the trailing update `W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]` and the
@@ -282,7 +284,7 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
                                  proxy_loss=proxy_loss)
 
 
-def calibrate_linear(linear, H, n_out, name, bits=4, group_size=128, frob_norm=True, outidx=None, **kw):
+def calibrate_linear(linear, H, n_out, name, bits=4, group_size=128, frob_norm=True, outidx=None, pack="host", **kw):
     """One fp16 nn.Linear + its accumulated Hessian -> (QuantLinear, quantinfo): select_outliers -> gptq_reorder ->
     QuantLinear.pack(outlieridx=out_ids, scales=scale_group, zeros=zero_group) -> set_kernel().
 
@@ -293,7 +295,13 @@ def calibrate_linear(linear, H, n_out, name, bits=4, group_size=128, frob_norm=T
 
     The packed columns are in `ids` order.  A module whose name contains 'o_proj' or 'out_proj' gathers its own input
     (set_kernel installs reorder_ids == ids); for any other name the caller feeds x[..., ids] until the offline global reordering
-    exists.  n_out = 0 is plain GPTQ: nothing is selected and ids is the identity."""
+    exists.  n_out = 0 is plain GPTQ: nothing is selected and ids is the identity.
+
+    pack: "host" (the default) copies the reconstruction to the CPU, runs QuantLinear.pack there and copies the module back;
+    "device" runs QuantLinear.pack_device (one launch of qeft_quant_pack): the same buffers bit for bit,
+    and no tensor leaves the GPU."""
+    if pack not in ("host", "device"):
+        raise ValueError(f"pack = {pack!r}: 'host' or 'device'")
     W = linear.weight.data
     _need_gpu(W, "linear.weight")
     _need_gpu(H, "H")
@@ -309,13 +317,66 @@ def calibrate_linear(linear, H, n_out, name, bits=4, group_size=128, frob_norm=T
     res = gptq_reorder(W, H, ids, n_out, bits=bits, group_size=group_size, **kw)
     N, K = W.shape
     module = QuantLinear(bits, K, N, linear.bias is not None, torch.float16, n_out, group_size, True, name)
-    # pack() is host-side layout arithmetic (the checkpoint path runs it on the CPU)
-    bias = linear.bias.detach().cpu() if linear.bias is not None else None
-    holder = types.SimpleNamespace(weight=types.SimpleNamespace(data=res.weight.cpu()), bias=bias)
-    module.pack(holder, scales=res.scale_group.cpu(), zeros=res.zero_group.cpu(), outlieridx=out_ids.cpu())
-    module = module.to(W.device)
+    if pack == "device":
+        holder = types.SimpleNamespace(weight=types.SimpleNamespace(data=res.weight), bias=linear.bias)
+        module = module.to(W.device)
+        module.pack_device(holder, scales=res.scale_group, zeros=res.zero_group, outlieridx=out_ids)
+    else:
+        # pack() is host-side layout arithmetic (the checkpoint path runs it on the CPU)
+        bias = linear.bias.detach().cpu() if linear.bias is not None else None
+        holder = types.SimpleNamespace(weight=types.SimpleNamespace(data=res.weight.cpu()), bias=bias)
+        module.pack(holder, scales=res.scale_group.cpu(), zeros=res.zero_group.cpu(), outlieridx=out_ids.cpu())
+        module = module.to(W.device)
     module.set_kernel()
     info = types.SimpleNamespace(bits=bits, sym=False, group_size=group_size, n_out=n_out, reorder=True,
                                  scale_group=res.scale_group, zero_group=res.zero_group, out_ids=out_ids, ids=ids,
                                  proxy_loss=res.proxy_loss, weight=res.weight)
+    return module, info
+
+
+def rtn_linear(linear, n_out, name, H=None, outidx=None, bits=4, group_size=128, frob_norm=True, tuning="minmax"):
+    """Round to nearest: the reference's --nearest (n_out == 0) and --nearest_owq (GPTQ_OWQ.fasterquant_nearest_owq_reorder,
+    recon.py:327-384) of one fp16 nn.Linear on the GPU -> (QuantLinear, quantinfo), with no error feedback and no factorisation.
+
+    n_out > 0: the outlier columns come from select_outliers (diag(H), weighed by frob_norm as in calibrate_linear, or `outidx`
+    as given; one of H and outidx is required) and stay fp16; the other columns, in `ids` order, are quantised per 128-column
+    group with the min-max parameters of the group's live columns -- gather, search, rounding and packing in ONE launch of
+    qeft_quant_pack (QuantLinear.pack_device in find mode).  The quantinfo namespace has the fields
+    calibrate_linear returns (proxy_loss is None: no Hessian is needed here; weight is not kept), so the layer saves and loads
+    like any other, and the same rule for o_proj / out_proj names applies.  Only tuning="minmax": the MSE search is refused."""
+    if tuning != "minmax":
+        raise ValueError(f"tuning = {tuning!r}: rtn_linear finds min-max parameters inside the pack launch; the MSE search "
+                         "runs only in calibrate_linear")
+    if group_size != BLOCK:
+        raise ValueError(f"group_size = {group_size}: only {BLOCK} is supported")
+    if bits not in (3, 4):
+        raise ValueError(f"bits = {bits}: only 3 and 4 are supported")
+    W = linear.weight.data
+    _need_gpu(W, "linear.weight")
+    N, K = W.shape
+    if n_out % 2 != 0 or not 0 <= n_out < K:
+        raise ValueError(f"n_out = {n_out}: must be even and in 0 .. K - 1 = {K - 1}")
+    dev = W.device
+    if n_out == 0:
+        out_ids, ids, col_ids = torch.zeros(0, dtype=torch.int32, device=dev), torch.arange(K, device=dev), None
+    else:
+        if H is None and outidx is None:
+            raise ValueError("rtn_linear with n_out > 0 needs H (to select the outlier columns) or outidx")
+        if H is None:
+            out_ids = outidx.to(device=dev, dtype=torch.int32)
+            ids = sparse_to_dense_ids(out_ids, K)
+        else:
+            _need_gpu(H, "H")
+            if frob_norm is True:
+                frob_norm = frob_norm_error(W, bits, group_size, tuning)
+            elif frob_norm is False:
+                frob_norm = None
+            out_ids, ids = select_outliers(H, n_out, frob_norm=frob_norm, outidx=outidx)
+        col_ids = ids.to(torch.int32)
+    module = QuantLinear(bits, K, N, linear.bias is not None, torch.float16, n_out, group_size, True, name).to(dev)
+    holder = types.SimpleNamespace(weight=types.SimpleNamespace(data=W.to(torch.float16)), bias=linear.bias)
+    scale, zero = module.pack_device(holder, None, None, out_ids, col_ids=col_ids)
+    module.set_kernel()
+    info = types.SimpleNamespace(bits=bits, sym=False, group_size=group_size, n_out=n_out, reorder=True, scale_group=scale,
+                                 zero_group=zero, out_ids=out_ids, ids=ids, proxy_loss=None, weight=None)
     return module, info

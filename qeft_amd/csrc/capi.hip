@@ -20,6 +20,7 @@
 #include "calib.h"
 #include "calib_mse.h"
 #include "calib_factor.h"
+#include "quant_pack.h"
 
 static thread_local int g_last_hip_error = 0;
 thread_local const char* qeft::g_last_variant = "";
@@ -1518,6 +1519,24 @@ int qeft_hinv_factor(void* a, int ld, void* u, int* info, int k, qeft_stream_t s
     if (!a || !u || !info || a == u) return QEFT_ERR_NULL;
     if (!aligned16(a) || !aligned16(u) || ((uintptr_t)info & 3)) return QEFT_ERR_ALIGN;
     return finish(qeft::hinv_factor_launch(a, u, info, qeft::HfGeom{k, ld}, (hipStream_t)stream));
+}
+
+// ---- quantise and pack (quant_pack.hip)
+int qeft_quant_pack(const void* w, int ld_w, const void* col_ids, const void* scale_in, const void* zero_in, void* qweight,
+                    void* scales, void* scaled_zeros, void* scale_out, void* zero_out, int n, int k, int n_out, int bits,
+                    int group_size, qeft_stream_t stream) {
+    if ((bits != 3 && bits != 4) || n < qeft::QP_ROWS || n % qeft::QP_ROWS != 0 || n > qeft::QP_MAX_N || k < qeft::QP_GROUP ||
+        k % qeft::QP_GROUP != 0 || k > qeft::QP_MAX_K || ld_w < k || (!col_ids && ld_w % 8 != 0) || n_out < 0 || n_out % 2 != 0 ||
+        n_out >= k || (bits == 3 && n_out % qeft::QP_GROUP != 0))
+        return QEFT_ERR_SHAPE;
+    if (group_size != qeft::QP_GROUP) return QEFT_ERR_GROUP;
+    if (!w || !qweight || !scales || !scaled_zeros || (scale_in == nullptr) != (zero_in == nullptr)) return QEFT_ERR_NULL;
+    if (!aligned16(qweight) || (!col_ids && !aligned16(w))) return QEFT_ERR_ALIGN;
+    if (((uintptr_t)w | (uintptr_t)scales | (uintptr_t)scaled_zeros) & 1) return QEFT_ERR_ALIGN;
+    if (((uintptr_t)col_ids | (uintptr_t)scale_in | (uintptr_t)zero_in | (uintptr_t)scale_out | (uintptr_t)zero_out) & 3) return QEFT_ERR_ALIGN;
+    const qeft::QpGeom G{n, k, ld_w, n_out, bits};
+    return finish(qeft::quant_pack_launch(w, col_ids, scale_in, zero_in, qweight, scales, scaled_zeros, scale_out, zero_out, G,
+                                          (hipStream_t)stream));
 }
 
 // ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)

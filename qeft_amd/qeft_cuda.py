@@ -320,6 +320,50 @@ def pack_oweight_device(oweights):
     return out
 
 
+def quant_pack(weight, scales=None, zeros=None, n_out=0, bits=4, group_size=128, col_ids=None):
+    """fp16 weight [N, K] -> (qweight, scales16, scaled_zeros16, scale32, zero32) in one launch of qeft_quant_pack
+    (csrc/quant_pack.hip): what QuantLinear.pack computes on the host, on the weight's device.
+
+    scales / zeros fp32 [N, K / 128] given: the codes of those parameters (finishing a GPTQ reconstruction); both None: round to
+    nearest with quant.minmax_params found per group over its live columns.  The last n_out columns stay fp16 elsewhere.
+    col_ids int32 [K]: column j of the operand is weight[:, col_ids[j]] (the gather of calibrate.select_outliers' ids).
+    qweight: int16 [N / 4, K] at 4 bits, int32 [N / 16, (K - n_out) / 128 * 192] at 3; scales16, scaled_zeros16: fp16 [K / 128, N];
+    scale32, zero32: fp32 [N, K / 128], the given tensors or what was found.  GPU tensors only, no torch fallback."""
+    _need(isinstance(weight, torch.Tensor) and weight.is_cuda, "weight must be a GPU tensor (qeft_quant_pack has no CPU path)")
+    _need(weight.dtype == torch.float16 and weight.dim() == 2, "expected a 2-d Half weight")
+    _need((scales is None) == (zeros is None), "scales and zeros: both (given mode) or neither (find mode)")
+    n, k = weight.shape
+    dev = weight.device
+    w = weight if weight.stride(1) == 1 and weight.stride(0) >= k else weight.contiguous()
+    if col_ids is None and (w.stride(0) % 8 != 0 or w.data_ptr() % 16 != 0):
+        w = w.contiguous()
+    groups = k // group_size if group_size > 0 else 0
+    find = scales is None
+    if find:
+        scale32 = torch.empty((n, groups), dtype=torch.float32, device=dev)
+        zero32 = torch.empty((n, groups), dtype=torch.float32, device=dev)
+    else:
+        for t, name in ((scales, "scales"), (zeros, "zeros")):
+            _need(t.device == dev and t.dtype == torch.float32 and tuple(t.shape) == (n, groups),
+                  f"{name} must be fp32 [{n}, {groups}] on {dev}")
+        scale32, zero32 = scales.contiguous(), zeros.contiguous()
+    if col_ids is not None:
+        _need(col_ids.device == dev and col_ids.numel() == k, f"col_ids must hold {k} indices on {dev}")
+        col_ids = col_ids.to(torch.int32).contiguous()
+    live_groups = max(k - n_out, 0) // 128
+    qweight = torch.empty((n // 16, live_groups * 192), dtype=torch.int32, device=dev) if bits == 3 else \
+        torch.empty((n // 4, k), dtype=torch.int16, device=dev)
+    scales16 = torch.empty((groups, n), dtype=torch.float16, device=dev)
+    scaled_zeros16 = torch.empty((groups, n), dtype=torch.float16, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().qeft_quant_pack(
+            w.data_ptr(), w.stride(0), ptr(col_ids), None if find else scale32.data_ptr(), None if find else zero32.data_ptr(),
+            qweight.data_ptr(), scales16.data_ptr(), scaled_zeros16.data_ptr(), scale32.data_ptr() if find else None,
+            zero32.data_ptr() if find else None, n, k, n_out, bits, group_size, _stream(weight)))
+    return qweight, scales16, scaled_zeros16, scale32, zero32
+
+
 # ---- 3-bit extension (include/qeft_hip.h, "3-bit EXTENSION"); the reference has no counterpart --------------------
 def gemv_3bit(x, qweight3, scales, scaled_zeros, oweight_il, bias, residual, m, n, k, group_size, sz_packed=None):
     """y[m, n] = x . W3^T (+ bias, + residual) on the 3-bit stream; any m >= 1."""

@@ -19,6 +19,12 @@ of every side before any measurement, the sides alternating (medians of --reps r
   --only-factor  (> profiles/calib_factor_bench.json.log) the factor of the inverse Hessian at K = 4096 and 11008: the three torch
                  calls against hinv_factor (qeft_hinv_factor, 3 K / 128 - 1 launches) on the same damped matrix, then a whole
                  4096 x K reconstruction with factor = "torch" and factor = "own" 
+  --only-pack    (> profiles/quant_pack_bench.json.log) the packing step: calibrate_linear(factor="own") end
+                 to end with pack="host" and pack="device", alternating, at N x K = 4096 x 4096, 11008 x 4096 and 4096 x 11008
+                 with 128 outlier columns; then the qeft_quant_pack launch alone, given and find mode, in windows of back-to-back
+                 launches through the C entry on preallocated outputs -- over ONE weight matrix (it fits the Infinity Cache) and
+                 cycling 8 (they do not) -- with its algorithmic bytes 2 N K + N K / 2 + 12 N K / 128 over that time as a
+                 share of 8 TB/s
 One JSON line per part; no threshold.  Every part runs under its own time limit."""
 import argparse
 import faulthandler
@@ -260,6 +266,57 @@ def factor_bench(n, k, r, reps):
     print(json.dumps(res), flush=True)
 
 
+def pack_bench(n, k, r, reps, inner):
+    """The packing step: the whole per-linear calibration with the host pack and with the device pack, then the launch alone."""
+    from qeft_amd import _lib
+    from qeft_amd.calibrate import HessianAccumulator, calibrate_linear
+    g = torch.Generator(device=DEV).manual_seed(2)
+    lin = torch.nn.Linear(k, n, bias=False).half().to(DEV)
+    lin.weight.data = (torch.randn(n, k, generator=g, device=DEV) * 0.02).half()
+    acc = HessianAccumulator(k, DEV)
+    acc.add_batch(rows(2048, k, 3))
+    ids = torch.arange(k - r, k, device=DEV, dtype=torch.int32)
+    out = {}
+
+    def side(pack):
+        def run():
+            out[pack] = calibrate_linear(lin, acc.H, r, "q_proj", outidx=ids, factor="own", pack=pack)
+        return run
+
+    e2e, spread = medians_ms([side("host"), side("device")], reps)
+    sd_h, sd_d = out["host"][0].state_dict(), out["device"][0].state_dict()
+    same = list(sd_h) == list(sd_d) and all(torch.equal(sd_h[key], sd_d[key]) for key in sd_h)
+    W, scale, zero = out["device"][1].weight, out["device"][1].scale_group.contiguous(), out["device"][1].zero_group.contiguous()
+    del out, sd_h, sd_d
+    copies = [W] + [W.clone() for _ in range(7)]
+    q = torch.empty(n // 4, k, dtype=torch.int16, device=DEV)
+    s16, z16 = (torch.empty(k // 128, n, dtype=torch.float16, device=DEV) for _ in range(2))
+    s32, z32 = torch.empty_like(scale), torch.empty_like(zero)
+    lib, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
+
+    def window(find, n_w):
+        def run():
+            for i in range(inner):
+                w = copies[i % n_w]
+                _lib.check(lib.qeft_quant_pack(w.data_ptr(), k, None, None if find else scale.data_ptr(), None if find else zero.data_ptr(),
+                                               q.data_ptr(), s16.data_ptr(), z16.data_ptr(), s32.data_ptr() if find else None,
+                                               z32.data_ptr() if find else None, n, k, r, 4, 128, st))
+        return run
+
+    names = ("given_one_matrix", "given_eight_matrices", "find_one_matrix", "find_eight_matrices")
+    ks, kspread = medians_ms([window(False, 1), window(False, 8), window(True, 1), window(True, 8)], reps)
+    nbytes = 2.0 * n * k + n * k / 2 + 12.0 * n * k / 128
+    res = dict(bench="calibrate", op="quant_pack", n=n, k=k, n_out=r, bits=4, reps=reps, inner=inner,
+               calibrate_linear_host_pack_ms=round(e2e[0], 2), calibrate_linear_host_pack_ms_min_max=[round(v, 2) for v in spread[0]],
+               calibrate_linear_device_pack_ms=round(e2e[1], 2), calibrate_linear_device_pack_ms_min_max=[round(v, 2) for v in spread[1]],
+               device_over_host=round(e2e[1] / e2e[0], 4), same_state_dict=same, algorithmic_bytes=int(nbytes))
+    for name, ms, sp in zip(names, ks, kspread):
+        res[f"launch_{name}_us"] = round(ms * 1e3 / inner, 2)
+        res[f"launch_{name}_us_min_max"] = [round(v * 1e3 / inner, 2) for v in sp]
+        res[f"launch_{name}_share_of_8TBps"] = round(nbytes / (ms * 1e-3 / inner) / 8e12, 4)
+    print(json.dumps(res), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -267,8 +324,14 @@ if __name__ == "__main__":
     ap.add_argument("--only-add-batch", action="store_true")
     ap.add_argument("--only-mse", action="store_true", help="the MSE search parts alone (profiles/calib_mse_bench.json.log)")
     ap.add_argument("--only-factor", action="store_true", help="the inverse-Hessian factor alone (profiles/calib_factor_bench.json.log)")
+    ap.add_argument("--only-pack", action="store_true", help="the packing step alone (profiles/quant_pack_bench.json.log)")
     a = ap.parse_args()
     print(json.dumps(dict(bench="calibrate", device=torch.cuda.get_device_name(0), torch=torch.__version__)), flush=True)
+    if a.only_pack:
+        for n, k in ([(64, 384)] if a.small else [(4096, 4096), (11008, 4096), (4096, 11008)]):
+            with limit(300):
+                pack_bench(n, k, 128, a.reps, 8 if a.small else 2000)
+        sys.exit(0)
     if a.only_factor:
         for n, k in ([(64, 384)] if a.small else [(4096, 4096), (4096, 11008)]):
             with limit(400):

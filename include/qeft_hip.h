@@ -864,6 +864,29 @@ int qeft_quant_pack(const void* w, int ld_w, const void* col_ids, const void* sc
                     void* scales, void* scaled_zeros, void* scale_out, void* zero_out, int n, int k, int n_out, int bits,
                     int group_size, qeft_stream_t stream);
 
+/* The whole GPTQ error-feedback loop of one weight matrix in ONE launch, every workgroup owning 16 rows (csrc/calib_rows.hip,
+ * csrc/calib_rows.h; qeft_amd/calibrate.py: gptq_reorder(loop="rows")).
+ * w0: fp32 [n][k], rows ld_w elements apart, columns in the order of the reconstruction with dead columns zeroed; read only.
+ * hinv: fp32 [k][k], rows ld_h apart: the upper factor U of the inverse damped Hessian (either factor route); what lies below the
+ *   diagonal does not matter.  n_nonout: the live columns (the first n_nonout); k - n_nonout is even and may be 0.
+ * q: fp32 [n][k] contiguous.  Live columns: the dequantised values; the others: w0 - err . U[:n_nonout, n_nonout:].
+ * err: fp32 [n][n_nonout] contiguous: the errors e of the pinned lines -- a result, and the kernel's own operand.
+ * scale, zero: fp32 [n][k / 128]: one pair per started group of 128 live columns, the last repeated up to k / 128.
+ * Per 128-column block, starting at column i1: w = w0[., blk] - err[., :i1] . U[:i1, blk] (fp32 MFMA accumulation, ascending, one
+ *   fixed order); the pair is quant.minmax_params over the block's live columns of w as torch runs it on the device (the lines of
+ *   qeft_quant_pack's find mode, except s = fl((xmax - xmin) * fl(1 / maxq)): torch's division by a host scalar there);
+ *   then the lines of qeft_gptq_block above, i ascending.  With the same w at a block's start, q, err, scale and zero carry the
+ *   bits of that entry.  A row's outputs depend on that row and hinv alone, not on n, the row's index or the grid; the same input
+ *   gives the same bits on every run.  No workspace, no atomics, no host synchronisation.
+ * qeft_gptq_rows_blocks(n): the grid, ceil(n / 16) workgroups (0 for n < 1); pure host.
+ * QEFT_ERR_SHAPE first: n < 1, k < 128, k % 128 != 0, k > 32768, ld_w or ld_h below k or no multiple of 4 (rows are read 16 bytes
+ *   at a time), n_nonout outside 1 .. k, k - n_nonout odd, maxq other than 7 or 15; then QEFT_ERR_GROUP for a group_size other
+ *   than 128; then QEFT_ERR_NULL (every pointer is required); then QEFT_ERR_ALIGN (w0, hinv, q, err 16-byte aligned, scale and
+ *   zero 4-byte). */
+int qeft_gptq_rows_blocks(int n);
+int qeft_gptq_rows(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
+                   int n_nonout, int maxq, int group_size, qeft_stream_t stream);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py). A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

@@ -8,10 +8,13 @@ GPTQ_OWQ.add_batch / hessian_sorting / fasterquant_reorder; main.py:130-171 for 
     U = hinv_factor(Hd)                     the upper factor of Hd^-1 the loop runs on, what factor="own" calls    (qeft_hinv_factor)
     module, info = calibrate_linear(..., pack="device")     the packing step on the GPU as well, DESIGN.md section 4.22  (qeft_quant_pack)
     module, info = rtn_linear(linear, n_out, name, H)       round to nearest, the reference's --nearest / --nearest_owq  (qeft_quant_pack)
+    module, info = calibrate_linear(..., loop="rows")       the whole error-feedback loop in ONE launch, a workgroup per 16 rows,
+                                                            DESIGN.md section 4.23                                 (qeft_gptq_rows)
 
 GPU tensors only: the kernels have no CPU path and no torch fallback.  Around them the reference's own torch expressions
 remain: dead columns, damping, the three Cholesky calls (factor="torch", the default), the trailing update `W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]` and the
 group parameters, which are computed between launches (group size == block size == 128, so a group starts where a block does).
+With loop="rows" the last two are inside the one launch as well: nothing of the loop then runs outside HIP.
 
 Out of scope, still: whole-model calibration (layer-by-layer activation capture, the shared outlier index, make_reorder's folding
 of the permutation into norms and embeddings), act_order and sym=True.
@@ -198,8 +201,10 @@ def hinv_factor(Hd):
     return u
 
 
-def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning="minmax", hinv=None, sym=False, factor="torch"):
-    """The reference's fasterquant_reorder (recon.py:488-573) of one weight matrix on the GPU, 128 columns per launch.
+def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning="minmax", hinv=None, sym=False, factor="torch",
+                 loop="blocks"):
+    """The reference's fasterquant_reorder (recon.py:488-573) of one weight matrix on the GPU, 128 columns per launch
+    (loop="blocks") or the whole loop in one (loop="rows").
 
     W [N, K] (any float dtype), H fp32 [K, K] as accumulated, ids the column order (select_outliers), the last n_out columns of
     which stay unquantised.  Returns a namespace:
@@ -212,7 +217,17 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
     tuning: 'minmax' (quant.minmax_params on the block's current columns), 'mse' (mse_search: the reference's default search in
     one launch per block) or 'mse_torch' (mse_params, the same search as 640 torch passes: the comparison route).  hinv: the upper Cholesky factor of the inverse damped Hessian in `ids` order,
     for a caller that has one (it replaces the factorisation).  factor: how that matrix is computed otherwise -- 'torch' (the
-    reference's three Cholesky calls) or 'own' (hinv_factor: one blocked factorisation in HIP)."""
+    reference's three Cholesky calls) or 'own' (hinv_factor: one blocked factorisation in HIP).
+    loop: 'blocks' (the default: per 128 columns a torch min-max, one qeft_gptq_block launch and a rocBLAS GEMM for the trailing
+    update) or 'rows' (qeft_gptq_rows, DESIGN.md section 4.23: ONE launch in which a workgroup owns 16 rows and sweeps every
+    column of them, the trailing update formed left-looking on the matrix unit; min-max parameters only -- the same lines and,
+    from the same block-start columns, the same bits; the trailing sums have another order than rocBLAS's, so the two routes
+    agree as closely as either agrees with fp64, not bit for bit)."""
+    if loop not in ("blocks", "rows"):
+        raise ValueError(f"loop = {loop!r}: 'blocks' or 'rows'")
+    if loop == "rows" and tuning != "minmax":
+        raise ValueError(f"tuning = {tuning!r} with loop='rows': the MSE search runs between launches; inside the one launch "
+                         "it is a change of its own -- use loop='blocks'")
     if group_size != BLOCK:
         raise ValueError(f"group_size = {group_size}: only {BLOCK} is supported (a group must start where a block does)")
     if sym:
@@ -257,6 +272,14 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
         raise ValueError(f"hinv {tuple(hinv.shape)}: want [{K}, {K}]")
 
     lib, st = _lib.lib(), _stream(dev)
+    if loop == "rows":
+        Q = torch.empty_like(Wk)
+        err = torch.empty((N, n_nonout), dtype=torch.float32, device=dev)
+        scale_group = torch.empty((N, K // BLOCK), dtype=torch.float32, device=dev)
+        zero_group = torch.empty_like(scale_group)
+        _lib.check(lib.qeft_gptq_rows(Wk.data_ptr(), K, hinv.data_ptr(), K, Q.data_ptr(), err.data_ptr(), scale_group.data_ptr(),
+                                      zero_group.data_ptr(), N, K, n_nonout, maxq, group_size, st))
+        return _reorder_result(W0, Q, H0, scale_group, zero_group, ids, n_nonout, bits, group_size, n_out)
     Q = torch.zeros_like(Wk)
     scales, zeros = [], []
     for i1 in range(0, n_nonout, BLOCK):
@@ -277,9 +300,14 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
         scales.append(scales[-1])
         zeros.append(zeros[-1])
     Q[:, n_nonout:] = Wk[:, n_nonout:]
+    return _reorder_result(W0, Q, H0, torch.cat(scales, 1), torch.cat(zeros, 1), ids, n_nonout, bits, group_size, n_out)
+
+
+def _reorder_result(W0, Q, H0, scale_group, zero_group, ids, n_nonout, bits, group_size, n_out):
+    """What gptq_reorder returns, from either loop: the fp16 weight, the groups and the proxy loss in fp64 on the undamped H."""
     E = (W0 - Q).double()
     proxy_loss = ((E @ H0) * E).sum().item()
-    return types.SimpleNamespace(weight=Q.to(torch.float16), scale_group=torch.cat(scales, 1), zero_group=torch.cat(zeros, 1),
+    return types.SimpleNamespace(weight=Q.to(torch.float16), scale_group=scale_group, zero_group=zero_group,
                                  out_ids=ids[n_nonout:].to(torch.int32), ids=ids, bits=bits, group_size=group_size, n_out=n_out,
                                  proxy_loss=proxy_loss)
 
@@ -290,7 +318,7 @@ def calibrate_linear(linear, H, n_out, name, bits=4, group_size=128, frob_norm=T
 
     frob_norm: True = weigh diag(H) by frob_norm_error(W) as the reference does by default, False/None = diag(H) alone, or the
     tensor to use.  outidx: fixed outlier columns instead of a selection.  Other keywords go to gptq_reorder (percdamp, tuning,
-    hinv, factor).  The quantinfo namespace carries what checkpoint.save_packed / quant.lm_pack read (bits, sym, group_size, n_out,
+    hinv, factor, loop).  The quantinfo namespace carries what checkpoint.save_packed / quant.lm_pack read (bits, sym, group_size, n_out,
     reorder, scale_group, zero_group, out_ids) plus ids and proxy_loss, so the layer saves and loads like any other.
 
     The packed columns are in `ids` order.  A module whose name contains 'o_proj' or 'out_proj' gathers its own input

@@ -1,0 +1,206 @@
+// The row-owned GPTQ loop (calibrate.gptq_reorder(loop="rows")): every 128-column block of the
+// error-feedback loop, the trailing updates and the block-start parameters in ONE launch.  The contract, the split of the work,
+// the three phases of a tile and the bounds of every address: calib_rows.h.  Nothing below may be contracted into an FMA (the
+// pinned lines of calib.h), hence the pragma over the whole file; the divisions are IEEE (the compiler's default for fp32).
+#include <math.h>
+
+#include "qeft_common.h"
+#include "calib_rows.h"
+#include "quant_pack.h"
+
+#pragma clang fp contract(off)
+
+namespace qeft {
+
+// Steps I .. 127 of the serial sweep, unrolled by recursion so that the row stays in registers and every register index, lane
+// index and LDS offset is a constant (a 128-step loop is past the size at which the unroll pragma is obeyed); a column >= count
+// is skipped by a uniform branch.  The lines are calib.h's; all 16 lanes of a row compute the same q and e, the owner keeps them.
+template <int I>
+__device__ __forceinline__ void gr_sweep(float (&w)[8], float (&qv)[8], float (&ev)[8], const float* Hs, float s, float z, float maxq,
+                                         int count, int lane, int c) {
+    if constexpr (I < GR_B) {
+        constexpr int m = I >> 4, o = I & 15;
+        if (I < count) {
+            const float wi = __shfl(w[m], (lane & 48) | o);
+            const float d = Hs[I * GR_B + I];
+            const float xs = wi / s;
+            const float cc = fminf(fmaxf(rintf(xs) + z, 0.f), maxq);
+            const float q = s * (cc - z);
+            const float e = (wi - q) / d;
+            if (c == o) {
+                qv[m] = q;
+                ev[m] = e;
+            }
+#pragma unroll
+            for (int mm = m; mm < 8; ++mm)
+                if (mm > m || c >= o) {
+                    const float p = e * Hs[I * GR_B + c + 16 * mm];
+                    w[mm] = w[mm] - p;
+                }
+        }
+        gr_sweep<I + 1>(w, qv, ev, Hs, s, z, maxq, count, lane, c);
+    }
+}
+
+// Err is read AND written (by other threads of the workgroup, a tile earlier): no __restrict__ on it.
+__global__ __launch_bounds__(GR_THREADS) void gptq_rows_kernel(const float* __restrict__ W0, const float* __restrict__ U,
+                                                               float* __restrict__ Q, float* Err, float* __restrict__ scale,
+                                                               float* __restrict__ zero, GrGeom G, float maxq) {
+    extern __shared__ __attribute__((aligned(16))) float gr_smem[];
+    float* Us = gr_smem;                                    // [2][32][GR_LDU]   chunks of U[0:depth, tile]
+    float* Es = Us + 2 * GR_BK * GR_LDU;                    // [2][16][GR_LDE]   chunks of Err[rows, 0:depth]
+    float* Cs = Es + 2 * GR_ROWS * GR_LDE;                  // [16][GR_LDC]      the accumulators on their way to the sweep's layout
+    float* Hs = Cs + GR_ROWS * GR_LDC;                      // [128][128]        the diagonal block, zeros below the diagonal
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ml = lane & 15, mg = lane >> 4;               // the matrix unit's view: A row / B column ml, k mg of a step's 4
+    const int srow = tid >> 4, c = tid & 15;                // the sweep's view (and the Err staging's): row srow, columns c + 16 m
+    const int ur = tid >> 5, uc4 = tid & 31;                // the U staging's: chunk rows ur + 8 p, columns 4 uc4 .. + 3
+    const int row = blockIdx.x * GR_ROWS + srow;
+    const bool live = row < G.n;
+    const int rc = live ? row : G.n - 1;                    // a thread past n repeats the last row and stores nothing
+    const int ng = G.k / GR_B, nn = G.n_nonout;
+    const float* wrow = W0 + (size_t)rc * G.ld_w;
+    float* qrow = Q + (size_t)rc * G.k;
+    float* erow = Err + (size_t)rc * nn;
+    float s = 1.f, z = 0.f;                                 // the last live group's pair (every call has a live tile 0)
+
+    for (int t = 0; t < ng; ++t) {
+        const int cb = t * GR_B;
+        const int count = min(max(nn - cb, 0), GR_B);       // live columns of the tile: the serial phase runs over them
+        const bool sweep = count > 0;
+        const int depth = sweep ? cb : nn;                  // rows of Err . U that are already final
+        const int nch = (depth + GR_BK - 1) / GR_BK;
+
+        float w[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) w[m] = wrow[cb + c + 16 * m];
+
+        // ---- phase 1: acc = Err[rows, 0:depth] . U[0:depth, tile]
+        f32x4 acc[2];
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) acc[sub] = f32x4{0.f, 0.f, 0.f, 0.f};
+        float4 ru[4], rt[4];
+        float2 re;
+        auto load = [&](int kc) {
+            const int k0 = kc * GR_BK;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int kr = k0 + ur + 8 * p;
+                ru[p] = kr < depth ? *(const float4*)(U + (size_t)kr * G.ld_h + cb + 4 * uc4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            const int ke = k0 + 2 * c;                      // depth is even: the pair is inside or outside as one
+            re = ke < depth ? *(const float2*)(erow + ke) : make_float2(0.f, 0.f);
+        };
+        auto stage = [&](int kc) {
+            float* ub = Us + (kc & 1) * GR_BK * GR_LDU;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) *(float4*)(ub + (ur + 8 * p) * GR_LDU + 4 * uc4) = ru[p];
+            *(float2*)(Es + (kc & 1) * GR_ROWS * GR_LDE + srow * GR_LDE + 2 * c) = re;
+        };
+        // piece tp of the diagonal block: rows 32 tp + ur + 8 p
+        auto tri_load = [&](int tp) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int i = 32 * tp + ur + 8 * p;
+                rt[p] = *(const float4*)(U + (size_t)(cb + i) * G.ld_h + cb + 4 * uc4);
+            }
+        };
+        auto tri_store = [&](int tp) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int i = 32 * tp + ur + 8 * p, j = 4 * uc4;
+                *(float4*)(Hs + i * GR_B + j) = make_float4(j >= i ? rt[p].x : 0.f, j + 1 >= i ? rt[p].y : 0.f,
+                                                            j + 2 >= i ? rt[p].z : 0.f, j + 3 >= i ? rt[p].w : 0.f);
+            }
+        };
+
+        int tp = sweep ? 0 : 4;                             // an outlier tile has no serial phase and needs no triangle
+        if (nch > 0) load(0);
+        for (int kc = 0; kc < nch; ++kc) {
+            stage(kc);                                      // buffer kc & 1: everyone left it before the barrier of chunk kc - 1
+            if (kc + 1 < nch) load(kc + 1);                 // in flight behind this chunk's MFMAs
+            if (tp < 4) tri_load(tp);
+            __syncthreads();
+            const float* ub = Us + (kc & 1) * GR_BK * GR_LDU + mg * GR_LDU + 32 * wave + ml;
+            const float* eb = Es + (kc & 1) * GR_ROWS * GR_LDE + ml * GR_LDE + mg;
+#pragma unroll
+            for (int st = 0; st < GR_BK / 4; ++st) {
+                const float a = eb[4 * st];
+                const float b0 = ub[4 * st * GR_LDU], b1 = ub[4 * st * GR_LDU + 16];
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, acc[1], 0, 0, 0);
+            }
+            if (tp < 4) {
+                tri_store(tp);
+                ++tp;
+            }
+        }
+        for (; tp < 4; ++tp) {                              // tile 0: no chunk to ride on
+            tri_load(tp);
+            tri_store(tp);
+        }
+
+        // ---- phase 2: the accumulators into the sweep's layout; w = W0 - acc
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Cs[(4 * mg + r) * GR_LDC + 32 * wave + 16 * sub + ml] = acc[sub][r];
+        __syncthreads();                                    // Cs, and every piece of Hs
+#pragma unroll
+        for (int m = 0; m < 8; ++m) w[m] = w[m] - Cs[srow * GR_LDC + c + 16 * m];
+
+        if (sweep) {
+            float lo = 0.f, hi = 0.f;                       // min and max do not round: any order gives the row's
+#pragma unroll
+            for (int m = 0; m < 8; ++m)
+                if (c + 16 * m < count) {
+                    lo = fminf(lo, w[m]);
+                    hi = fmaxf(hi, w[m]);
+                }
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) {        // the row's 16 lanes
+                lo = fminf(lo, __shfl_xor(lo, off));
+                hi = fmaxf(hi, __shfl_xor(hi, off));
+            }
+            qp_minmax_pair<true>(lo, hi, maxq, s, z);         // the block route's bits: torch's own lines on the device
+
+            // ---- phase 3: the serial sweep
+            float qv[8], ev[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) qv[m] = ev[m] = 0.f;
+            gr_sweep<0>(w, qv, ev, Hs, s, z, maxq, count, lane, c);
+            if (live) {
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    const int j = c + 16 * m;
+                    if (j < count) {
+                        qrow[cb + j] = qv[m];
+                        erow[cb + j] = ev[m];
+                    } else {
+                        qrow[cb + j] = w[m];                // an outlier column that shares the tile: W0 - Err . U, complete
+                    }
+                }
+            }
+        } else if (live) {
+#pragma unroll
+            for (int m = 0; m < 8; ++m) qrow[cb + c + 16 * m] = w[m];
+        }
+        if (live && c == 0) {                               // a tile without a live column repeats the last pair
+            scale[(size_t)row * ng + t] = s;
+            zero[(size_t)row * ng + t] = z;
+        }
+        __syncthreads();                                    // the tile's err is stored and visible; Us, Es, Cs, Hs are free
+    }
+}
+
+hipError_t gptq_rows_launch(const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero, const GrGeom& G,
+                            float maxq, hipStream_t st) {
+    g_last_variant = "gptq_rows_16";
+    if (hipError_t e = hipFuncSetAttribute((const void*)gptq_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GR_LDS)) return e;
+    hipLaunchKernelGGL(gptq_rows_kernel, dim3((unsigned)gr_blocks(G)), dim3(GR_THREADS), GR_LDS, st, (const float*)w0,
+                       (const float*)hinv, (float*)q, (float*)err, (float*)scale, (float*)zero, G, maxq);
+    return hipGetLastError();
+}
+
+}  // namespace qeft

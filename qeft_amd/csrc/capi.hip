@@ -20,6 +20,7 @@
 #include "calib.h"
 #include "calib_mse.h"
 #include "calib_factor.h"
+#include "calib_rows.h"
 #include "quant_pack.h"
 
 static thread_local int g_last_hip_error = 0;
@@ -1537,6 +1538,22 @@ int qeft_quant_pack(const void* w, int ld_w, const void* col_ids, const void* sc
     const qeft::QpGeom G{n, k, ld_w, n_out, bits};
     return finish(qeft::quant_pack_launch(w, col_ids, scale_in, zero_in, qweight, scales, scaled_zeros, scale_out, zero_out, G,
                                           (hipStream_t)stream));
+}
+
+// ---- the row-owned GPTQ loop (calib_rows.hip)
+int qeft_gptq_rows_blocks(int n) { return n < 1 ? 0 : qeft::gr_blocks(qeft::GrGeom{n, 0, 0, 0, 0}); }
+
+int qeft_gptq_rows(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
+                   int n_nonout, int maxq, int group_size, qeft_stream_t stream) {
+    if (n < 1 || k < qeft::GR_B || k % qeft::GR_B != 0 || k > qeft::GR_MAX_K || ld_w < k || ld_w % 4 != 0 || ld_h < k || ld_h % 4 != 0 ||
+        n_nonout < 1 || n_nonout > k || (k - n_nonout) % 2 != 0 || (maxq != 7 && maxq != 15))
+        return QEFT_ERR_SHAPE;
+    if (group_size != qeft::GR_B) return QEFT_ERR_GROUP;
+    if (!w0 || !hinv || !q || !err || !scale || !zero) return QEFT_ERR_NULL;
+    if (!aligned16(w0) || !aligned16(hinv) || !aligned16(q) || !aligned16(err)) return QEFT_ERR_ALIGN;
+    if (((uintptr_t)scale | (uintptr_t)zero) & 3) return QEFT_ERR_ALIGN;
+    const qeft::GrGeom G{n, k, ld_w, ld_h, n_nonout};
+    return finish(qeft::gptq_rows_launch(w0, hinv, q, err, scale, zero, G, (float)maxq, (hipStream_t)stream));
 }
 
 // ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)

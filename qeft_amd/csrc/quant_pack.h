@@ -77,6 +77,21 @@ QP_HD long long qp_q3_off(const QpGeom& G, int row, int group, int lane) {
     return (long long)(row >> 4) * (qp_live(G) / QP_GROUP * 192) + (long long)(group * 64 + lane) * 3;
 }
 
+// The pair of find mode from a row's min and max over the group's live columns with 0 among them (lo <= 0 <= hi): the lines of
+// quant.minmax_params, one rounding per operation, IEEE division, rint = half to even (nothing here can contract).  Shared with
+// the row-owned GPTQ loop (calib_rows.hip), whose block-start parameters are these as torch runs them ON THE DEVICE: there a
+// division by a host scalar is the product with the scalar's fp32 reciprocal, s = fl((xmax - xmin) * fl(1 / maxq)), which is not
+// the quotient's bits for most rows (RECIP).  The division of two tensors behind z is IEEE on both.
+template <bool RECIP = false>
+__device__ __forceinline__ void qp_minmax_pair(float lo, float hi, float maxq, float& s, float& z) {
+    if (lo == 0.f && hi == 0.f) {
+        lo = -1.f;
+        hi = 1.f;
+    }
+    s = RECIP ? (hi - lo) * (1.f / maxq) : (hi - lo) / maxq;
+    z = rintf(-lo / s);
+}
+
 // ---- host side: quant_pack.hip.  col_ids, scale_in / zero_in (both or neither), scale_out, zero_out may be null.
 hipError_t quant_pack_launch(const void* w, const void* col_ids, const void* scale_in, const void* zero_in, void* qweight, void* scales,
                              void* scaled_zeros, void* scale_out, void* zero_out, const QpGeom& G, hipStream_t st);

@@ -74,12 +74,7 @@ __global__ __launch_bounds__(QP_THREADS) void quant_pack_kernel(const _Float16* 
             lo = fminf(lo, __shfl_xor(lo, off));
             hi = fmaxf(hi, __shfl_xor(hi, off));
         }
-        if (lo == 0.f && hi == 0.f) {
-            lo = -1.f;
-            hi = 1.f;
-        }
-        s = (hi - lo) / MAXQ;
-        z = rintf(-lo / s);
+        qp_minmax_pair(lo, hi, MAXQ, s, z);
     } else {
         s = scale_in[(size_t)row * ng + group];
         z = zero_in[(size_t)row * ng + group];

@@ -25,6 +25,9 @@ of every side before any measurement, the sides alternating (medians of --reps r
                  launches through the C entry on preallocated outputs -- over ONE weight matrix (it fits the Infinity Cache) and
                  cycling 8 (they do not) -- with its algorithmic bytes 2 N K + N K / 2 + 12 N K / 128 over that time as a
                  share of 8 TB/s
+  --only-loop    (> profiles/calib_rows_bench.json.log) the error-feedback loop alone: gptq_reorder with a
+                 precomputed hinv, loop = "blocks" against loop = "rows", alternating, at N x K = 4096 x 4096, 11008 x 4096 and
+                 4096 x 11008 with 128 outlier columns; then the qeft_gptq_rows launch alone on preallocated outputs
 One JSON line per part; no threshold.  Every part runs under its own time limit."""
 import argparse
 import faulthandler
@@ -317,6 +320,50 @@ def pack_bench(n, k, r, reps, inner):
     print(json.dumps(res), flush=True)
 
 
+def loop_bench(n, k, r, reps):
+    """The loop alone: gptq_reorder on a given factor with each loop (the factorisation is outside both sides), then the one
+    launch of the "rows" side without the torch around it (the gathers, the clones and the fp64 proxy loss)."""
+    from qeft_amd import _lib
+    from qeft_amd.calibrate import HessianAccumulator, gptq_reorder, hinv_factor
+    g = torch.Generator(device=DEV).manual_seed(2)
+    W = (torch.randn(n, k, generator=g, device=DEV) * 0.02).half()
+    acc = HessianAccumulator(k, DEV)
+    acc.add_batch(rows(2048, k, 3))
+    H = acc.H
+    Hd = H.clone()
+    Hd.diagonal().add_(0.01 * torch.mean(torch.diag(H)))
+    hinv = hinv_factor(Hd)
+    del Hd
+    ids = torch.arange(k, device=DEV)
+    out = {}
+
+    def side(loop):
+        def run():
+            out[loop] = gptq_reorder(W, H, ids, r, hinv=hinv, loop=loop)
+        return run
+
+    us, spread = medians_ms([side("blocks"), side("rows")], reps)
+    a, b = out["blocks"], out["rows"]
+    differ = (a.weight != b.weight).float().mean().item()
+    W0 = W.float()
+    q, sc = torch.empty_like(W0), torch.empty(n, k // 128, device=DEV)
+    err, ze = torch.empty(n, k - r, device=DEV), torch.empty_like(sc)
+    lib, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
+
+    def launch():
+        _lib.check(lib.qeft_gptq_rows(W0.data_ptr(), k, hinv.data_ptr(), k, q.data_ptr(), err.data_ptr(), sc.data_ptr(), ze.data_ptr(),
+                                      n, k, k - r, 15, 128, st))
+
+    ls, lspread = medians_ms([launch], reps)
+    res = dict(bench="calibrate", op="gptq_loop", n=n, k=k, n_out=r, reps=reps, workgroups=lib.qeft_gptq_rows_blocks(n),
+               blocks_ms=round(us[0], 2), blocks_ms_min_max=[round(v, 2) for v in spread[0]],
+               rows_ms=round(us[1], 2), rows_ms_min_max=[round(v, 2) for v in spread[1]], rows_over_blocks=round(us[1] / us[0], 4),
+               rows_launch_alone_ms=round(ls[0], 3), rows_launch_alone_ms_min_max=[round(v, 3) for v in lspread[0]],
+               rows_launch_useful_tflops=round(n * float(k - r) * (k + r) / (ls[0] * 1e-3) / 1e12, 2),
+               proxy_loss_blocks=a.proxy_loss, proxy_loss_rows=b.proxy_loss, share_of_fp16_weights_that_differ=differ)
+    print(json.dumps(res), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -325,8 +372,14 @@ if __name__ == "__main__":
     ap.add_argument("--only-mse", action="store_true", help="the MSE search parts alone (profiles/calib_mse_bench.json.log)")
     ap.add_argument("--only-factor", action="store_true", help="the inverse-Hessian factor alone (profiles/calib_factor_bench.json.log)")
     ap.add_argument("--only-pack", action="store_true", help="the packing step alone (profiles/quant_pack_bench.json.log)")
+    ap.add_argument("--only-loop", action="store_true", help="the error-feedback loop alone (profiles/calib_rows_bench.json.log)")
     a = ap.parse_args()
     print(json.dumps(dict(bench="calibrate", device=torch.cuda.get_device_name(0), torch=torch.__version__)), flush=True)
+    if a.only_loop:
+        for n, k in ([(72, 384)] if a.small else [(4096, 4096), (11008, 4096), (4096, 11008)]):
+            with limit(300):
+                loop_bench(n, k, 128, a.reps)
+        sys.exit(0)
     if a.only_pack:
         for n, k in ([(64, 384)] if a.small else [(4096, 4096), (11008, 4096), (4096, 11008)]):
             with limit(300):

@@ -887,6 +887,19 @@ int qeft_gptq_rows_blocks(int n);
 int qeft_gptq_rows(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
                    int n_nonout, int maxq, int group_size, qeft_stream_t stream);
 
+/* qeft_gptq_rows with the block-start pair found by the MSE search INSIDE the launch (csrc/calib_rows.hip, csrc/calib_rows.h;
+ * qeft_amd/calibrate.py: gptq_reorder(tuning="mse_fused", loop="rows")).  Operands, outputs, grid and
+ * the lines of a block are those of qeft_gptq_rows; only the pair differs: per row and live tile, over the tile's live columns
+ * of w, the search of qeft_mse_search above -- num ranges i = 1 .. num, 2^bits zero points each, every candidate's residuals by
+ * the same pinned fp32 lines, scored by sum |d|^2.4 (d d exp2(0.4 log2 |d|) on the hardware transcendentals), the first minimum
+ * in the order (i ascending, zp ascending) winning, the closing lines as there.  The score sum has this kernel's own fixed order
+ * (a lane's 8 columns ascending, then a tree over the row's 16 lanes: csrc/calib_rows.h), not qeft_mse_search's: among
+ * candidates closer than the sums' rounding another one may win, so no bit parity with that entry is claimed.  A row's outputs
+ * depend on that row and hinv alone; the same input gives the same bits on every run.  No workspace, no atomics.
+ * Refusals and their order are qeft_gptq_rows'; num outside 1 .. 40 is QEFT_ERR_SHAPE.  Variants gptq_rows_mse_w4 / _w3. */
+int qeft_gptq_rows_mse(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
+                       int n_nonout, int maxq, int group_size, int num, qeft_stream_t stream);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py). A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

@@ -10,6 +10,8 @@ GPTQ_OWQ.add_batch / hessian_sorting / fasterquant_reorder; main.py:130-171 for 
     module, info = rtn_linear(linear, n_out, name, H)       round to nearest, the reference's --nearest / --nearest_owq  (qeft_quant_pack)
     module, info = calibrate_linear(..., loop="rows")       the whole error-feedback loop in ONE launch, a workgroup per 16 rows,
                                                             DESIGN.md section 4.23                                 (qeft_gptq_rows)
+    module, info = calibrate_linear(..., loop="rows", tuning="mse_fused")   that launch with the MSE search of every block start
+                                                            inside it, DESIGN.md section 4.24                  (qeft_gptq_rows_mse)
 
 GPU tensors only: the kernels have no CPU path and no torch fallback.  Around them the reference's own torch expressions
 remain: dead columns, damping, the three Cholesky calls (factor="torch", the default), the trailing update `W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]` and the
@@ -139,11 +141,11 @@ def _params(x, bits, tuning):
     """(scale, zero) fp32 [N, 1] of ONE group holding every column of x."""
     if tuning == "minmax":
         return minmax_params(x, x.shape[1], bits)
-    if tuning == "mse":
+    if tuning in ("mse", "mse_fused"):                  # "mse_fused" names where gptq_reorder searches; a whole row is no tile
         return mse_search(x, bits)
     if tuning == "mse_torch":
         return mse_params(x, bits)
-    raise ValueError(f"tuning = {tuning!r}: 'minmax', 'mse' or 'mse_torch'")
+    raise ValueError(f"tuning = {tuning!r}: 'minmax', 'mse', 'mse_fused' or 'mse_torch'")
 
 
 def frob_norm_error(W, bits=4, group_size=128, tuning="minmax"):
@@ -214,7 +216,7 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
                    (recon.py:560-563); K - n_out need not be a multiple of 128 -- the last block and group are short
       out_ids (int32), ids, bits, group_size, n_out
       proxy_loss   tr((W - Q) H (W - Q)^T) on the undamped H in fp64, Q the fp32 values before the rounding to fp16
-    tuning: 'minmax' (quant.minmax_params on the block's current columns), 'mse' (mse_search: the reference's default search in
+    tuning: 'minmax' (quant.minmax_params on the block's current columns), 'mse_fused' (below), 'mse' (mse_search: the reference's default search in
     one launch per block) or 'mse_torch' (mse_params, the same search as 640 torch passes: the comparison route).  hinv: the upper Cholesky factor of the inverse damped Hessian in `ids` order,
     for a caller that has one (it replaces the factorisation).  factor: how that matrix is computed otherwise -- 'torch' (the
     reference's three Cholesky calls) or 'own' (hinv_factor: one blocked factorisation in HIP).
@@ -222,12 +224,19 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
     update) or 'rows' (qeft_gptq_rows, DESIGN.md section 4.23: ONE launch in which a workgroup owns 16 rows and sweeps every
     column of them, the trailing update formed left-looking on the matrix unit; min-max parameters only -- the same lines and,
     from the same block-start columns, the same bits; the trailing sums have another order than rocBLAS's, so the two routes
-    agree as closely as either agrees with fp64, not bit for bit)."""
+    agree as closely as either agrees with fp64, not bit for bit).
+    tuning='mse_fused' (with loop='rows' only; qeft_gptq_rows_mse): the reference's search, 40 ranges x
+    2^bits zero points over each block's current columns, INSIDE the one launch, in the registers of the 16 lanes that hold the
+    row's block.  The same candidates and residuals as 'mse'; the score sums have that kernel's own order, so among near-tied
+    candidates another one may win: its own name, no bit parity with 'mse'."""
     if loop not in ("blocks", "rows"):
         raise ValueError(f"loop = {loop!r}: 'blocks' or 'rows'")
-    if loop == "rows" and tuning != "minmax":
-        raise ValueError(f"tuning = {tuning!r} with loop='rows': the MSE search runs between launches; inside the one launch "
-                         "it is a change of its own -- use loop='blocks'")
+    if tuning == "mse_fused" and loop != "rows":
+        raise ValueError(f"tuning = 'mse_fused' with loop={loop!r}: the search inside the launch exists for loop='rows' only "
+                         "-- use tuning='mse' here")
+    if loop == "rows" and tuning not in ("minmax", "mse_fused"):
+        raise ValueError(f"tuning = {tuning!r} with loop='rows': the MSE search runs between launches -- use loop='blocks', or "
+                         "tuning='mse_fused' for the search inside the one launch")
     if group_size != BLOCK:
         raise ValueError(f"group_size = {group_size}: only {BLOCK} is supported (a group must start where a block does)")
     if sym:
@@ -277,8 +286,9 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
         err = torch.empty((N, n_nonout), dtype=torch.float32, device=dev)
         scale_group = torch.empty((N, K // BLOCK), dtype=torch.float32, device=dev)
         zero_group = torch.empty_like(scale_group)
-        _lib.check(lib.qeft_gptq_rows(Wk.data_ptr(), K, hinv.data_ptr(), K, Q.data_ptr(), err.data_ptr(), scale_group.data_ptr(),
-                                      zero_group.data_ptr(), N, K, n_nonout, maxq, group_size, st))
+        args = (Wk.data_ptr(), K, hinv.data_ptr(), K, Q.data_ptr(), err.data_ptr(), scale_group.data_ptr(), zero_group.data_ptr(),
+                N, K, n_nonout, maxq, group_size)
+        _lib.check(lib.qeft_gptq_rows_mse(*args, 40, st) if tuning == "mse_fused" else lib.qeft_gptq_rows(*args, st))
         return _reorder_result(W0, Q, H0, scale_group, zero_group, ids, n_nonout, bits, group_size, n_out)
     Q = torch.zeros_like(Wk)
     scales, zeros = [], []
@@ -318,7 +328,8 @@ def calibrate_linear(linear, H, n_out, name, bits=4, group_size=128, frob_norm=T
 
     frob_norm: True = weigh diag(H) by frob_norm_error(W) as the reference does by default, False/None = diag(H) alone, or the
     tensor to use.  outidx: fixed outlier columns instead of a selection.  Other keywords go to gptq_reorder (percdamp, tuning,
-    hinv, factor, loop).  The quantinfo namespace carries what checkpoint.save_packed / quant.lm_pack read (bits, sym, group_size, n_out,
+    hinv, factor, loop; tuning="mse_fused" needs loop="rows", and the whole-row search of frob_norm_error is then mse_search's).
+    The quantinfo namespace carries what checkpoint.save_packed / quant.lm_pack read (bits, sym, group_size, n_out,
     reorder, scale_group, zero_group, out_ids) plus ids and proxy_loss, so the layer saves and loads like any other.
 
     The packed columns are in `ids` order.  A module whose name contains 'o_proj' or 'out_proj' gathers its own input

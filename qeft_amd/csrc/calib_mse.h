@@ -49,6 +49,18 @@ MSE_HD int ms_row(const MsGeom& G, int block, int lane) {
 // element offset in x of column `col` (< g) of row `row` (< n)
 MSE_HD long long ms_x_off(const MsGeom& G, int row, int col) { return (long long)row * G.ld + col; }
 
+// ---- device side: the lines that calib_mse.hip and the in-launch search of calib_rows.hip share (products, min and max only:
+// nothing here could be contracted, whichever side of a unit's contract pragma the include stands on)
+constexpr float MS_EPS = 1e-8f;
+
+// |d|^2.4 as d * d * 2^(0.4 log2 |d|) on v_log_f32 / v_exp_f32: log2(0) = -inf and 2^-inf = 0, so d == 0 gives exactly 0.
+__device__ __forceinline__ float ms_term(float d) {
+    const float e = __builtin_amdgcn_exp2f(0.4f * __builtin_amdgcn_logf(fabsf(d)));
+    return d * d * e;
+}
+
+__device__ __forceinline__ float ms_clamp(float v, float maxq) { return fminf(fmaxf(v, 0.f), maxq); }
+
 // ---- host side: calib_mse.hip
 hipError_t mse_search_launch(const void* x, void* scale, void* zero, const MsGeom& G, hipStream_t st);
 

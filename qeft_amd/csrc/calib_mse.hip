@@ -12,16 +12,6 @@
 
 namespace qeft {
 
-constexpr float MS_EPS = 1e-8f;
-
-// |d|^2.4 as d * d * 2^(0.4 log2 |d|) on v_log_f32 / v_exp_f32: log2(0) = -inf and 2^-inf = 0, so d == 0 gives exactly 0.
-__device__ __forceinline__ float ms_term(float d) {
-    const float e = __builtin_amdgcn_exp2f(0.4f * __builtin_amdgcn_logf(fabsf(d)));
-    return d * d * e;
-}
-
-__device__ __forceinline__ float ms_clamp(float v, float maxq) { return fminf(fmaxf(v, 0.f), maxq); }
-
 template <int BITS>
 __global__ __launch_bounds__(MS_THREADS) void mse_search_kernel(const float* __restrict__ x, float* __restrict__ scale_out,
                                                                 float* __restrict__ zero_out, MsGeom G) {

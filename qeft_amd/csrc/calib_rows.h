@@ -44,12 +44,35 @@
 //   column with column < 128 and tile start + 128 <= k; hinv at (r < depth <= k) * ld_h + tile start + 4-column piece, or the
 //   diagonal block (tile start + i) * ld_h + tile start + piece; err at row * n_nonout + (column < depth <= n_nonout) for loads and
 //   (column < count) for stores; scale / zero at row * (k / 128) + tile.
+//
+// qeft_gptq_rows_mse    the same launch -- phases 1 and 2, the sweep, LDS, workgroup, grid and every address above -- with the
+//   block-start pair found by the reference's MSE search (Quantizer.find_params(mse=True): num ranges x 2^bits zero points) over
+//   the tile's live block-start columns, between phase 2 and the sweep (gptq_reorder(tuning="mse_fused",
+//   loop="rows")).  After phase 2 the 16 lanes of a row hold its 128 block-start columns in registers and nothing outside those
+//   lanes enters a row's result, so the search needs no LDS, no barrier and no global address.
+//   Pinned, as calib_mse.h (fp32, nothing contracted, IEEE divisions, rint half to even), over the count live columns of the tile:
+//     xmin = min(min_j w_j, 0);  xmax = max(max_j w_j, 0);  step = (xmax - xmin) / num
+//     per range i = 1 .. num:  tmp_max = fl(step i);  delta = max(tmp_max / maxq, 1e-8f);  x_round = rint(w_j / delta)
+//     per zero point zp:  new_min = 0 - fl(zp delta);  zero = clamp(0 - rint(new_min / delta), 0, maxq)
+//       x_q = delta (clamp(x_round + zero, 0, maxq) - zero);  d = w_j - x_q;  term = d d exp2(0.4 log2 |d|)  (0 for d == 0)
+//     the winner's closing lines: new_max = tmp_max - fl(zp delta);  lo = min(new_min, 0);  hi = max(new_max, 0)
+//       scale = max((hi - lo) / maxq, 1e-8f);  zero = clamp(0 - rint(lo / scale), 0, maxq)
+//   so a candidate's residuals are the bits calibrate.mse_params gives on the CPU.  A candidate's score has the kernel's OWN
+//   order: lane c sums the terms of its columns c, c + 16, .., c + 112 (ascending; a column >= count adds an exact +0), and the
+//   row's 16 partials are combined by the fixed tree ((p_c + p_c^8) + (p_c^4 + p_c^12)) + .. over lane ^ 8, 4, 2, 1 -- a
+//   reduce-scatter that leaves lane c with the score of zero point c % 2^bits.  The order does not depend on the row's index, n,
+//   the grid or the lane that asks; it is NOT qeft_mse_search's ascending-j order, so no bit parity with tuning="mse" is claimed.
+//   The winner is the first minimum in the reference's order (i ascending, then zp ascending, strict <): each lane keeps the
+//   first minimum over i of its zero point, one 16-lane arg-min on (score, i 2^bits + zp) follows, and all 16 lanes form the pair
+//   from the same key -- the sweep needs the same s and z bits in every lane of the row.  Without a candidate below infinity the
+//   pair is that of (xmin, xmax).  A tile without a live column repeats the last pair; a short last block searches its count
+//   columns.  num is 1 .. 40 (MS_MAX_NUM).
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace qeft {
 
-constexpr int GR_ROWS = 16;                             // rows of a workgroup
+constexpr int GR_ROWS = 16;                            // rows of a workgroup
 constexpr int GR_THREADS = 256;
 constexpr int GR_B = 128;                               // tile == block == group
 constexpr int GR_BK = 32;                               // depth of a staged chunk
@@ -68,5 +91,7 @@ __host__ __device__ inline int gr_blocks(const GrGeom& G) { return (G.n + GR_ROW
 // ---- host side: calib_rows.hip
 hipError_t gptq_rows_launch(const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero, const GrGeom& G,
                             float maxq, hipStream_t st);
+hipError_t gptq_rows_mse_launch(const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero, const GrGeom& G,
+                                int bits, int num, hipStream_t st);
 
 }  // namespace qeft

@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "qeft_common.h"
+#include "calib_mse.h"
 #include "calib_rows.h"
 #include "quant_pack.h"
 
@@ -42,10 +43,106 @@ __device__ __forceinline__ void gr_sweep(float (&w)[8], float (&qv)[8], float (&
     }
 }
 
+// The reduce-scatter of the in-launch search, steps lane ^ OFF, OFF / 2, .., 1 (recursion: every register index a constant).  A
+// step with OFF < LPR halves the zero points a lane still carries -- lanes with bit OFF keep the upper half -- and adds the
+// partner's partial of each kept one; a step with OFF >= LPR (3 bits, lane ^ 8) is a plain exchange-and-add, the same bits on
+// both sides.  Afterwards p[0] of lane c is the row's score of zero point c % LPR.
+template <int LPR, int OFF>
+__device__ __forceinline__ void gr_scatter(float (&p)[LPR], int c) {
+    if constexpr (OFF >= 1) {
+        if constexpr (OFF < LPR) {
+            const bool up = (c & OFF) != 0;
+#pragma unroll
+            for (int v = 0; v < OFF; ++v) {
+                const float keep = up ? p[v + OFF] : p[v], send = up ? p[v] : p[v + OFF];
+                p[v] = keep + __shfl_xor(send, OFF);
+            }
+        } else {
+#pragma unroll
+            for (int v = 0; v < LPR; ++v) p[v] = p[v] + __shfl_xor(p[v], OFF);
+        }
+        gr_scatter<LPR, OFF / 2>(p, c);
+    }
+}
+
+// The MSE search of one tile (qeft_gptq_rows_mse; the contract and the order of every sum: calib_rows.h), between phase 2 and the
+// sweep, in registers and cross-lane reads alone: no LDS, no barrier, no global address.  w: the lane's 8 block-start columns
+// c + 16 m; xmin / xmax: the row's extremes over the live columns and 0, the same bits in the row's 16 lanes.  A column at or past
+// count enters as 0: its x_round is 0, no zero point clamps it, d is exactly 0 and its term +0, which leaves every sum's bits.
+// Per range i the lane's partial scores of all 2^BITS zero points stay in registers (8 columns, m ascending); a reduce-scatter
+// over lane ^ 8, 4, 2, 1 then leaves lane c with the row's score of zero point c % 2^BITS (at 3 bits the first step is a plain
+// exchange-and-add, so lanes c and c ^ 8 hold the same bits), and the lane keeps the first minimum over i.  One 16-lane arg-min
+// on (score, i 2^BITS + zp) ends the search; every lane then forms the pair from the winning key by the closing lines.
+template <int BITS>
+__device__ __forceinline__ void gr_mse_pair(const float (&w)[8], int count, int c, int num, float xmin, float xmax, float& s,
+                                            float& z) {
+    constexpr int LPR = 1 << BITS;
+    constexpr float MAXQ = (float)(LPR - 1);
+    const int zp_own = c & (LPR - 1);
+    float x[8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) x[m] = c + 16 * m < count ? w[m] : 0.f;
+    const float step = (xmax - xmin) / (float)num;          // xrange / num; tmp_max = step * i
+    float best = INFINITY;
+    int key = 0;                                            // i * LPR + zp; 0: no candidate scored below infinity
+#pragma unroll 1
+    for (int i = 1; i <= num; ++i) {
+        const float tmp_max = step * (float)i;
+        const float delta = fmaxf(tmp_max / MAXQ, MS_EPS);
+        // the zero point of candidate zp_own, by the pinned lines: one division per lane, read by the row's lanes below
+        const float new_min = 0.f - (float)zp_own * delta;
+        const float zero_own = ms_clamp(0.f - rintf(new_min / delta), MAXQ);
+        float xr[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) xr[m] = rintf(x[m] / delta);
+        float p[LPR];
+#pragma unroll
+        for (int zp = 0; zp < LPR; ++zp) {
+            const float zero = __shfl(zero_own, zp, 16);
+            // clamp(x_round + zero, 0, maxq) - zero == clamp(x_round, -zero, maxq - zero): x_round itself inside the window (small
+            // integers, exact; -0 for +0 leaves d), and the same bound outside it, however large x_round is
+            const float k_lo = 0.f - zero, k_hi = MAXQ - zero;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const float x_q = delta * __builtin_amdgcn_fmed3f(xr[m], k_lo, k_hi);
+                const float term = ms_term(x[m] - x_q);
+                p[zp] = m == 0 ? term : p[zp] + term;
+            }
+        }
+        gr_scatter<LPR, 8>(p, c);
+        if (p[0] < best) {                                  // strict: the first i among equal scores
+            best = p[0];
+            key = i * LPR + zp_own;
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {                // the first minimum in the order (i, zp): the same in all 16 lanes
+        const float ob = __shfl_xor(best, off);
+        const int ok = __shfl_xor(key, off);
+        if (ob < best || (ob == best && ok < key)) {
+            best = ob;
+            key = ok;
+        }
+    }
+    float best_min = xmin, best_max = xmax;                 // the reference's initial pair
+    if (key != 0) {
+        const float tmp_max = step * (float)(key >> BITS);
+        const float delta = fmaxf(tmp_max / MAXQ, MS_EPS);
+        const float zd = (float)(key & (LPR - 1)) * delta;
+        best_min = 0.f - zd;
+        best_max = tmp_max - zd;
+    }
+    const float mn = fminf(best_min, 0.f), mx = fmaxf(best_max, 0.f);
+    s = fmaxf((mx - mn) / MAXQ, MS_EPS);
+    z = ms_clamp(0.f - rintf(mn / s), MAXQ);
+}
+
+// MSE: 0 = the min-max pair (qeft_gptq_rows), 3 / 4 = the search at that width over `num` ranges (qeft_gptq_rows_mse).
 // Err is read AND written (by other threads of the workgroup, a tile earlier): no __restrict__ on it.
+template <int MSE>
 __global__ __launch_bounds__(GR_THREADS) void gptq_rows_kernel(const float* __restrict__ W0, const float* __restrict__ U,
                                                                float* __restrict__ Q, float* Err, float* __restrict__ scale,
-                                                               float* __restrict__ zero, GrGeom G, float maxq) {
+                                                               float* __restrict__ zero, GrGeom G, float maxq, int num) {
     extern __shared__ __attribute__((aligned(16))) float gr_smem[];
     float* Us = gr_smem;                                    // [2][32][GR_LDU]   chunks of U[0:depth, tile]
     float* Es = Us + 2 * GR_BK * GR_LDU;                    // [2][16][GR_LDE]   chunks of Err[rows, 0:depth]
@@ -163,7 +260,10 @@ __global__ __launch_bounds__(GR_THREADS) void gptq_rows_kernel(const float* __re
                 lo = fminf(lo, __shfl_xor(lo, off));
                 hi = fmaxf(hi, __shfl_xor(hi, off));
             }
-            qp_minmax_pair<true>(lo, hi, maxq, s, z);         // the block route's bits: torch's own lines on the device
+            if constexpr (MSE == 0)
+                qp_minmax_pair<true>(lo, hi, maxq, s, z);     // the block route's bits: torch's own lines on the device
+            else
+                gr_mse_pair<MSE>(w, count, c, num, lo, hi, s, z);
 
             // ---- phase 3: the serial sweep
             float qv[8], ev[8];
@@ -194,13 +294,26 @@ __global__ __launch_bounds__(GR_THREADS) void gptq_rows_kernel(const float* __re
     }
 }
 
+template <int MSE>
+static hipError_t gr_launch(const char* variant, const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero,
+                            const GrGeom& G, float maxq, int num, hipStream_t st) {
+    g_last_variant = variant;
+    if (hipError_t e = hipFuncSetAttribute((const void*)gptq_rows_kernel<MSE>, hipFuncAttributeMaxDynamicSharedMemorySize, GR_LDS))
+        return e;
+    hipLaunchKernelGGL(gptq_rows_kernel<MSE>, dim3((unsigned)gr_blocks(G)), dim3(GR_THREADS), GR_LDS, st, (const float*)w0,
+                       (const float*)hinv, (float*)q, (float*)err, (float*)scale, (float*)zero, G, maxq, num);
+    return hipGetLastError();
+}
+
 hipError_t gptq_rows_launch(const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero, const GrGeom& G,
                             float maxq, hipStream_t st) {
-    g_last_variant = "gptq_rows_16";
-    if (hipError_t e = hipFuncSetAttribute((const void*)gptq_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GR_LDS)) return e;
-    hipLaunchKernelGGL(gptq_rows_kernel, dim3((unsigned)gr_blocks(G)), dim3(GR_THREADS), GR_LDS, st, (const float*)w0,
-                       (const float*)hinv, (float*)q, (float*)err, (float*)scale, (float*)zero, G, maxq);
-    return hipGetLastError();
+    return gr_launch<0>("gptq_rows_16", w0, hinv, q, err, scale, zero, G, maxq, 0, st);
+}
+
+hipError_t gptq_rows_mse_launch(const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero, const GrGeom& G,
+                                int bits, int num, hipStream_t st) {
+    if (bits == 4) return gr_launch<4>("gptq_rows_mse_w4", w0, hinv, q, err, scale, zero, G, 15.f, num, st);
+    return gr_launch<3>("gptq_rows_mse_w3", w0, hinv, q, err, scale, zero, G, 7.f, num, st);
 }
 
 }  // namespace qeft

@@ -1543,17 +1543,33 @@ int qeft_quant_pack(const void* w, int ld_w, const void* col_ids, const void* sc
 // ---- the row-owned GPTQ loop (calib_rows.hip)
 int qeft_gptq_rows_blocks(int n) { return n < 1 ? 0 : qeft::gr_blocks(qeft::GrGeom{n, 0, 0, 0, 0}); }
 
-int qeft_gptq_rows(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
-                   int n_nonout, int maxq, int group_size, qeft_stream_t stream) {
+// the refusals both entries share, in their order; QEFT_OK fills G
+static int gr_geom(qeft::GrGeom& G, const void* w0, int ld_w, const void* hinv, int ld_h, const void* q, const void* err,
+                   const void* scale, const void* zero, int n, int k, int n_nonout, int maxq, int group_size, bool num_ok) {
     if (n < 1 || k < qeft::GR_B || k % qeft::GR_B != 0 || k > qeft::GR_MAX_K || ld_w < k || ld_w % 4 != 0 || ld_h < k || ld_h % 4 != 0 ||
-        n_nonout < 1 || n_nonout > k || (k - n_nonout) % 2 != 0 || (maxq != 7 && maxq != 15))
+        n_nonout < 1 || n_nonout > k || (k - n_nonout) % 2 != 0 || (maxq != 7 && maxq != 15) || !num_ok)
         return QEFT_ERR_SHAPE;
     if (group_size != qeft::GR_B) return QEFT_ERR_GROUP;
     if (!w0 || !hinv || !q || !err || !scale || !zero) return QEFT_ERR_NULL;
     if (!aligned16(w0) || !aligned16(hinv) || !aligned16(q) || !aligned16(err)) return QEFT_ERR_ALIGN;
     if (((uintptr_t)scale | (uintptr_t)zero) & 3) return QEFT_ERR_ALIGN;
-    const qeft::GrGeom G{n, k, ld_w, ld_h, n_nonout};
+    G = qeft::GrGeom{n, k, ld_w, ld_h, n_nonout};
+    return QEFT_OK;
+}
+
+int qeft_gptq_rows(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
+                   int n_nonout, int maxq, int group_size, qeft_stream_t stream) {
+    qeft::GrGeom G{};
+    if (int e = gr_geom(G, w0, ld_w, hinv, ld_h, q, err, scale, zero, n, k, n_nonout, maxq, group_size, true)) return e;
     return finish(qeft::gptq_rows_launch(w0, hinv, q, err, scale, zero, G, (float)maxq, (hipStream_t)stream));
+}
+
+int qeft_gptq_rows_mse(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
+                       int n_nonout, int maxq, int group_size, int num, qeft_stream_t stream) {
+    qeft::GrGeom G{};
+    if (int e = gr_geom(G, w0, ld_w, hinv, ld_h, q, err, scale, zero, n, k, n_nonout, maxq, group_size, num >= 1 && num <= qeft::MS_MAX_NUM))
+        return e;
+    return finish(qeft::gptq_rows_mse_launch(w0, hinv, q, err, scale, zero, G, maxq == 15 ? 4 : 3, num, (hipStream_t)stream));
 }
 
 // ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)

@@ -28,6 +28,10 @@ of every side before any measurement, the sides alternating (medians of --reps r
   --only-loop    (> profiles/calib_rows_bench.json.log) the error-feedback loop alone: gptq_reorder with a
                  precomputed hinv, loop = "blocks" against loop = "rows", alternating, at N x K = 4096 x 4096, 11008 x 4096 and
                  4096 x 11008 with 128 outlier columns; then the qeft_gptq_rows launch alone on preallocated outputs
+  --only-rows-mse  (> profiles/calib_rows_mse_bench.json.log) the MSE search inside the one launch:
+                 gptq_reorder with a precomputed hinv at the same three shapes with loop = "blocks", tuning = "mse" (the parent's
+                 only way to the search), loop = "rows", tuning = "minmax" (the price of the search inside the launch) and
+                 loop = "rows", tuning = "mse_fused", alternating; then the qeft_gptq_rows_mse launch alone on preallocated outputs
 One JSON line per part; no threshold.  Every part runs under its own time limit."""
 import argparse
 import faulthandler
@@ -364,6 +368,49 @@ def loop_bench(n, k, r, reps):
     print(json.dumps(res), flush=True)
 
 
+def rows_mse_bench(n, k, r, reps):
+    """The three routes on one given factor, then the one launch of the fused route without the torch around it."""
+    from qeft_amd import _lib
+    from qeft_amd.calibrate import HessianAccumulator, gptq_reorder, hinv_factor
+    g = torch.Generator(device=DEV).manual_seed(2)
+    W = (torch.randn(n, k, generator=g, device=DEV) * 0.02).half()
+    acc = HessianAccumulator(k, DEV)
+    acc.add_batch(rows(2048, k, 3))
+    H = acc.H
+    Hd = H.clone()
+    Hd.diagonal().add_(0.01 * torch.mean(torch.diag(H)))
+    hinv = hinv_factor(Hd)
+    del Hd
+    ids = torch.arange(k, device=DEV)
+    sides = (("blocks_mse", "blocks", "mse"), ("rows_minmax", "rows", "minmax"), ("rows_mse_fused", "rows", "mse_fused"))
+    out = {}
+
+    def side(name, loop, tuning):
+        def run():
+            out[name] = gptq_reorder(W, H, ids, r, hinv=hinv, loop=loop, tuning=tuning).proxy_loss
+        return run
+
+    us, spread = medians_ms([side(*s) for s in sides], reps)
+    W0 = W.float()
+    q, sc = torch.empty_like(W0), torch.empty(n, k // 128, device=DEV)
+    err, ze = torch.empty(n, k - r, device=DEV), torch.empty_like(sc)
+    lib, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
+
+    def launch():
+        _lib.check(lib.qeft_gptq_rows_mse(W0.data_ptr(), k, hinv.data_ptr(), k, q.data_ptr(), err.data_ptr(), sc.data_ptr(),
+                                          ze.data_ptr(), n, k, k - r, 15, 128, 40, st))
+
+    ls, lspread = medians_ms([launch], reps)
+    res = dict(bench="calibrate", op="gptq_rows_mse", n=n, k=k, n_out=r, bits=4, reps=reps, workgroups=lib.qeft_gptq_rows_blocks(n))
+    for (name, _, _), ms, sp in zip(sides, us, spread):
+        res[f"{name}_ms"] = round(ms, 2)
+        res[f"{name}_ms_min_max"] = [round(v, 2) for v in sp]
+        res[f"proxy_loss_{name}"] = out[name]
+    res.update(fused_over_blocks_mse=round(us[2] / us[0], 4), fused_over_rows_minmax=round(us[2] / us[1], 4),
+               fused_launch_alone_ms=round(ls[0], 3), fused_launch_alone_ms_min_max=[round(v, 3) for v in lspread[0]])
+    print(json.dumps(res), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -373,8 +420,14 @@ if __name__ == "__main__":
     ap.add_argument("--only-factor", action="store_true", help="the inverse-Hessian factor alone (profiles/calib_factor_bench.json.log)")
     ap.add_argument("--only-pack", action="store_true", help="the packing step alone (profiles/quant_pack_bench.json.log)")
     ap.add_argument("--only-loop", action="store_true", help="the error-feedback loop alone (profiles/calib_rows_bench.json.log)")
+    ap.add_argument("--only-rows-mse", action="store_true", help="the MSE search inside the launch (profiles/calib_rows_mse_bench.json.log)")
     a = ap.parse_args()
     print(json.dumps(dict(bench="calibrate", device=torch.cuda.get_device_name(0), torch=torch.__version__)), flush=True)
+    if a.only_rows_mse:
+        for n, k in ([(72, 384)] if a.small else [(4096, 4096), (11008, 4096), (4096, 11008)]):
+            with limit(300):
+                rows_mse_bench(n, k, 128, a.reps)
+        sys.exit(0)
     if a.only_loop:
         for n, k in ([(72, 384)] if a.small else [(4096, 4096), (11008, 4096), (4096, 11008)]):
             with limit(300):

@@ -17,15 +17,20 @@ REL_MARGIN = 16 * 2.9e-8
 CASES_W3 = [(0, {}), (11, dict(N=256, K=512, r=128, S=4, T=160))]
 
 
-def make_case(seed, N=32, K=256, r=64, S=4, T=96):
-    """W ~ N(0, 0.02^2) rounded to fp16; X = Z (0.6 I + 0.4 G / sqrt(K)), r random channels x 8, rounded to fp16 [S, T, K]."""
+def make_case(seed, N=32, K=256, r=64, S=4, T=96, dead=()):
+    """W ~ N(0, 0.02^2) rounded to fp16; X = Z (0.6 I + 0.4 G / sqrt(K)), r random channels x 8, rounded to fp16 [S, T, K].
+    dead: positions in dense_ids order (the other channels, ascending) whose channel of X is set to zero before the rounding;
+    nothing else changes, W and the scaled channels are those of the same seed without it."""
     g = torch.Generator().manual_seed(seed)
     W = (torch.randn(N, K, generator=g) * 0.02).half()
     A = 0.6 * torch.eye(K) + 0.4 * torch.randn(K, K, generator=g) / math.sqrt(K)
     X = torch.randn(S, T, K, generator=g) @ A
     hot = torch.randperm(K, generator=g)[:r]
     X[..., hot] *= 8
-    return W, X.half(), torch.sort(hot)[0]
+    hot = torch.sort(hot)[0]
+    if len(dead):
+        X[..., dense_ids(hot, K)[list(dead)]] = 0
+    return W, X.half(), hot
 
 
 def hessian64(X):
@@ -77,9 +82,10 @@ def factor(Hp, dtype, percdamp=0.01):
     return torch.linalg.cholesky(H, upper=True), dead
 
 
-def gptq_reorder(Wp, Hp, n_nonout, dtype, bits=4, percdamp=0.01, g=128, hinv=None):
+def gptq_reorder(Wp, Hp, n_nonout, dtype, bits=4, percdamp=0.01, g=128, hinv=None, params=minmax):
     """recon.py:488-566 with min-max parameters at each group start, on columns already in `ids` order.  Returns
-    (Q [N, K] with the outlier columns carrying their feedback, scale_group, zero_group [N, K / g], hinv)."""
+    (Q [N, K] with the outlier columns carrying their feedback, scale_group, zero_group [N, K / g], hinv).
+    params(x, maxq) -> (scale, zero) [N, 1]: another rule for the pair of a group's current columns."""
     maxq = 2 ** bits - 1
     W = Wp.to(dtype).clone()
     K = W.shape[1]
@@ -90,7 +96,7 @@ def gptq_reorder(Wp, Hp, n_nonout, dtype, bits=4, percdamp=0.01, g=128, hinv=Non
     ss, zz = [], []
     for i1 in range(0, n_nonout, g):
         i2 = min(i1 + g, n_nonout)
-        s, z = minmax(W[:, i1:i2], maxq)
+        s, z = params(W[:, i1:i2], maxq)
         Q1, E1, _ = block_lines(W[:, i1:i2], hinv[i1:i2, i1:i2], s[:, 0], z[:, 0], maxq)
         Q[:, i1:i2] = Q1
         W[:, i2:] -= E1 @ hinv[i1:i2, i2:]

@@ -30,16 +30,37 @@ def layer(N, K, r):
     return W, X, H, ids, W.float()[:, ids].contiguous(), U
 
 
-def run_rows(W0, U, nn, maxq):
+def _placed(t, rows, ld, r0, c0):
+    """The CPU image of t as a view at [r0, c0] of a NaN-filled [rows, ld] buffer (ld None: t itself), and the view's offset."""
+    if ld is None:
+        return t.contiguous(), 0
+    big = torch.full((rows, ld), float("nan"))
+    big[r0:r0 + t.shape[0], c0:c0 + t.shape[1]] = t
+    return big, r0 * ld + c0
+
+
+def run_rows(W0, U, nn, maxq, ld_w=None, ld_h=None, num=None):
+    """One launch of qeft_gptq_rows (num None) or qeft_gptq_rows_mse (num ranges) through the C entry.  ld_w: W0 is a view at
+    [1, 4] of a NaN-filled [n + 2, ld_w] buffer; ld_h: U is a view at [2, 8] of a NaN-filled [k + 3, ld_h] buffer with NaN written
+    below the diagonal inside the view (both offsets are multiples of 4 floats).  The inputs, padding included, must come back
+    with the bits they went in with; the outputs keep their dense strides and carry one NaN guard row that must stay NaN."""
     from qeft_amd import _lib
     n, k = W0.shape
-    w, u = W0.contiguous().to(DEV), U.contiguous().to(DEV)
-    q, err, s, z = (torch.full(shape, float("nan"), device=DEV) for shape in ((n, k), (n, nn), (n, k // 128), (n, k // 128)))
-    _lib.check(_lib.lib().qeft_gptq_rows(w.data_ptr(), k, u.data_ptr(), k, q.data_ptr(), err.data_ptr(), s.data_ptr(), z.data_ptr(),
-                                         n, k, nn, maxq, 128, torch.cuda.current_stream().cuda_stream))
+    nan = float("nan")
+    Uin = U if ld_h is None else torch.where(torch.ones_like(U, dtype=torch.bool).tril(-1), torch.full_like(U, nan), U)
+    (wi, wo), (ui, uo) = _placed(W0, n + 2, ld_w, 1, 4), _placed(Uin, k + 3, ld_h, 2, 8)
+    w, u = wi.to(DEV), ui.to(DEV)
+    q, err, s, z = (torch.full((n + 1, cols), nan, device=DEV) for cols in (k, nn, k // 128, k // 128))
+    args = (w.data_ptr() + 4 * wo, ld_w or k, u.data_ptr() + 4 * uo, ld_h or k, q.data_ptr(), err.data_ptr(), s.data_ptr(), z.data_ptr(),
+            n, k, nn, maxq, 128)
+    st = torch.cuda.current_stream().cuda_stream
+    _lib.check(_lib.lib().qeft_gptq_rows(*args, st) if num is None else _lib.lib().qeft_gptq_rows_mse(*args, num, st))
     torch.cuda.synchronize()
-    assert _lib.last_variant() == "gptq_rows_16" and torch.equal(w.cpu(), W0) and torch.equal(u.cpu(), U)
-    return q.cpu(), err.cpu(), s.cpu(), z.cpu()
+    assert _lib.last_variant() == ("gptq_rows_16" if num is None else f"gptq_rows_mse_w{3 + (maxq == 15)}")
+    assert torch.equal(w.cpu().view(torch.int32), wi.view(torch.int32)) and torch.equal(u.cpu().view(torch.int32), ui.view(torch.int32))
+    out = [t.cpu() for t in (q, err, s, z)]
+    assert all(torch.isnan(t[n]).all() for t in out)
+    return tuple(t[:n].contiguous() for t in out)
 
 
 def assert_identity(W0, q, err, U, nn, what):

@@ -6,23 +6,41 @@ import pytest
 import torch
 
 import calib_ref as R
-from test_gpu_gptq_rows import assert_identity, golden, layer  # noqa: F401  (golden is a fixture)
+from test_gpu_gptq_rows import assert_identity, golden, layer, run_rows  # noqa: F401  (golden is a fixture)
 from test_gpu_mse_search import G, bits_of, candidates
 
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def run_rows_mse(W0, U, nn, maxq, num=40):
-    from qeft_amd import _lib
-    n, k = W0.shape
-    w, u = W0.contiguous().to(DEV), U.contiguous().to(DEV)
-    q, err, s, z = (torch.full(shape, float("nan"), device=DEV) for shape in ((n, k), (n, nn), (n, k // 128), (n, k // 128)))
-    _lib.check(_lib.lib().qeft_gptq_rows_mse(w.data_ptr(), k, u.data_ptr(), k, q.data_ptr(), err.data_ptr(), s.data_ptr(), z.data_ptr(),
-                                             n, k, nn, maxq, 128, num, torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    assert _lib.last_variant() == f"gptq_rows_mse_w{3 + (maxq == 15)}" and torch.equal(w.cpu(), W0) and torch.equal(u.cpu(), U)
-    return q.cpu(), err.cpu(), s.cpu(), z.cpu()
+def run_rows_mse(W0, U, nn, maxq, num=40, ld_w=None, ld_h=None):
+    return run_rows(W0, U, nn, maxq, ld_w=ld_w, ld_h=ld_h, num=num)
+
+
+def assert_the_pairs_are_the_searchs(W0, Ub, outs, groups, bits, num=40):
+    """Criteria (1) to (3) of test_gpu_mse_search for every live group (i1, i2) of a run on a block-diagonal factor, the sweep of
+    the block with the kernel's own pair bit for bit, and the last pair repeated in the groups after the last live one.  An exact
+    tie for the minimum leaves a row in (3): `nxt` is the next DISTINCT score, and the reference's pair is the first candidate's."""
+    q, err, s, z = outs
+    N, maxq = W0.shape[0], 2 ** bits - 1
+    for g, (i1, i2) in enumerate(groups):
+        x, sg, zg = W0[:, i1:i2], s[:, g], z[:, g]
+        scores, pairs = candidates(x, bits, num)
+        best, first, inf = scores.min(0)[0], scores.argmin(0), torch.full_like(scores, float("inf"))
+        member = (bits_of(pairs[:, 0]) == bits_of(sg)) & (bits_of(pairs[:, 1]) == bits_of(zg))
+        mine, nxt = torch.where(member, scores, inf).min(0)[0], torch.where(scores > best, scores, inf).min(0)[0]
+        clear = (best == 0) | (nxt - best >= G * best)
+        ref = pairs[first, :, torch.arange(N)]
+        same = (bits_of(ref[:, 0]) == bits_of(sg)) & (bits_of(ref[:, 1]) == bits_of(zg))
+        excess = torch.where(best > 0, mine / best.clamp_min(1e-300) - 1, mine)
+        print(f"{bits} bits, num {num}, group {g} ({i2 - i1} columns): largest score excess {excess.max().item():.3g}, rows left out "
+              f"of (3) {(~clear).sum().item()} / {N}, rows with another pair than the reference's {(~same).sum().item()}")
+        assert member.any(0).all() and torch.equal(zg, zg.round()) and zg.min() >= 0 and zg.max() <= maxq and sg.min() >= 1e-8   # (1)
+        assert (mine <= (1 + G) * best).all() and (~clear).sum().item() <= 0.1 * N and same[clear].all()                        # (2), (3)
+        Q1, E1, _ = R.block_lines(x, Ub[i1:i2, i1:i2], sg, zg, maxq)        # the sweep, with the kernel's own pair
+        assert torch.equal(q[:, i1:i2], Q1) and torch.equal(err[:, i1:i2], E1)
+    for g in range(len(groups), s.shape[1]):
+        assert torch.equal(bits_of(s[:, g]), bits_of(s[:, len(groups) - 1])) and torch.equal(bits_of(z[:, g]), bits_of(z[:, len(groups) - 1]))
 
 
 @gpu
@@ -32,23 +50,7 @@ def test_the_pair_is_the_searchs_in_every_group(bits):
     N, K, nn, maxq = 24, 384, 254, 2 ** bits - 1
     _, _, _, _, W0, U = layer(N, K, 130)
     Ub = torch.block_diag(*(U[i:i + 128, i:i + 128] for i in range(0, K, 128))).contiguous()
-    q, err, s, z = run_rows_mse(W0, Ub, nn, maxq)
-    for g, (i1, i2) in enumerate([(0, 128), (128, nn)]):
-        x, sg, zg = W0[:, i1:i2], s[:, g], z[:, g]
-        scores, pairs = candidates(x, bits)
-        best, first, inf = scores.min(0)[0], scores.argmin(0), torch.full_like(scores, float("inf"))
-        member = (bits_of(pairs[:, 0]) == bits_of(sg)) & (bits_of(pairs[:, 1]) == bits_of(zg))
-        mine, nxt = torch.where(member, scores, inf).min(0)[0], torch.where(scores > best, scores, inf).min(0)[0]
-        clear = (best == 0) | (nxt - best >= G * best)
-        ref = pairs[first, :, torch.arange(N)]
-        same = (bits_of(ref[:, 0]) == bits_of(sg)) & (bits_of(ref[:, 1]) == bits_of(zg))
-        print(f"{bits} bits, group {g}: largest score excess {(mine / best - 1).max().item():.3g}, rows left out of (3) "
-              f"{(~clear).sum().item()} / {N}, rows with another pair than the reference's {(~same).sum().item()}")
-        assert member.any(0).all() and torch.equal(zg, zg.round()) and zg.min() >= 0 and zg.max() <= maxq and sg.min() >= 1e-8   # (1)
-        assert (mine <= (1 + G) * best).all() and (~clear).sum().item() <= 0.1 * N and same[clear].all()                        # (2), (3)
-        Q1, E1, _ = R.block_lines(x, Ub[i1:i2, i1:i2], sg, zg, maxq)        # the sweep, with the kernel's own pair
-        assert torch.equal(q[:, i1:i2], Q1) and torch.equal(err[:, i1:i2], E1)
-    assert torch.equal(bits_of(s[:, 2]), bits_of(s[:, 1])) and torch.equal(bits_of(z[:, 2]), bits_of(z[:, 1]))
+    assert_the_pairs_are_the_searchs(W0, Ub, run_rows_mse(W0, Ub, nn, maxq), [(0, 128), (128, nn)], bits)
 
 
 @gpu

@@ -900,6 +900,31 @@ int qeft_gptq_rows(const void* w0, int ld_w, const void* hinv, int ld_h, void* q
 int qeft_gptq_rows_mse(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
                        int n_nonout, int maxq, int group_size, int num, qeft_stream_t stream);
 
+/* Per-channel grids, the reference's --groupsize -1: ONE (scale, zero) pair per output row (csrc/calib_rows.hip, csrc/calib_rows.h,
+ * csrc/quant_pack.hip, csrc/quant_pack.h; gptq_reorder / calibrate_linear / rtn_linear(group_size=-1)).
+ * qeft_gptq_rows_pc, qeft_gptq_rows_pc_mse: the launches of qeft_gptq_rows / qeft_gptq_rows_mse -- operands, grid, the lines of a
+ *   block, independence of the rows, reproducibility -- except that scale and zero are fp32 [n] and there is no group_size.  The
+ *   pair is found once per row, before the first block, over the first n_nonout columns of w0 AS GIVEN (dead columns zeroed, no
+ *   feedback yet), and every block is swept with it.  _pc: quant.minmax_params(w0[:, :n_nonout], n_nonout, bits) as torch runs
+ *   it on the device (s = fl((xmax - xmin) * fl(1 / maxq))).  _pc_mse: the search of qeft_mse_search over those n_nonout columns,
+ *   num ranges x 2^bits zero points, the same pinned residual lines, the first minimum in the order (i, zp) winning; a score is
+ *   summed per 128-column tile in qeft_gptq_rows_mse's order and then over the tiles ascending -- this kernel's own fixed order,
+ *   so no bit parity with qeft_mse_search is claimed.  Variants gptq_rows_pc, gptq_rows_pc_mse_w4 / _w3.
+ *   QEFT_ERR_SHAPE as qeft_gptq_rows (num outside 1 .. 40 among it), then QEFT_ERR_NULL, then QEFT_ERR_ALIGN; no QEFT_ERR_GROUP.
+ * qeft_quant_pack_pc: qeft_quant_pack with one pair per row: scale_in / zero_in (both or neither) and scale_out / zero_out are
+ *   fp32 [n], scales / scaled_zeros fp16 [n]; qweight as there, every dead nibble holding the row's z.  Neither given: the pair is
+ *   quant.minmax_params over ALL the row's live columns (s = (xmax - xmin) / maxq, the CPU's bits), found in a first pass over w;
+ *   the codes follow in a second.  The packed buffers are those of QuantLinear.pack on the host with scales [n][1] (codes clamped
+ *   to 0..maxq here).  Variants quant_pack_pc_w4 / _w3.  QEFT_ERR_SHAPE as qeft_quant_pack, then QEFT_ERR_NULL (scale_in without
+ *   zero_in or the reverse among it), then QEFT_ERR_ALIGN; no QEFT_ERR_GROUP. */
+int qeft_gptq_rows_pc(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
+                      int n_nonout, int maxq, qeft_stream_t stream);
+int qeft_gptq_rows_pc_mse(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n,
+                          int k, int n_nonout, int maxq, int num, qeft_stream_t stream);
+int qeft_quant_pack_pc(const void* w, int ld_w, const void* col_ids, const void* scale_in, const void* zero_in, void* qweight,
+                       void* scales, void* scaled_zeros, void* scale_out, void* zero_out, int n, int k, int n_out, int bits,
+                       qeft_stream_t stream);
+
 /* Sampled token end (csrc/decode_sample.hip, qeft_amd/sampling.py). A parameter record is int32 [8] in device memory:
  * temperature (fp32 bits), top_k, top_p (fp32 bits), seed lo, seed hi, 3 reserved zeros.  Per row, in HF's warper order:
  *   temperature T == 0: the argmax (lowest index among equal maxima), bit-identical to qeft_token_end / qeft_token_end_batch;

@@ -12,6 +12,8 @@ GPTQ_OWQ.add_batch / hessian_sorting / fasterquant_reorder; main.py:130-171 for 
                                                             DESIGN.md section 4.23                                 (qeft_gptq_rows)
     module, info = calibrate_linear(..., loop="rows", tuning="mse_fused")   that launch with the MSE search of every block start
                                                             inside it, DESIGN.md section 4.24                  (qeft_gptq_rows_mse)
+    module, info = calibrate_linear(..., group_size=-1)     per-channel, the reference's default: one pair per row, found before
+                                                            the loop, DESIGN.md section 4.26   (qeft_gptq_rows_pc, qeft_quant_pack_pc)
 
 GPU tensors only: the kernels have no CPU path and no torch fallback.  Around them the reference's own torch expressions
 remain: dead columns, damping, the three Cholesky calls (factor="torch", the default), the trailing update `W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]` and the
@@ -30,7 +32,7 @@ from .qlinear import QuantLinear
 from .quant import minmax_params, quantize
 from .reorder import sparse_to_dense_ids
 
-BLOCK = 128          # columns per qeft_gptq_block launch == the only supported group size
+BLOCK = 128          # columns per qeft_gptq_block launch == the only supported group size besides -1 (per-channel)
 
 
 def _stream(dev):
@@ -213,7 +215,8 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
       weight       fp16 [N, K], columns in `ids` order: dequantised values, then the outlier columns WITH the error feedback they
                    received (the reference's Q[:, n_nonout:] = W[:, n_nonout:])
       scale_group, zero_group   fp32 [N, K / 128]: one pair per started group of live columns, the last repeated up to K / 128
-                   (recon.py:560-563); K - n_out need not be a multiple of 128 -- the last block and group are short
+                   (recon.py:560-563); K - n_out need not be a multiple of 128 -- the last block and group are short.
+                   group_size=-1: fp32 [N, 1], the reference's quantizer.scale shape
       out_ids (int32), ids, bits, group_size, n_out
       proxy_loss   tr((W - Q) H (W - Q)^T) on the undamped H in fp64, Q the fp32 values before the rounding to fp16
     tuning: 'minmax' (quant.minmax_params on the block's current columns), 'mse_fused' (below), 'mse' (mse_search: the reference's default search in
@@ -228,7 +231,12 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
     tuning='mse_fused' (with loop='rows' only; qeft_gptq_rows_mse): the reference's search, 40 ranges x
     2^bits zero points over each block's current columns, INSIDE the one launch, in the registers of the 16 lanes that hold the
     row's block.  The same candidates and residuals as 'mse'; the score sums have that kernel's own order, so among near-tied
-    candidates another one may win: its own name, no bit parity with 'mse'."""
+    candidates another one may win: its own name, no bit parity with 'mse'.
+    group_size: 128, or -1 = per-channel, the reference's default: ONE pair per row, found over the row's
+    live columns of the working matrix before the loop (recon.py:504; here after the dead columns are zeroed, which moves neither a
+    min-max that includes 0 nor a score) and used by every block.  loop='blocks' finds it by the tuning's whole-row route and hands
+    it to every launch; loop='rows' finds it in a prologue of the one launch (qeft_gptq_rows_pc, or qeft_gptq_rows_pc_mse for
+    'mse_fused': the search's scores then have that kernel's own order -- tile sums, tiles ascending)."""
     if loop not in ("blocks", "rows"):
         raise ValueError(f"loop = {loop!r}: 'blocks' or 'rows'")
     if tuning == "mse_fused" and loop != "rows":
@@ -237,8 +245,9 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
     if loop == "rows" and tuning not in ("minmax", "mse_fused"):
         raise ValueError(f"tuning = {tuning!r} with loop='rows': the MSE search runs between launches -- use loop='blocks', or "
                          "tuning='mse_fused' for the search inside the one launch")
-    if group_size != BLOCK:
-        raise ValueError(f"group_size = {group_size}: only {BLOCK} is supported (a group must start where a block does)")
+    if group_size not in (BLOCK, -1):
+        raise ValueError(f"group_size = {group_size}: only {BLOCK} is supported (a group must start where a block does), or -1: "
+                         "per-channel, one pair per row")
     if sym:
         raise ValueError("sym=True is not supported: the block kernel clamps to 0..maxq (asymmetric grid only)")
     if bits not in (3, 4):
@@ -258,6 +267,7 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
     ids = ids.to(dev).long()
     maxq = 2 ** bits - 1
     n_nonout = K - n_out
+    per_channel = group_size == -1
 
     W0 = W.float()[:, ids].contiguous()
     Hp = H.float()[ids][:, ids].contiguous()
@@ -284,19 +294,26 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
     if loop == "rows":
         Q = torch.empty_like(Wk)
         err = torch.empty((N, n_nonout), dtype=torch.float32, device=dev)
-        scale_group = torch.empty((N, K // BLOCK), dtype=torch.float32, device=dev)
+        scale_group = torch.empty((N, 1 if per_channel else K // BLOCK), dtype=torch.float32, device=dev)
         zero_group = torch.empty_like(scale_group)
         args = (Wk.data_ptr(), K, hinv.data_ptr(), K, Q.data_ptr(), err.data_ptr(), scale_group.data_ptr(), zero_group.data_ptr(),
-                N, K, n_nonout, maxq, group_size)
-        _lib.check(lib.qeft_gptq_rows_mse(*args, 40, st) if tuning == "mse_fused" else lib.qeft_gptq_rows(*args, st))
+                N, K, n_nonout, maxq)
+        if per_channel:
+            _lib.check(lib.qeft_gptq_rows_pc_mse(*args, 40, st) if tuning == "mse_fused" else lib.qeft_gptq_rows_pc(*args, st))
+        else:
+            _lib.check(lib.qeft_gptq_rows_mse(*args, group_size, 40, st) if tuning == "mse_fused" else
+                       lib.qeft_gptq_rows(*args, group_size, st))
         return _reorder_result(W0, Q, H0, scale_group, zero_group, ids, n_nonout, bits, group_size, n_out)
     Q = torch.zeros_like(Wk)
     scales, zeros = [], []
+    if per_channel:                                     # the reference's find_params before its loop: one pair, every launch
+        scale, zero = (t.contiguous() for t in _params(Wk[:, :n_nonout], bits, tuning))
     for i1 in range(0, n_nonout, BLOCK):
         i2 = min(i1 + BLOCK, n_nonout)
         count = i2 - i1
-        scale, zero = _params(Wk[:, i1:i2], bits, tuning)
-        scale, zero = scale.contiguous(), zero.contiguous()
+        if not per_channel:
+            scale, zero = _params(Wk[:, i1:i2], bits, tuning)
+            scale, zero = scale.contiguous(), zero.contiguous()
         q1 = torch.empty((N, count), dtype=torch.float32, device=dev)
         err1 = torch.empty((N, count), dtype=torch.float32, device=dev)
         _lib.check(lib.qeft_gptq_block(Wk.data_ptr() + 4 * i1, K, hinv.data_ptr() + 4 * (i1 * K + i1), K, scale.data_ptr(),
@@ -306,10 +323,12 @@ def gptq_reorder(W, H, ids, n_out, bits=4, group_size=128, percdamp=0.01, tuning
             Wk[:, i2:] -= err1.matmul(hinv[i1:i2, i2:])
         scales.append(scale)
         zeros.append(zero)
-    for _ in range(K // group_size - len(scales)):
+    for _ in range(K // BLOCK - len(scales)):
         scales.append(scales[-1])
         zeros.append(zeros[-1])
     Q[:, n_nonout:] = Wk[:, n_nonout:]
+    if per_channel:
+        scales, zeros = [scale], [zero]
     return _reorder_result(W0, Q, H0, torch.cat(scales, 1), torch.cat(zeros, 1), ids, n_nonout, bits, group_size, n_out)
 
 
@@ -338,7 +357,7 @@ def calibrate_linear(linear, H, n_out, name, bits=4, group_size=128, frob_norm=T
 
     pack: "host" (the default) copies the reconstruction to the CPU, runs QuantLinear.pack there and copies the module back;
     "device" runs QuantLinear.pack_device (one launch of qeft_quant_pack): the same buffers bit for bit,
-    and no tensor leaves the GPU."""
+    and no tensor leaves the GPU.  group_size=-1: a per-channel layer (scales [1, N]; "device" is qeft_quant_pack_pc)."""
     if pack not in ("host", "device"):
         raise ValueError(f"pack = {pack!r}: 'host' or 'device'")
     W = linear.weight.data
@@ -380,14 +399,15 @@ def rtn_linear(linear, n_out, name, H=None, outidx=None, bits=4, group_size=128,
     n_out > 0: the outlier columns come from select_outliers (diag(H), weighed by frob_norm as in calibrate_linear, or `outidx`
     as given; one of H and outidx is required) and stay fp16; the other columns, in `ids` order, are quantised per 128-column
     group with the min-max parameters of the group's live columns -- gather, search, rounding and packing in ONE launch of
-    qeft_quant_pack (QuantLinear.pack_device in find mode).  The quantinfo namespace has the fields
+    qeft_quant_pack (QuantLinear.pack_device in find mode); group_size=-1: per ROW, over all its live
+    columns, in one launch of qeft_quant_pack_pc.  The quantinfo namespace has the fields
     calibrate_linear returns (proxy_loss is None: no Hessian is needed here; weight is not kept), so the layer saves and loads
     like any other, and the same rule for o_proj / out_proj names applies.  Only tuning="minmax": the MSE search is refused."""
     if tuning != "minmax":
         raise ValueError(f"tuning = {tuning!r}: rtn_linear finds min-max parameters inside the pack launch; the MSE search "
                          "runs only in calibrate_linear")
-    if group_size != BLOCK:
-        raise ValueError(f"group_size = {group_size}: only {BLOCK} is supported")
+    if group_size not in (BLOCK, -1):
+        raise ValueError(f"group_size = {group_size}: only {BLOCK} is supported, or -1: per-channel")
     if bits not in (3, 4):
         raise ValueError(f"bits = {bits}: only 3 and 4 are supported")
     W = linear.weight.data

@@ -67,6 +67,26 @@
 //   from the same key -- the sweep needs the same s and z bits in every lane of the row.  Without a candidate below infinity the
 //   pair is that of (xmin, xmax).  A tile without a live column repeats the last pair; a short last block searches its count
 //   columns.  num is 1 .. 40 (MS_MAX_NUM).
+//
+// qeft_gptq_rows_pc, qeft_gptq_rows_pc_mse    the same launch with ONE pair per row, the reference's --groupsize -1 (DESIGN.md
+//   section 4.26; gptq_reorder(group_size=-1, loop="rows")): scale and zero are fp32 [n], every other operand, the grid, the
+//   workgroup, phases 1 and 3, LDS and every address above are unchanged; phase 2 searches nothing.  The pair is found in
+//   phase 0, per workgroup before tile 0, from W0 itself (dead columns zeroed, no feedback yet -- the reference's find_params
+//   before its loop): thread (row, c) walks its row's live columns c + 16 m of every live tile, W0 at row * ld_w + column with
+//   column < n_nonout.
+//     min-max   the row's extremes over the live columns and 0 (16-lane reduce), then qp_minmax_pair<true>: the bits of
+//               quant.minmax_params(W0[:, :n_nonout], n_nonout, bits) as torch runs it on the device.
+//     MSE       a second pass (it needs xmin / xmax): the search above, num ranges x 2^bits zero points, over the row's n_nonout
+//               columns.  Tiles outer, ranges inner: per (tile, range) the per-lane partials and the reduce-scatter of the tile
+//               search, then lane c adds its zero point's tile sum into its own slot of a score table [num][256] floats in LDS
+//               (40 KiB at num = 40).  The table lies over the Us and Es regions, idle until phase 1 of tile 1, so GR_LDS does not
+//               grow; a lane touches only its own slots (a wave's 64 lanes hit 64 consecutive words), so the pass has no barrier;
+//               one barrier follows it.  No score lives in a dynamically indexed register array (that would be scratch).
+//               A score is: the tile sum in the order stated above, then tiles ascending -- independent of n, the row's index
+//               and the grid; not qeft_mse_search's order (no bit parity with tuning="mse").  The lane then takes the first
+//               minimum over i of its slots (strict <), and the 16-lane arg-min and the closing lines are the tile search's.
+//   The sweep of every tile runs with the row's pair; scale[row] and zero[row] are stored once.  Rows are independent, a rerun
+//   gives the same bits, no workspace, no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -82,6 +102,8 @@ constexpr int GR_LDC = GR_B + 4;                        // row stride of the acc
 constexpr int GR_MAX_K = 1 << 15;
 constexpr int GR_LDS_FLOATS = 2 * GR_BK * GR_LDU + 2 * GR_ROWS * GR_LDE + GR_ROWS * GR_LDC + GR_B * GR_B;
 constexpr int GR_LDS = GR_LDS_FLOATS * 4;               // 115 456 bytes: one workgroup per CU
+constexpr int GR_PC_TABLE_FLOATS = 40 * GR_THREADS;     // the per-channel search's scores [MS_MAX_NUM][256], over Us and Es
+static_assert(GR_PC_TABLE_FLOATS <= 2 * GR_BK * GR_LDU + 2 * GR_ROWS * GR_LDE, "the score table must end before Cs");
 
 struct GrGeom {
     int n, k, ld_w, ld_h, n_nonout;
@@ -93,5 +115,10 @@ hipError_t gptq_rows_launch(const void* w0, const void* hinv, void* q, void* err
                             float maxq, hipStream_t st);
 hipError_t gptq_rows_mse_launch(const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero, const GrGeom& G,
                                 int bits, int num, hipStream_t st);
+// per-channel: scale and zero are fp32 [n]
+hipError_t gptq_rows_pc_launch(const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero, const GrGeom& G,
+                               float maxq, hipStream_t st);
+hipError_t gptq_rows_pc_mse_launch(const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero, const GrGeom& G,
+                                   int bits, int num, hipStream_t st);
 
 }  // namespace qeft

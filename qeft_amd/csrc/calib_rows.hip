@@ -65,58 +65,48 @@ __device__ __forceinline__ void gr_scatter(float (&p)[LPR], int c) {
     }
 }
 
-// The MSE search of one tile (qeft_gptq_rows_mse; the contract and the order of every sum: calib_rows.h), between phase 2 and the
-// sweep, in registers and cross-lane reads alone: no LDS, no barrier, no global address.  w: the lane's 8 block-start columns
-// c + 16 m; xmin / xmax: the row's extremes over the live columns and 0, the same bits in the row's 16 lanes.  A column at or past
-// count enters as 0: its x_round is 0, no zero point clamps it, d is exactly 0 and its term +0, which leaves every sum's bits.
-// Per range i the lane's partial scores of all 2^BITS zero points stay in registers (8 columns, m ascending); a reduce-scatter
-// over lane ^ 8, 4, 2, 1 then leaves lane c with the row's score of zero point c % 2^BITS (at 3 bits the first step is a plain
-// exchange-and-add, so lanes c and c ^ 8 hold the same bits), and the lane keeps the first minimum over i.  One 16-lane arg-min
-// on (score, i 2^BITS + zp) ends the search; every lane then forms the pair from the winning key by the closing lines.
+// The row's scores of ONE range of the search over the lane's 8 columns x (a column outside the live ones enters as 0: its
+// x_round is 0, no zero point clamps it, d is exactly 0 and its term +0, which leaves every sum's bits).  The lane's partial scores
+// of all 2^BITS zero points stay in registers (8 columns, m ascending); a reduce-scatter over lane ^ 8, 4, 2, 1 then leaves lane c
+// with the row's score of zero point c % 2^BITS (at 3 bits the first step is a plain exchange-and-add, so lanes c and c ^ 8 hold
+// the same bits).  Shared by the per-tile search (gr_mse_pair) and the per-channel one (gr_pc_mse_pair): the order of a tile's sum.
 template <int BITS>
-__device__ __forceinline__ void gr_mse_pair(const float (&w)[8], int count, int c, int num, float xmin, float xmax, float& s,
-                                            float& z) {
+__device__ __forceinline__ float gr_mse_score(const float (&x)[8], float delta, int c) {
     constexpr int LPR = 1 << BITS;
     constexpr float MAXQ = (float)(LPR - 1);
-    const int zp_own = c & (LPR - 1);
-    float x[8];
+    // the zero point of candidate c % LPR, by the pinned lines: one division per lane, read by the row's lanes below
+    const float new_min = 0.f - (float)(c & (LPR - 1)) * delta;
+    const float zero_own = ms_clamp(0.f - rintf(new_min / delta), MAXQ);
+    float xr[8];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) x[m] = c + 16 * m < count ? w[m] : 0.f;
-    const float step = (xmax - xmin) / (float)num;          // xrange / num; tmp_max = step * i
-    float best = INFINITY;
-    int key = 0;                                            // i * LPR + zp; 0: no candidate scored below infinity
-#pragma unroll 1
-    for (int i = 1; i <= num; ++i) {
-        const float tmp_max = step * (float)i;
-        const float delta = fmaxf(tmp_max / MAXQ, MS_EPS);
-        // the zero point of candidate zp_own, by the pinned lines: one division per lane, read by the row's lanes below
-        const float new_min = 0.f - (float)zp_own * delta;
-        const float zero_own = ms_clamp(0.f - rintf(new_min / delta), MAXQ);
-        float xr[8];
+    for (int m = 0; m < 8; ++m) xr[m] = rintf(x[m] / delta);
+    float p[LPR];
 #pragma unroll
-        for (int m = 0; m < 8; ++m) xr[m] = rintf(x[m] / delta);
-        float p[LPR];
+    for (int zp = 0; zp < LPR; ++zp) {
+        const float zero = __shfl(zero_own, zp, 16);
+        // clamp(x_round + zero, 0, maxq) - zero == clamp(x_round, -zero, maxq - zero): x_round itself inside the window (small
+        // integers, exact; -0 for +0 leaves d), and the same bound outside it, however large x_round is
+        const float k_lo = 0.f - zero, k_hi = MAXQ - zero;
 #pragma unroll
-        for (int zp = 0; zp < LPR; ++zp) {
-            const float zero = __shfl(zero_own, zp, 16);
-            // clamp(x_round + zero, 0, maxq) - zero == clamp(x_round, -zero, maxq - zero): x_round itself inside the window (small
-            // integers, exact; -0 for +0 leaves d), and the same bound outside it, however large x_round is
-            const float k_lo = 0.f - zero, k_hi = MAXQ - zero;
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const float x_q = delta * __builtin_amdgcn_fmed3f(xr[m], k_lo, k_hi);
-                const float term = ms_term(x[m] - x_q);
-                p[zp] = m == 0 ? term : p[zp] + term;
-            }
-        }
-        gr_scatter<LPR, 8>(p, c);
-        if (p[0] < best) {                                  // strict: the first i among equal scores
-            best = p[0];
-            key = i * LPR + zp_own;
+        for (int m = 0; m < 8; ++m) {
+            const float x_q = delta * __builtin_amdgcn_fmed3f(xr[m], k_lo, k_hi);
+            const float term = ms_term(x[m] - x_q);
+            p[zp] = m == 0 ? term : p[zp] + term;
         }
     }
+    gr_scatter<LPR, 8>(p, c);
+    return p[0];
+}
+
+// The end of a search: each lane holds the first minimum over i of its zero point as (best, key = i 2^BITS + zp; 0: no candidate
+// scored below infinity).  One 16-lane arg-min on (score, key) gives the first minimum in the order (i, zp), the same in all 16
+// lanes; every lane then forms the pair from the winning key by the closing lines.
+template <int BITS>
+__device__ __forceinline__ void gr_mse_close(float best, int key, float step, float xmin, float xmax, float& s, float& z) {
+    constexpr int LPR = 1 << BITS;
+    constexpr float MAXQ = (float)(LPR - 1);
 #pragma unroll
-    for (int off = 1; off < 16; off <<= 1) {                // the first minimum in the order (i, zp): the same in all 16 lanes
+    for (int off = 1; off < 16; off <<= 1) {
         const float ob = __shfl_xor(best, off);
         const int ok = __shfl_xor(key, off);
         if (ob < best || (ob == best && ok < key)) {
@@ -137,9 +127,76 @@ __device__ __forceinline__ void gr_mse_pair(const float (&w)[8], int count, int 
     z = ms_clamp(0.f - rintf(mn / s), MAXQ);
 }
 
+// The MSE search of one tile (qeft_gptq_rows_mse; the contract and the order of every sum: calib_rows.h), between phase 2 and the
+// sweep, in registers and cross-lane reads alone: no LDS, no barrier, no global address.  w: the lane's 8 block-start columns
+// c + 16 m; xmin / xmax: the row's extremes over the live columns and 0, the same bits in the row's 16 lanes.  Per range i one
+// gr_mse_score; the lane keeps the first minimum over i of its zero point, gr_mse_close ends the search.
+template <int BITS>
+__device__ __forceinline__ void gr_mse_pair(const float (&w)[8], int count, int c, int num, float xmin, float xmax, float& s,
+                                            float& z) {
+    constexpr int LPR = 1 << BITS;
+    constexpr float MAXQ = (float)(LPR - 1);
+    float x[8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) x[m] = c + 16 * m < count ? w[m] : 0.f;
+    const float step = (xmax - xmin) / (float)num;          // xrange / num; tmp_max = step * i
+    float best = INFINITY;
+    int key = 0;
+#pragma unroll 1
+    for (int i = 1; i <= num; ++i) {
+        const float tmp_max = step * (float)i;
+        const float delta = fmaxf(tmp_max / MAXQ, MS_EPS);
+        const float sc = gr_mse_score<BITS>(x, delta, c);
+        if (sc < best) {                                    // strict: the first i among equal scores
+            best = sc;
+            key = i * LPR + (c & (LPR - 1));
+        }
+    }
+    gr_mse_close<BITS>(best, key, step, xmin, xmax, s, z);
+}
+
+// The per-channel MSE search of phase 0 (qeft_gptq_rows_pc_mse; calib_rows.h): the same candidates over the row's WHOLE live
+// width, nn columns of W0 in tiles of 128.  Tiles outer, ranges inner: per (tile, range) one gr_mse_score, whose result lane c
+// adds into its own running score slots[(i - 1) * GR_THREADS] -- a table [num][256] in LDS, a lane's slots its own alone (no
+// barrier in here, no bank conflict: a wave's 64 lanes touch 64 consecutive words), so no score lives in an indexed register.
+// A score is therefore: the tile sum in gr_mse_score's order, then tiles ascending.  The lane then walks its slots, i ascending.
+template <int BITS>
+__device__ __forceinline__ void gr_pc_mse_pair(const float* __restrict__ wrow, float* slots, int nn, int c, int num, float xmin,
+                                               float xmax, float& s, float& z) {
+    constexpr int LPR = 1 << BITS;
+    constexpr float MAXQ = (float)(LPR - 1);
+    const float step = (xmax - xmin) / (float)num;
+    for (int cb = 0; cb < nn; cb += GR_B) {
+        float x[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) x[m] = cb + c + 16 * m < nn ? wrow[cb + c + 16 * m] : 0.f;
+#pragma unroll 1
+        for (int i = 1; i <= num; ++i) {
+            const float tmp_max = step * (float)i;
+            const float delta = fmaxf(tmp_max / MAXQ, MS_EPS);
+            const float sc = gr_mse_score<BITS>(x, delta, c);
+            float* slot = slots + (i - 1) * GR_THREADS;
+            *slot = cb == 0 ? sc : *slot + sc;
+        }
+    }
+    float best = INFINITY;
+    int key = 0;
+#pragma unroll 1
+    for (int i = 1; i <= num; ++i) {
+        const float sc = slots[(i - 1) * GR_THREADS];
+        if (sc < best) {                                    // strict: the first i among equal scores
+            best = sc;
+            key = i * LPR + (c & (LPR - 1));
+        }
+    }
+    gr_mse_close<BITS>(best, key, step, xmin, xmax, s, z);
+}
+
 // MSE: 0 = the min-max pair (qeft_gptq_rows), 3 / 4 = the search at that width over `num` ranges (qeft_gptq_rows_mse).
+// PC: per-channel (qeft_gptq_rows_pc / _pc_mse) -- ONE pair per row, found in phase 0 from W0's live columns before tile 0;
+// scale and zero are then [n], phase 2 searches nothing and every tile's sweep runs with the row's pair.
 // Err is read AND written (by other threads of the workgroup, a tile earlier): no __restrict__ on it.
-template <int MSE>
+template <int MSE, bool PC>
 __global__ __launch_bounds__(GR_THREADS) void gptq_rows_kernel(const float* __restrict__ W0, const float* __restrict__ U,
                                                                float* __restrict__ Q, float* Err, float* __restrict__ scale,
                                                                float* __restrict__ zero, GrGeom G, float maxq, int num) {
@@ -161,6 +218,35 @@ __global__ __launch_bounds__(GR_THREADS) void gptq_rows_kernel(const float* __re
     float* qrow = Q + (size_t)rc * G.k;
     float* erow = Err + (size_t)rc * nn;
     float s = 1.f, z = 0.f;                                 // the last live group's pair (every call has a live tile 0)
+
+    if constexpr (PC) {
+        // ---- phase 0: the row's one pair, from W0's live columns (c + 16 m of every live tile) before any feedback
+        float lo = 0.f, hi = 0.f;                           // min and max do not round: any order gives the row's
+        for (int cb = 0; cb < nn; cb += GR_B)
+#pragma unroll
+            for (int m = 0; m < 8; ++m)
+                if (cb + c + 16 * m < nn) {
+                    const float v = wrow[cb + c + 16 * m];
+                    lo = fminf(lo, v);
+                    hi = fmaxf(hi, v);
+                }
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) {            // the row's 16 lanes
+            lo = fminf(lo, __shfl_xor(lo, off));
+            hi = fmaxf(hi, __shfl_xor(hi, off));
+        }
+        if constexpr (MSE == 0) {
+            qp_minmax_pair<true>(lo, hi, maxq, s, z);
+        } else {
+            // the score table [num][256] lies over Us and Es (GR_PC_TABLE_FLOATS <= their size), idle until tile 1's phase 1
+            gr_pc_mse_pair<MSE>(wrow, gr_smem + tid, nn, c, num, lo, hi, s, z);
+            __syncthreads();                                // every lane is done with its slots before the region is staged into
+        }
+        if (live && c == 0) {
+            scale[row] = s;
+            zero[row] = z;
+        }
+    }
 
     for (int t = 0; t < ng; ++t) {
         const int cb = t * GR_B;
@@ -248,22 +334,24 @@ __global__ __launch_bounds__(GR_THREADS) void gptq_rows_kernel(const float* __re
         for (int m = 0; m < 8; ++m) w[m] = w[m] - Cs[srow * GR_LDC + c + 16 * m];
 
         if (sweep) {
-            float lo = 0.f, hi = 0.f;                       // min and max do not round: any order gives the row's
+            if constexpr (!PC) {
+                float lo = 0.f, hi = 0.f;                   // min and max do not round: any order gives the row's
 #pragma unroll
-            for (int m = 0; m < 8; ++m)
-                if (c + 16 * m < count) {
-                    lo = fminf(lo, w[m]);
-                    hi = fmaxf(hi, w[m]);
+                for (int m = 0; m < 8; ++m)
+                    if (c + 16 * m < count) {
+                        lo = fminf(lo, w[m]);
+                        hi = fmaxf(hi, w[m]);
+                    }
+#pragma unroll
+                for (int off = 1; off < 16; off <<= 1) {    // the row's 16 lanes
+                    lo = fminf(lo, __shfl_xor(lo, off));
+                    hi = fmaxf(hi, __shfl_xor(hi, off));
                 }
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {        // the row's 16 lanes
-                lo = fminf(lo, __shfl_xor(lo, off));
-                hi = fmaxf(hi, __shfl_xor(hi, off));
+                if constexpr (MSE == 0)
+                    qp_minmax_pair<true>(lo, hi, maxq, s, z);     // the block route's bits: torch's own lines on the device
+                else
+                    gr_mse_pair<MSE>(w, count, c, num, lo, hi, s, z);
             }
-            if constexpr (MSE == 0)
-                qp_minmax_pair<true>(lo, hi, maxq, s, z);     // the block route's bits: torch's own lines on the device
-            else
-                gr_mse_pair<MSE>(w, count, c, num, lo, hi, s, z);
 
             // ---- phase 3: the serial sweep
             float qv[8], ev[8];
@@ -286,7 +374,7 @@ __global__ __launch_bounds__(GR_THREADS) void gptq_rows_kernel(const float* __re
 #pragma unroll
             for (int m = 0; m < 8; ++m) qrow[cb + c + 16 * m] = w[m];
         }
-        if (live && c == 0) {                               // a tile without a live column repeats the last pair
+        if (!PC && live && c == 0) {                        // a tile without a live column repeats the last pair
             scale[(size_t)row * ng + t] = s;
             zero[(size_t)row * ng + t] = z;
         }
@@ -294,13 +382,13 @@ __global__ __launch_bounds__(GR_THREADS) void gptq_rows_kernel(const float* __re
     }
 }
 
-template <int MSE>
+template <int MSE, bool PC = false>
 static hipError_t gr_launch(const char* variant, const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero,
                             const GrGeom& G, float maxq, int num, hipStream_t st) {
     g_last_variant = variant;
-    if (hipError_t e = hipFuncSetAttribute((const void*)gptq_rows_kernel<MSE>, hipFuncAttributeMaxDynamicSharedMemorySize, GR_LDS))
+    if (hipError_t e = hipFuncSetAttribute((const void*)gptq_rows_kernel<MSE, PC>, hipFuncAttributeMaxDynamicSharedMemorySize, GR_LDS))
         return e;
-    hipLaunchKernelGGL(gptq_rows_kernel<MSE>, dim3((unsigned)gr_blocks(G)), dim3(GR_THREADS), GR_LDS, st, (const float*)w0,
+    hipLaunchKernelGGL((gptq_rows_kernel<MSE, PC>), dim3((unsigned)gr_blocks(G)), dim3(GR_THREADS), GR_LDS, st, (const float*)w0,
                        (const float*)hinv, (float*)q, (float*)err, (float*)scale, (float*)zero, G, maxq, num);
     return hipGetLastError();
 }
@@ -314,6 +402,17 @@ hipError_t gptq_rows_mse_launch(const void* w0, const void* hinv, void* q, void*
                                 int bits, int num, hipStream_t st) {
     if (bits == 4) return gr_launch<4>("gptq_rows_mse_w4", w0, hinv, q, err, scale, zero, G, 15.f, num, st);
     return gr_launch<3>("gptq_rows_mse_w3", w0, hinv, q, err, scale, zero, G, 7.f, num, st);
+}
+
+hipError_t gptq_rows_pc_launch(const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero, const GrGeom& G,
+                               float maxq, hipStream_t st) {
+    return gr_launch<0, true>("gptq_rows_pc", w0, hinv, q, err, scale, zero, G, maxq, 0, st);
+}
+
+hipError_t gptq_rows_pc_mse_launch(const void* w0, const void* hinv, void* q, void* err, void* scale, void* zero, const GrGeom& G,
+                                   int bits, int num, hipStream_t st) {
+    if (bits == 4) return gr_launch<4, true>("gptq_rows_pc_mse_w4", w0, hinv, q, err, scale, zero, G, 15.f, num, st);
+    return gr_launch<3, true>("gptq_rows_pc_mse_w3", w0, hinv, q, err, scale, zero, G, 7.f, num, st);
 }
 
 }  // namespace qeft

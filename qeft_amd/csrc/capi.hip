@@ -1523,33 +1523,54 @@ int qeft_hinv_factor(void* a, int ld, void* u, int* info, int k, qeft_stream_t s
 }
 
 // ---- quantise and pack (quant_pack.hip)
-int qeft_quant_pack(const void* w, int ld_w, const void* col_ids, const void* scale_in, const void* zero_in, void* qweight,
-                    void* scales, void* scaled_zeros, void* scale_out, void* zero_out, int n, int k, int n_out, int bits,
-                    int group_size, qeft_stream_t stream) {
+// the refusals both entries share, in their order (group_size < 0: the per-channel entry, which has no GROUP step); QEFT_OK fills G
+static int qp_geom(qeft::QpGeom& G, const void* w, int ld_w, const void* col_ids, const void* scale_in, const void* zero_in,
+                   const void* qweight, const void* scales, const void* scaled_zeros, const void* scale_out, const void* zero_out, int n,
+                   int k, int n_out, int bits, int group_size) {
     if ((bits != 3 && bits != 4) || n < qeft::QP_ROWS || n % qeft::QP_ROWS != 0 || n > qeft::QP_MAX_N || k < qeft::QP_GROUP ||
         k % qeft::QP_GROUP != 0 || k > qeft::QP_MAX_K || ld_w < k || (!col_ids && ld_w % 8 != 0) || n_out < 0 || n_out % 2 != 0 ||
         n_out >= k || (bits == 3 && n_out % qeft::QP_GROUP != 0))
         return QEFT_ERR_SHAPE;
-    if (group_size != qeft::QP_GROUP) return QEFT_ERR_GROUP;
+    if (group_size >= 0 && group_size != qeft::QP_GROUP) return QEFT_ERR_GROUP;
     if (!w || !qweight || !scales || !scaled_zeros || (scale_in == nullptr) != (zero_in == nullptr)) return QEFT_ERR_NULL;
     if (!aligned16(qweight) || (!col_ids && !aligned16(w))) return QEFT_ERR_ALIGN;
     if (((uintptr_t)w | (uintptr_t)scales | (uintptr_t)scaled_zeros) & 1) return QEFT_ERR_ALIGN;
     if (((uintptr_t)col_ids | (uintptr_t)scale_in | (uintptr_t)zero_in | (uintptr_t)scale_out | (uintptr_t)zero_out) & 3) return QEFT_ERR_ALIGN;
-    const qeft::QpGeom G{n, k, ld_w, n_out, bits};
+    G = qeft::QpGeom{n, k, ld_w, n_out, bits};
+    return QEFT_OK;
+}
+
+int qeft_quant_pack(const void* w, int ld_w, const void* col_ids, const void* scale_in, const void* zero_in, void* qweight,
+                    void* scales, void* scaled_zeros, void* scale_out, void* zero_out, int n, int k, int n_out, int bits,
+                    int group_size, qeft_stream_t stream) {
+    qeft::QpGeom G{};
+    if (int e = qp_geom(G, w, ld_w, col_ids, scale_in, zero_in, qweight, scales, scaled_zeros, scale_out, zero_out, n, k, n_out, bits,
+                        group_size < 0 ? 0 : group_size))
+        return e;
     return finish(qeft::quant_pack_launch(w, col_ids, scale_in, zero_in, qweight, scales, scaled_zeros, scale_out, zero_out, G,
                                           (hipStream_t)stream));
+}
+
+int qeft_quant_pack_pc(const void* w, int ld_w, const void* col_ids, const void* scale_in, const void* zero_in, void* qweight,
+                       void* scales, void* scaled_zeros, void* scale_out, void* zero_out, int n, int k, int n_out, int bits,
+                       qeft_stream_t stream) {
+    qeft::QpGeom G{};
+    if (int e = qp_geom(G, w, ld_w, col_ids, scale_in, zero_in, qweight, scales, scaled_zeros, scale_out, zero_out, n, k, n_out, bits, -1))
+        return e;
+    return finish(qeft::quant_pack_pc_launch(w, col_ids, scale_in, zero_in, qweight, scales, scaled_zeros, scale_out, zero_out, G,
+                                             (hipStream_t)stream));
 }
 
 // ---- the row-owned GPTQ loop (calib_rows.hip)
 int qeft_gptq_rows_blocks(int n) { return n < 1 ? 0 : qeft::gr_blocks(qeft::GrGeom{n, 0, 0, 0, 0}); }
 
-// the refusals both entries share, in their order; QEFT_OK fills G
+// the refusals the four entries share, in their order (group_size < 0: a per-channel entry, no GROUP step); QEFT_OK fills G
 static int gr_geom(qeft::GrGeom& G, const void* w0, int ld_w, const void* hinv, int ld_h, const void* q, const void* err,
                    const void* scale, const void* zero, int n, int k, int n_nonout, int maxq, int group_size, bool num_ok) {
     if (n < 1 || k < qeft::GR_B || k % qeft::GR_B != 0 || k > qeft::GR_MAX_K || ld_w < k || ld_w % 4 != 0 || ld_h < k || ld_h % 4 != 0 ||
         n_nonout < 1 || n_nonout > k || (k - n_nonout) % 2 != 0 || (maxq != 7 && maxq != 15) || !num_ok)
         return QEFT_ERR_SHAPE;
-    if (group_size != qeft::GR_B) return QEFT_ERR_GROUP;
+    if (group_size >= 0 && group_size != qeft::GR_B) return QEFT_ERR_GROUP;
     if (!w0 || !hinv || !q || !err || !scale || !zero) return QEFT_ERR_NULL;
     if (!aligned16(w0) || !aligned16(hinv) || !aligned16(q) || !aligned16(err)) return QEFT_ERR_ALIGN;
     if (((uintptr_t)scale | (uintptr_t)zero) & 3) return QEFT_ERR_ALIGN;
@@ -1560,16 +1581,32 @@ static int gr_geom(qeft::GrGeom& G, const void* w0, int ld_w, const void* hinv, 
 int qeft_gptq_rows(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
                    int n_nonout, int maxq, int group_size, qeft_stream_t stream) {
     qeft::GrGeom G{};
-    if (int e = gr_geom(G, w0, ld_w, hinv, ld_h, q, err, scale, zero, n, k, n_nonout, maxq, group_size, true)) return e;
+    if (int e = gr_geom(G, w0, ld_w, hinv, ld_h, q, err, scale, zero, n, k, n_nonout, maxq, group_size < 0 ? 0 : group_size, true)) return e;
     return finish(qeft::gptq_rows_launch(w0, hinv, q, err, scale, zero, G, (float)maxq, (hipStream_t)stream));
 }
 
 int qeft_gptq_rows_mse(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
                        int n_nonout, int maxq, int group_size, int num, qeft_stream_t stream) {
     qeft::GrGeom G{};
-    if (int e = gr_geom(G, w0, ld_w, hinv, ld_h, q, err, scale, zero, n, k, n_nonout, maxq, group_size, num >= 1 && num <= qeft::MS_MAX_NUM))
+    if (int e = gr_geom(G, w0, ld_w, hinv, ld_h, q, err, scale, zero, n, k, n_nonout, maxq, group_size < 0 ? 0 : group_size,
+                        num >= 1 && num <= qeft::MS_MAX_NUM))
         return e;
     return finish(qeft::gptq_rows_mse_launch(w0, hinv, q, err, scale, zero, G, maxq == 15 ? 4 : 3, num, (hipStream_t)stream));
+}
+
+int qeft_gptq_rows_pc(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n, int k,
+                      int n_nonout, int maxq, qeft_stream_t stream) {
+    qeft::GrGeom G{};
+    if (int e = gr_geom(G, w0, ld_w, hinv, ld_h, q, err, scale, zero, n, k, n_nonout, maxq, -1, true)) return e;
+    return finish(qeft::gptq_rows_pc_launch(w0, hinv, q, err, scale, zero, G, (float)maxq, (hipStream_t)stream));
+}
+
+int qeft_gptq_rows_pc_mse(const void* w0, int ld_w, const void* hinv, int ld_h, void* q, void* err, void* scale, void* zero, int n,
+                          int k, int n_nonout, int maxq, int num, qeft_stream_t stream) {
+    qeft::GrGeom G{};
+    if (int e = gr_geom(G, w0, ld_w, hinv, ld_h, q, err, scale, zero, n, k, n_nonout, maxq, -1, num >= 1 && num <= qeft::MS_MAX_NUM))
+        return e;
+    return finish(qeft::gptq_rows_pc_mse_launch(w0, hinv, q, err, scale, zero, G, maxq == 15 ? 4 : 3, num, (hipStream_t)stream));
 }
 
 // ---- fused lm_head + cross-entropy pieces (lm_head_nll.hip)

@@ -42,6 +42,17 @@
 //   Every global address: W at (row < n) * ld_w + (col < k), col a multiple of 8 on the 16-byte route (ld_w % 8 == 0, base
 //   aligned) or clamp(col_ids[col], 0, k - 1); qweight at qp_q4_off / qp_q3_off, proven inside by qp_*_elems below; the
 //   parameter arrays at row * G + group or group * n + row with row < n, group < G.
+//
+// qeft_quant_pack_pc    the same operand, modes, pinned lines, code layouts and clamp with ONE pair per row (per-channel, the
+//   reference's --groupsize -1): scale_in / zero_in and scale_out / zero_out are fp32 [n], scales /
+//   scaled_zeros fp16 [n] (a QuantLinear's [1][n]).  Find mode: quant.minmax_params over ALL the row's live columns and 0
+//   (qp_minmax_pair, the quotient: the CPU's bits); every dead nibble holds the row's min(max(z, 0), maxq).
+//   Split of the work -- a wave that owns "16 rows x one group" cannot know the row's extremes: a workgroup of QPC_WAVES waves
+//   owns 16 rows, wave v takes their groups v, v + QPC_WAVES, ..; lane = chunk * 16 + row as above.  Find mode is two passes:
+//   pass 1 takes each wave's extremes over the live columns of its groups (4-lane reduce), one exchange through LDS
+//   ([2][QPC_WAVES][16] floats) and ONE barrier give every lane the row's; pass 2 quantises and packs with the per-group body
+//   above, reading w again.  Given mode is pass 2 alone (the barrier is not compiled in).  Wave 0 writes the 16 pairs.  Grid n / 16.
+//   Addresses: W and qweight as above (group < k / 128, row < n), the parameter arrays at row < n.  A rerun gives the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,6 +64,8 @@ constexpr int QP_GROUP = 128;                           // the only group size
 constexpr int QP_ROWS = 16;                             // rows of a wave
 constexpr int QP_WAVES = 4;                             // groups of a block
 constexpr int QP_THREADS = 64 * QP_WAVES;
+constexpr int QPC_WAVES = 16;                           // per-channel: waves of a workgroup, sharing one row set's groups
+constexpr int QPC_THREADS = 64 * QPC_WAVES;
 constexpr int QP_MAX_N = 1 << 20;                       // grid x = n / 16
 constexpr int QP_MAX_K = 1 << 20;                       // grid y = k / 512
 
@@ -95,5 +108,8 @@ __device__ __forceinline__ void qp_minmax_pair(float lo, float hi, float maxq, f
 // ---- host side: quant_pack.hip.  col_ids, scale_in / zero_in (both or neither), scale_out, zero_out may be null.
 hipError_t quant_pack_launch(const void* w, const void* col_ids, const void* scale_in, const void* zero_in, void* qweight, void* scales,
                              void* scaled_zeros, void* scale_out, void* zero_out, const QpGeom& G, hipStream_t st);
+// per-channel: the parameter arrays hold one entry per row
+hipError_t quant_pack_pc_launch(const void* w, const void* col_ids, const void* scale_in, const void* zero_in, void* qweight,
+                                void* scales, void* scaled_zeros, void* scale_out, void* zero_out, const QpGeom& G, hipStream_t st);
 
 }  // namespace qeft

@@ -328,7 +328,9 @@ def quant_pack(weight, scales=None, zeros=None, n_out=0, bits=4, group_size=128,
     nearest with quant.minmax_params found per group over its live columns.  The last n_out columns stay fp16 elsewhere.
     col_ids int32 [K]: column j of the operand is weight[:, col_ids[j]] (the gather of calibrate.select_outliers' ids).
     qweight: int16 [N / 4, K] at 4 bits, int32 [N / 16, (K - n_out) / 128 * 192] at 3; scales16, scaled_zeros16: fp16 [K / 128, N];
-    scale32, zero32: fp32 [N, K / 128], the given tensors or what was found.  GPU tensors only, no torch fallback."""
+    scale32, zero32: fp32 [N, K / 128], the given tensors or what was found.  GPU tensors only, no torch fallback.
+    group_size=-1: per-channel, one launch of qeft_quant_pack_pc -- one pair per row over all its live
+    columns; scales / zeros and scale32 / zero32 are then fp32 [N, 1], scales16 / scaled_zeros16 fp16 [1, N]."""
     _need(isinstance(weight, torch.Tensor) and weight.is_cuda, "weight must be a GPU tensor (qeft_quant_pack has no CPU path)")
     _need(weight.dtype == torch.float16 and weight.dim() == 2, "expected a 2-d Half weight")
     _need((scales is None) == (zeros is None), "scales and zeros: both (given mode) or neither (find mode)")
@@ -337,7 +339,7 @@ def quant_pack(weight, scales=None, zeros=None, n_out=0, bits=4, group_size=128,
     w = weight if weight.stride(1) == 1 and weight.stride(0) >= k else weight.contiguous()
     if col_ids is None and (w.stride(0) % 8 != 0 or w.data_ptr() % 16 != 0):
         w = w.contiguous()
-    groups = k // group_size if group_size > 0 else 0
+    groups = 1 if group_size == -1 else k // group_size if group_size > 0 else 0
     find = scales is None
     if find:
         scale32 = torch.empty((n, groups), dtype=torch.float32, device=dev)
@@ -356,11 +358,14 @@ def quant_pack(weight, scales=None, zeros=None, n_out=0, bits=4, group_size=128,
     scales16 = torch.empty((groups, n), dtype=torch.float16, device=dev)
     scaled_zeros16 = torch.empty((groups, n), dtype=torch.float16, device=dev)
     ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().qeft_quant_pack(
-            w.data_ptr(), w.stride(0), ptr(col_ids), None if find else scale32.data_ptr(), None if find else zero32.data_ptr(),
+    args = (w.data_ptr(), w.stride(0), ptr(col_ids), None if find else scale32.data_ptr(), None if find else zero32.data_ptr(),
             qweight.data_ptr(), scales16.data_ptr(), scaled_zeros16.data_ptr(), scale32.data_ptr() if find else None,
-            zero32.data_ptr() if find else None, n, k, n_out, bits, group_size, _stream(weight)))
+            zero32.data_ptr() if find else None, n, k, n_out, bits)
+    with torch.cuda.device(dev):
+        if group_size == -1:
+            _lib.check(_lib.lib().qeft_quant_pack_pc(*args, _stream(weight)))
+        else:
+            _lib.check(_lib.lib().qeft_quant_pack(*args, group_size, _stream(weight)))
     return qweight, scales16, scaled_zeros16, scale32, zero32
 
 

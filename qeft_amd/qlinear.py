@@ -238,8 +238,9 @@ class QuantLinear(nn.Module):
         section 4.22) plus the outlier slice, with no tensor leaving the device.  linear.weight.data fp16 [N, K] on the GPU,
         its columns in packing order -- or gathered by col_ids (int32 [K]) inside the launch; scales / zeros fp32 [N, K / 128]
         as for pack(), or both None: round to nearest, the min-max parameters found per group on the spot.  Returns the fp32
-        (scale, zero) used.  Where pack() leaves a code outside 0..maxq to spill into its neighbours, this clamps it."""
-        assert self.group_size == 128, "pack_device: group size 128 only"
+        (scale, zero) used.  A per-channel layer (group_size == infeatures): scales / zeros fp32 [N, 1], one launch of
+        qeft_quant_pack_pc.  Where pack() leaves a code outside 0..maxq to spill into its neighbours, this clamps it."""
+        assert self.group_size in (128, self.infeatures), "pack_device: group size 128 or per-channel (== infeatures) only"
         self.sym = sym
         if scales is None and sym:
             raise ValueError("pack_device: sym=True needs given scales / zeros (find mode is the asymmetric min-max grid)")
@@ -250,7 +251,7 @@ class QuantLinear(nn.Module):
         if linear.bias is not None:
             self.bias = linear.bias.detach().to(device=W.device, dtype=self.dtype)
         self.qweight, self.scales, self.scaled_zeros, scale32, zero32 = qeft_cuda.quant_pack(
-            W, scales, zeros, r, self.bits, self.group_size, col_ids)
+            W, scales, zeros, r, self.bits, 128 if self.group_size == 128 else -1, col_ids)
         if r > 0:
             self.oweight = (W[:, -r:] if col_ids is None else W[:, col_ids[-r:].long()]).contiguous()
             self.oweight_interleaved = qeft_cuda.pack_oweight_device(self.oweight)

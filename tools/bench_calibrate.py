@@ -32,6 +32,9 @@ of every side before any measurement, the sides alternating (medians of --reps r
                  gptq_reorder with a precomputed hinv at the same three shapes with loop = "blocks", tuning = "mse" (the parent's
                  only way to the search), loop = "rows", tuning = "minmax" (the price of the search inside the launch) and
                  loop = "rows", tuning = "mse_fused", alternating; then the qeft_gptq_rows_mse launch alone on preallocated outputs
+  --only-pc      (> profiles/calib_pc_bench.json.log) per-channel grids, group_size = -1: gptq_reorder with
+                 a precomputed hinv at the same three shapes, loop = "rows" / "blocks" x min-max / the search, alternating; the
+                 qeft_gptq_rows_pc and qeft_gptq_rows_pc_mse launches alone; qeft_quant_pack_pc given and find in windows of launches
 One JSON line per part; no threshold.  Every part runs under its own time limit."""
 import argparse
 import faulthandler
@@ -411,6 +414,68 @@ def rows_mse_bench(n, k, r, reps):
     print(json.dumps(res), flush=True)
 
 
+def pc_bench(n, k, r, reps, inner):
+    """Per-channel grids (group_size=-1; DESIGN.md section 4.26): the four routes of gptq_reorder on one given factor, alternating;
+    each rows launch alone on preallocated outputs; then qeft_quant_pack_pc in windows of `inner` launches on eight matrices."""
+    from qeft_amd import _lib
+    from qeft_amd.calibrate import HessianAccumulator, gptq_reorder, hinv_factor
+    g = torch.Generator(device=DEV).manual_seed(2)
+    W = (torch.randn(n, k, generator=g, device=DEV) * 0.02).half()
+    acc = HessianAccumulator(k, DEV)
+    acc.add_batch(rows(2048, k, 3))
+    H = acc.H
+    Hd = H.clone()
+    Hd.diagonal().add_(0.01 * torch.mean(torch.diag(H)))
+    hinv = hinv_factor(Hd)
+    del Hd
+    ids = torch.arange(k, device=DEV)
+    sides = (("rows_minmax", "rows", "minmax"), ("rows_mse_fused", "rows", "mse_fused"), ("blocks_minmax", "blocks", "minmax"),
+             ("blocks_mse", "blocks", "mse"))
+    out = {}
+
+    def side(name, loop, tuning):
+        def run():
+            out[name] = gptq_reorder(W, H, ids, r, group_size=-1, hinv=hinv, loop=loop, tuning=tuning)
+        return run
+
+    us, spread = medians_ms([side(*s) for s in sides], reps)
+    W0 = W.float()
+    q, err = torch.empty_like(W0), torch.empty(n, k - r, device=DEV)
+    sc, ze = torch.empty(n, device=DEV), torch.empty(n, device=DEV)
+    lib, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
+    args = (W0.data_ptr(), k, hinv.data_ptr(), k, q.data_ptr(), err.data_ptr(), sc.data_ptr(), ze.data_ptr(), n, k, k - r, 15)
+    ls, lspread = medians_ms([lambda: _lib.check(lib.qeft_gptq_rows_pc(*args, st)),
+                              lambda: _lib.check(lib.qeft_gptq_rows_pc_mse(*args, 40, st))], reps)
+    res = dict(bench="calibrate", op="per_channel", n=n, k=k, n_out=r, bits=4, reps=reps, inner=inner)
+    for (name, _, _), ms, sp in zip(sides, us, spread):
+        res[f"{name}_ms"] = round(ms, 2)
+        res[f"{name}_ms_min_max"] = [round(v, 2) for v in sp]
+        res[f"proxy_loss_{name}"] = out[name].proxy_loss
+    for name, ms, sp in zip(("rows_pc", "rows_pc_mse"), ls, lspread):
+        res[f"{name}_launch_alone_ms"] = round(ms, 3)
+        res[f"{name}_launch_alone_ms_min_max"] = [round(v, 3) for v in sp]
+    Wq, scale, zero = out["rows_minmax"].weight, out["rows_minmax"].scale_group.contiguous(), out["rows_minmax"].zero_group.contiguous()
+    del out
+    copies = [Wq] + [Wq.clone() for _ in range(7)]
+    qw = torch.empty(n // 4, k, dtype=torch.int16, device=DEV)
+    s16, z16 = (torch.empty(1, n, dtype=torch.float16, device=DEV) for _ in range(2))
+    s32, z32 = torch.empty_like(scale), torch.empty_like(zero)
+
+    def window(find):
+        def run():
+            for i in range(inner):
+                _lib.check(lib.qeft_quant_pack_pc(copies[i % 8].data_ptr(), k, None, None if find else scale.data_ptr(),
+                                                  None if find else zero.data_ptr(), qw.data_ptr(), s16.data_ptr(), z16.data_ptr(),
+                                                  s32.data_ptr() if find else None, z32.data_ptr() if find else None, n, k, r, 4, st))
+        return run
+
+    ks, kspread = medians_ms([window(False), window(True)], reps)
+    for name, ms, sp in zip(("given", "find"), ks, kspread):
+        res[f"quant_pack_pc_{name}_us"] = round(ms * 1e3 / inner, 2)
+        res[f"quant_pack_pc_{name}_us_min_max"] = [round(v * 1e3 / inner, 2) for v in sp]
+    print(json.dumps(res), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -421,8 +486,14 @@ if __name__ == "__main__":
     ap.add_argument("--only-pack", action="store_true", help="the packing step alone (profiles/quant_pack_bench.json.log)")
     ap.add_argument("--only-loop", action="store_true", help="the error-feedback loop alone (profiles/calib_rows_bench.json.log)")
     ap.add_argument("--only-rows-mse", action="store_true", help="the MSE search inside the launch (profiles/calib_rows_mse_bench.json.log)")
+    ap.add_argument("--only-pc", action="store_true", help="per-channel grids, group_size=-1 (profiles/calib_pc_bench.json.log)")
     a = ap.parse_args()
     print(json.dumps(dict(bench="calibrate", device=torch.cuda.get_device_name(0), torch=torch.__version__)), flush=True)
+    if a.only_pc:
+        for n, k in ([(72, 384)] if a.small else [(4096, 4096), (11008, 4096), (4096, 11008)]):
+            with limit(300):
+                pc_bench(n - n % 16, k, 128, a.reps, 8 if a.small else 2000)
+        sys.exit(0)
     if a.only_rows_mse:
         for n, k in ([(72, 384)] if a.small else [(4096, 4096), (11008, 4096), (4096, 11008)]):
             with limit(300):

@@ -236,6 +236,21 @@ int qeft_rope_attn_decode(const void* q, const void* k, const void* v, const voi
                           int tab_rows, void* k_cache, void* v_cache, const int* pos, const int* out_pos, void* out,
                           void* workspace, int n_split, int n_heads, int n_kv_heads, int max_seq, qeft_stream_t stream);
 
+/* The same step for LONG caches: the parameter list and the meaning of every operand of qeft_rope_attn_decode (both rotary forms by
+ * tab_rows, out_pos, the fp16 caches [n_kv][max_seq][128]), with 16 <= max_seq <= 1048576, max_seq % 16 == 0 and n_split in
+ * {1, 2, 4, .., 64}.  The kernel (csrc/decode_attn_long.hip) keeps nothing per position: n_kv_heads * n_split blocks, each
+ * streaming one contiguous range of ONE kv head's rows once for all n_heads / n_kv_heads query heads of the group, online softmax
+ * with fp32 statistics, scores and P.V on the matrix unit (P rounded to fp16).  Row *pos of both caches is written (k rotated, v as
+ * given) and no other cache element; *pos outside [0, max_seq) makes the launch a no-op.  n_split > 1 needs `workspace`:
+ * qeft_attn_long_workspace_bytes(n_heads, n_split) bytes, 16-byte aligned, ZERO before the first call, not shared by launches that
+ * may overlap; a workspace sized for n_split = 64 serves every n_split in any order.  The result is deterministic for a given
+ * n_split.  Refusals, in this order: QEFT_ERR_SHAPE (tab_rows, heads, max_seq, n_split), QEFT_ERR_NULL (any operand but out_pos;
+ * workspace only for n_split > 1), QEFT_ERR_ALIGN (k_cache, v_cache, workspace). */
+int qeft_attn_long_workspace_bytes(int n_heads, int n_split);   /* 0 for n_split == 1 or bad arguments */
+int qeft_rope_attn_decode_long(const void* q, const void* k, const void* v, const void* cos_tab, const void* sin_tab,
+                               int tab_rows, void* k_cache, void* v_cache, const int* pos, const int* out_pos, void* out,
+                               void* workspace, int n_split, int n_heads, int n_kv_heads, int max_seq, qeft_stream_t stream);
+
 /* The same step on the REFERENCE's cache layout, for the `qeft_cuda.single_query_attention` boundary
  * (qeft/kernel/qeft_cuda.cpp:23-26, ft_attention.cpp:110-181; caller ftllama_modeling.py:139-153):
  *   k_cache_ft  fp16 [n_kv][128/8][max_seq][8]   (FasterTransformer key layout, ft_attention.cpp:131-133)

@@ -128,6 +128,8 @@ class BatchDecodeEngine:
     MULTI = llama.DecodeEngine.MULTI
 
     def __init__(self, engine, max_batch=8, use_graph=True):
+        if getattr(engine, "long_ctx", False):
+            raise ValueError(engine._long_needs("batched decoding (BatchDecodeEngine)"))
         why = batch_unsupported(engine)
         if why:
             raise RuntimeError(why)

@@ -13,6 +13,7 @@
 #include "gemv_v3.h"
 #include "decode_rows.h"
 #include "decode_kv8.h"
+#include "decode_attn_long.h"
 #include "prefill_attn.h"
 #include "attn_train.h"
 #include "train_glue.h"
@@ -657,6 +658,23 @@ int qeft_rope_attn_decode(const void* q, const void* k, const void* v, const voi
     if (!aligned16(k_cache) || !aligned16(v_cache) || !aligned16(workspace)) return QEFT_ERR_ALIGN;
     return finish(qeft::rope_attn_decode_launch(q, k, v, cos_tab, sin_tab, k_cache, v_cache, pos, out_pos, out, workspace,
                                                 n_heads, n_kv_heads, max_seq, n_split, tab_rows, (hipStream_t)stream));
+}
+
+int qeft_attn_long_workspace_bytes(int n_heads, int n_split) {
+    if (!qeft::attn_long_shape_ok(n_heads, 1, n_split, 16)) return 0;
+    return (int)qeft::attn_long_workspace_bytes(n_heads, n_split);
+}
+
+int qeft_rope_attn_decode_long(const void* q, const void* k, const void* v, const void* cos_tab, const void* sin_tab,
+                               int tab_rows, void* k_cache, void* v_cache, const int* pos, const int* out_pos, void* out,
+                               void* workspace, int n_split, int n_heads, int n_kv_heads, int max_seq, qeft_stream_t stream) {
+    if (tab_rows != 1 && tab_rows < max_seq) return QEFT_ERR_SHAPE;
+    if (!qeft::attn_long_shape_ok(n_heads, n_kv_heads, n_split, max_seq)) return QEFT_ERR_SHAPE;
+    if (!q || !k || !v || !cos_tab || !sin_tab || !k_cache || !v_cache || !pos || !out) return QEFT_ERR_NULL;
+    if (n_split > 1 && !workspace) return QEFT_ERR_NULL;
+    if (!aligned16(k_cache) || !aligned16(v_cache) || !aligned16(workspace)) return QEFT_ERR_ALIGN;
+    return finish(qeft::rope_attn_decode_long_launch(q, k, v, cos_tab, sin_tab, k_cache, v_cache, pos, out_pos, out, workspace,
+                                                     n_heads, n_kv_heads, max_seq, n_split, tab_rows, (hipStream_t)stream));
 }
 
 static int sqa_impl(const void* q, const void* k, const void* v, const void* cos_tab, const void* sin_tab, int tab_rows, void* k_cache_ft,

@@ -526,6 +526,7 @@ def _prefill_pass(model, tokens, engine, start, attn, head=True):
 
 
 KV_DTYPES = ("fp16", "fp8")
+ATTN_CEILING = 32768        # cache rows qeft_rope_attn_decode and its m-row / batch / e4m3 siblings take (include/qeft_hip.h)
 
 
 def kv_cache_arrays(kv_dtype, lead, n_kv, max_seq, dev):
@@ -681,6 +682,13 @@ class DecodeEngine:
         self.logits = torch.zeros(1, s.vocab, **f16)
         if kv_dtype == "fp8" and tp:
             raise ValueError(self._kv8_needs("this engine is tensor-parallel"))
+        # Past ATTN_CEILING cache rows the one-token attention is the streaming kernel (qeft_rope_attn_decode_long, DESIGN.md
+        # §4.4d): fp16 cache, one GPU.  The kernels that keep the ceiling refuse here, before any launch.
+        self.long_ctx = s.max_seq > ATTN_CEILING
+        if self.long_ctx and kv_dtype == "fp8":
+            raise ValueError(self._long_needs('kv_dtype="fp8" (qeft_kv8_store_rows and the e4m3 attention)'))
+        if self.long_ctx and tp:
+            raise ValueError(self._long_needs("a tensor-parallel engine"))
         # per layer: fp16 K, V; or e4m3 K codes, V codes (kc, vc) with their fp32 row scales (ks, vs)
         caches = [kv_cache_arrays(kv_dtype, (), self.kv_heads_l, s.max_seq, dev) for _ in range(s.n_layers)]
         self.kc, self.vc = [c[0] for c in caches], [c[1] for c in caches]
@@ -697,6 +705,8 @@ class DecodeEngine:
         self.attn_split_forced = int(forced) if forced else None
         self.attn_split = self.attn_split_forced or 1
         nws = max(self.lib.qeft_attn_workspace_bytes(self.heads_l, 8), self.lib.qeft_attn_kv8_workspace_bytes(self.heads_l, 8, 1))
+        if self.long_ctx:
+            nws = self.lib.qeft_attn_long_workspace_bytes(self.heads_l, 64)
         self.attn_ws = torch.zeros(nws // 4, dtype=torch.float32, device=dev)
         self.host_pos = 0          # host mirror of self.pos (chooses the split; any split is correct at any position)
         self.graphs = {}
@@ -872,6 +882,10 @@ class DecodeEngine:
     def _kv8_needs(why):
         return f'kv_dtype="fp8" runs on the single-GPU v3 engine only ({why})'
 
+    def _long_needs(self, what):
+        return (f"max_seq = {self.m.shape.max_seq} is above {ATTN_CEILING}: beyond it only the one-token attention of an fp16 "
+                f"cache on one GPU has a kernel (step / run / extend / prefill / score); {what} keeps the ceiling")
+
     def store_kv(self, li, k, v, T, start=0):
         """llama.prefill's hand-over: layer li's rotated keys and values [T, n_kv, 128] fp16 -> cache positions [start, start + T)."""
         fp8 = self.kv_dtype == "fp8"
@@ -888,7 +902,23 @@ class DecodeEngine:
     def _split_for(self, pos):
         if self.attn_split_forced:
             return self.attn_split_forced
+        if self.long_ctx:
+            # The streaming kernel launches kv_heads x S blocks and one block fills a CU.  From the measured table (DESIGN.md
+            # §4.4d): S doubles while the blocks cover at most half of the 256 CUs and a range keeps 256 positions; the last
+            # doubling, to one block on every CU, pays once a range keeps 4096.  More blocks than CUs were slower everywhere.
+            half = 1
+            while half < 64 and self.kv_heads_l * half * 2 <= 128:
+                half *= 2
+            sp = 1
+            while sp < half and pos + 1 >= 2 * sp * 256:
+                sp *= 2
+            if sp == half and sp < 64 and pos + 1 >= 2 * sp * 4096:
+                sp *= 2
+            return sp
         return 1 if pos < 256 else (4 if pos < 1536 else 8)
+
+    # positions at which _split_for may change (precapture): the short route's two, the long route's powers of two
+    SPLIT_EDGES = (256, 1536) + tuple(512 << i for i in range(10))
 
     def reset(self):
         self.set_position(0)
@@ -1068,10 +1098,11 @@ class DecodeEngine:
                                                           self.heads_l * 128, self.attn_ws.data_ptr(), self.attn_split, 1,
                                                           self.heads_l, self.kv_heads_l, self.m.shape.max_seq, 1, st))
             return
-        _lib.check(self.lib.qeft_rope_attn_decode(q, k, v, rope, rope + 64 * 4, 1, self.kc[li].data_ptr(), self.vc[li].data_ptr(),
-                                                  self.pos.data_ptr(), att_pos.data_ptr() if att_pos is not None else None,
-                                                  out.data_ptr(), self.attn_ws.data_ptr(), self.attn_split, self.heads_l,
-                                                  self.kv_heads_l, self.m.shape.max_seq, st))
+        entry = self.lib.qeft_rope_attn_decode_long if self.long_ctx else self.lib.qeft_rope_attn_decode
+        _lib.check(entry(q, k, v, rope, rope + 64 * 4, 1, self.kc[li].data_ptr(), self.vc[li].data_ptr(),
+                         self.pos.data_ptr(), att_pos.data_ptr() if att_pos is not None else None,
+                         out.data_ptr(), self.attn_ws.data_ptr(), self.attn_split, self.heads_l,
+                         self.kv_heads_l, self.m.shape.max_seq, st))
 
     def _head(self, h32, hn, logits, m, st):
         """Final RMSNorm of the fp32 residual rows at h32 (a device pointer) + fp16 lm_head -> logits[:m]: one launch where the
@@ -1226,8 +1257,8 @@ class DecodeEngine:
     def precapture(self, max_pos):
         """Capture the graphs of every attention split the positions [host_pos, max_pos) will use (so that none is
         captured inside a timed region)."""
-        for sp in sorted({self._split_for(p) for p in (self.host_pos, 255, 256, 1535, 1536, max_pos - 1)
-                          if self.host_pos <= p < max_pos}):
+        edges = [p for e in self.SPLIT_EDGES for p in (e - 2, e - 1, e)]
+        for sp in sorted({self._split_for(p) for p in (self.host_pos, *edges, max_pos - 1) if self.host_pos <= p < max_pos}):
             if self._step_key(sp) not in self.graphs:
                 self.capture(split=sp)
 
@@ -1397,6 +1428,8 @@ class DecodeEngine:
 
     def _verify_pass(self, tokens, greedy):
         """One verify pass; greedy: False (teacher-forced rows), True (accept by the argmax) or "sample" (accept by the draw)."""
+        if self.long_ctx:
+            raise ValueError(self._long_needs("the verify pass (verify / verify_sample)"))
         why = self._verify_unsupported()
         if why:
             raise RuntimeError(why)
